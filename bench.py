@@ -5,13 +5,17 @@ T_NeRF(256, 4) (eval-mode BN, random weights of the reference's init law), synth
 A "step" = one pass of the hot path over one ray batch: per-ray group network (season classes + sky colour)
 -> fused field network (sampling + PE + SIREN MLP + heads) -> wave-scan compositing, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, pre-warms, warms up, times K steps and prints the headline line.  `--full` adds every other
+measurement (see below and `--help`); `--dump-outputs DIR` writes the outputs of the last timed step as DIR/<name>.npy (float32;
+inputs and weights are seeded, so two builds can be compared output for output).
 
 N > 1: one process per GPU.  Either the driver starts the ranks (`python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N`: RANK / WORLD_SIZE set), or a bare `python bench.py --gpus N` starts them itself - as a CHILD process running
 torch.distributed.run, before this process has touched the GPU - and exits with the child's status.
 
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries the training step of BASELINE configs[2] as extra keys
+Prints ONE JSON line on rank 0.  At N = 1 with `--full` the line also carries the training step of BASELINE configs[2] as extra keys
 (`train_ms_per_step`, `train_roofline`, `train_cpu_baseline`; MSE colour loss = the reference-pinned path), the evaluator-seam
 time (`eval_seam_ms`) and the 512 x 512 x 96 + 12-step sweep render, all measured outside the headline timed region.  Multi-GPU: every rank renders its own 4096-ray tile (weak scaling, rays are
 independent) and the rendered RGB tiles are all-gathered over RCCL, 8 steps per asynchronous collective (the tile
@@ -652,7 +656,20 @@ def main():
     ap.add_argument("--bn_sync", default="local", choices=["local", "global"],
                     help="--workload train, N > 1: BatchNorm statistics per rank, or over the global batch (RCCL all-reduces of the "
                          "per-layer statistics: the single-process reference's semantics)")
+    ap.add_argument("--full", action="store_true",
+                    help="render workload: also measure everything beside the headline (repeated blocks, per-mode table, W = 512 / converged / exact-solar rows, "
+                         "512x512 sweep, evaluator seam, training steps, CPU baseline); the --no-* options above then leave parts out. Without it a run "
+                         "sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="render workload: after the timed steps write what the last timed step computed (RGB, per-ray class weights and sky colour, "
+                         "per-sample density / solar visibility / colour) as DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.workload != "render" or a.aux_kernel or a.backend == "gloo"):
+        ap.error("--dump-outputs applies to the render workload")
+    if not a.full and a.workload == "render":          # a plain render run: the headline alone
+        a.headline_only = a.no_aux = True
     if a.headline_only:
         a.no_sweep = a.no_train = a.no_cpu_baseline = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -769,8 +786,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     field_ms = float(np.mean([ev0[i].elapsed_time(ev1[i]) for i in range(a.steps)]))
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left in its output buffers (nothing below has run yet); under N > 1 the all-gathered RGB of every rank
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        outs = {"rgb": tg.gathered(a.steps - 1) if use_dist else rgb_local, "class_weights": cls, "sky_color_raw": sky_raw, "sky_color": sky,
+                "rho": rho.view(R, S), "solar_vis": sv.view(R, S), "color": col.view(R, S, 3)}
+        for k, v in outs.items():
+            np.save(os.path.join(a.dump_outputs, k + ".npy"), v.detach().float().cpu().numpy())
     blocks = None
-    if rank == 0 and world == 1 and not use_dist:
+    if rank == 0 and world == 1 and not use_dist and a.full:
         # the same K-step block 25 more times (outside the headline region): one 17 ms sample on a chip whose clock depends on its load
         # history is a thin basis - median and spread of the per-step time go into the line as extra keys
         bl = []

@@ -1,7 +1,7 @@
 """Comparison of the pipelined full-tile row GEMMs against the general row kernel: the 32x32x16 form bit for bit (same arithmetic,
 same summation order), the 16x16x32 form to fp32 summation rounding.  One child process per mode (read once per process).
 usage (GPU box): python3 tools/compare_gemm_paths.py"""
-import os, subprocess, sys
+import os, shutil, subprocess, sys, tempfile
 import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 if len(sys.argv) > 1:
@@ -69,15 +69,15 @@ if len(sys.argv) > 1:
         out[f"fz{it}dgrad_{M}_{n_out}_{n_cols}_{act}_{bn}"] = gi.cpu().numpy()
     np.savez(sys.argv[1], **out)
     sys.exit(0)
-os.makedirs("/tmp/cmp", exist_ok=True)
+TMP = tempfile.mkdtemp(prefix="cmp_gemm_")        # private to this run: the outputs of the three child processes
 # m0: general kernel; m1: full-tile 32x32x16 kernel (bit-identical to m0); m2: full-tile 16x16x32 kernel where the launcher picks it
 # (same products, the k terms of a 32-k step summed in another order: equal to fp32 summation rounding, never bitwise by design)
 # (SNERF_CMP_WREG=1 with SNERF_LIB pointing at a library built with -DSNERF_WITH_WREG=1 (python tools/variants.py build gemm16.hip wreg="-DSNERF_WITH_WREG=1"):
 #  mode 2 additionally routes the eligible shapes to the experimental gemm_wreg_kernel, weights in registers - not part of the shipped library)
 for mode, env_ in (("0", {"SNERF_GEMM_FULL": "0"}), ("1", {"SNERF_GEMM_FULL": "1", "SNERF_GEMM16": "0"}),
                    ("2", {"SNERF_GEMM_FULL": "1", "SNERF_GEMM16": "1", "SNERF_GEMM_WREG": os.environ.get("SNERF_CMP_WREG", "0")})):
-    subprocess.check_call([sys.executable, __file__, f"/tmp/cmp/m{mode}.npz"], env=dict(os.environ, **env_))
-a, b, c = np.load("/tmp/cmp/m0.npz"), np.load("/tmp/cmp/m1.npz"), np.load("/tmp/cmp/m2.npz")
+    subprocess.check_call([sys.executable, __file__, os.path.join(TMP, f"m{mode}.npz")], env=dict(os.environ, **env_))
+a, b, c = (np.load(os.path.join(TMP, f"m{m}.npz")) for m in "012")
 bad = n16 = 0
 for k in a.files:
     if "stats" in k or "sums" in k:      # double atomics over workgroups: order-dependent in the last bits
@@ -92,4 +92,5 @@ for k in a.files:
     bad += (not ok) + (not ok16)
 print("outputs the 16x16x32 kernel produced (differ in the last bits):", n16)
 print("mismatches:", bad)
+shutil.rmtree(TMP, ignore_errors=True)
 sys.exit(1 if (bad or n16 == 0) else 0)

@@ -2,8 +2,8 @@
 """On the GPU box, repo root:  python3 tools/profile_round.py TAG [--precision i8x3] [--no-train]
 
 Collects under gpurun_out/round_TAG/ what profiles/ needs for one build:
-  bench.json            the default `python3 bench.py` line
-  kernel_stats.csv      rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline --no-sweep --no-train --no-aux` (only 4096-ray launches of
+  bench.json            the `python3 bench.py --full` line
+  kernel_stats.csv      rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline --no-sweep --no-train --no-aux` (only 4096-ray launches of
                         the dominant kernel, so its AverageNs IS roofline.kernel_ms)
   pmc.txt               PMC passes, one counter set per run (--pmc only, no tracing flags): FETCH_SIZE, WRITE_SIZE, the MFMA set
   traffic.json          HBM bytes per launch of the dominant kernel (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE)
@@ -54,7 +54,7 @@ def main():
     out = os.path.join(REPO, "gpurun_out", "round_" + tag)
     os.makedirs(out, exist_ok=True)
     with open(os.path.join(out, "bench.json"), "w") as f:
-        subprocess.call(["python3", "bench.py"] + (["--precision", prec] if "--precision" in sys.argv else []), stdout=f, stderr=open(os.path.join(out, "bench.err"), "w"), cwd=REPO)
+        subprocess.call(["python3", "bench.py", "--full"] + (["--precision", prec] if "--precision" in sys.argv else []), stdout=f, stderr=open(os.path.join(out, "bench.err"), "w"), cwd=REPO)
     bench = json.load(open(os.path.join(out, "bench.json")))
     kname = bench["roofline"]["kernel"].split(" ")[0]                      # e.g. snerf::mlp_i8_kernel<0,256,0>
     key = kname.split("::")[-1].split("<")[0]                               # mlp_i8_kernel
@@ -65,7 +65,7 @@ def main():
 
     # kernel stats of the same command (only the 4096-ray launches)
     d = os.path.join(out, "prof")
-    sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", "python3", "bench.py", "--precision", prec,
+    sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", "python3", "bench.py", "--full", "--precision", prec,
         "--no-cpu-baseline", "--no-sweep", "--no-train", "--no-aux"], os.path.join(out, "prof.log"))
     st = find(d, "*kernel_stats.csv")
     rec = []
