@@ -409,7 +409,7 @@ static int field_launch(const snerf_model* m, int variant, MlpArgs& a, const sne
         // two waves per SIMD wherever the activations leave room for it (kernels_i8x2.hip); SNERF_I8_ONE_WAVE=1: A/B switch
         static const bool one_wave = getenv("SNERF_I8_ONE_WAVE") != nullptr;
         if (m->W <= 256 && !one_wave) e = launch_mlp_i8x2(m->W, variant, a, m->n_cu, (hipStream_t)stream);
-        else e = launch_mlp_i8(PROG_FIELD, m->W, variant, a, m->n_cu, (hipStream_t)stream);
+        else e = launch_mlp_i8(m->W, variant, a, m->n_cu, (hipStream_t)stream);
     } else if (ks_width(m->W)) {
         a.stream = m->d_stream_ks;
         a.stream_bytes = (uint32_t)field_variant_chunks_ks(m->W, m->C, variant) * kChunkBytes;

@@ -100,8 +100,12 @@ struct SweepArgs {
     float *base, *shadow_adjust, *raw_shadow;   // [R,3], [R,3], [R]
 };
 hipError_t launch_sweep(const SweepArgs& a, hipStream_t st);
+// workgroup tiles of a fused field launch: `rays` rays per tile in VARIANT 3 (ray visibility), `pts` points per tile otherwise
+__host__ __device__ inline int64_t field_tiles(int64_t n, int variant, int pts, int rays) { return variant == 3 ? (n + rays - 1) / rays : (n + pts - 1) / pts; }
+// persistent launch of a fused kernel: min(n_tiles, n_cu) workgroups (at least one) of `block` threads with `lds_bytes` of dynamic LDS (kernels.hip)
+hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st);
-hipError_t launch_mlp_i8(int prog, int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);      // kernels_i8.hip
+hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)
 int field_variant_chunks_i8(int W, int C, int variant);
 hipError_t launch_mlp_i8x2(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8x2.hip (W <= 256)
 hipError_t launch_mlp_ks(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_ks.hip (W = 512, bf16x3, K split over wave pairs)

@@ -125,26 +125,11 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
     // bias table -> LDS (once per workgroup)
     for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
 
-    // prologue: RING_D-2 chunks in flight (the refill target trails the consumer by two slots)
-    Ring rg;
-    rg.rd = 0;
-    rg.cur = 0;
-    rg.goff = 0;
-    {
-        uint32_t wr = 0;
-#pragma unroll
-        for (int c = 0; c < RING_D - 2; ++c) {
-            dma_chunk(A.stream, rg.goff, lds, wr, wave, lane);
-            rg.goff += kChunkBytes;
-            if (rg.goff >= A.stream_bytes) rg.goff = 0;
-            wr += kChunkBytes;
-        }
-        rg.wr = wr;   // = (RING_D-2)*chunk: at the step that publishes chunk k this is the slot of chunk k-2
-    }
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
     __syncthreads();   // bias table visible (drains the prologue DMAs once; harmless)
 
-    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 4 rays (one per wave), walked in `passes` steps of 32 samples
-    const int64_t n_tiles = VARIANT == 3 ? (A.n + 3) / 4 : (A.n + TILE_PTS - 1) / TILE_PTS;
+    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 4 rays (one per wave), walked in passes of 32 samples
+    const int64_t n_tiles = field_tiles(A.n, VARIANT, TILE_PTS, 4);
     const int passes = VARIANT == 3 ? (A.n_samples + 31) / 32 : 1;
     int pass = 0;
     RaySum rs;
@@ -155,33 +140,11 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
         const int64_t g = VARIANT == 3 ? 0 : nc / A.group_size;
 
         if constexpr (PROG == PROG_FIELD) {
-            // ---- sample position (misc.py:234-247 fused): top*(1-t) + bot*t, two roundings + one add, no fma
             float x0, x1, x2;
-            if constexpr (VARIANT == 3) {
-                raysum_point(rs, A, tile, 4, wave, pass, lane, x0, x1, x2);
-            } else if (A.points) {
-                x0 = A.points[nc * 3]; x1 = A.points[nc * 3 + 1]; x2 = A.points[nc * 3 + 2];
-            } else {
-                const int64_t r = nc / A.n_samples;
-                const int s = (int)(nc - r * A.n_samples);
-                const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-                x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-                x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-                x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
-            }
-            // every per-tile input is loaded here, before the MFMA chain: a plain load in the middle of the chain
-            // makes hipcc drain the LDS-DMA pipeline with vmcnt(0)
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-            float pcls[C_MAX];
-#pragma unroll
-            for (int c = 0; c < C_MAX; ++c) pcls[c] = 0.f;
-            if constexpr (VARIANT <= 1) { s0 = A.sun[g * 3]; s1 = A.sun[g * 3 + 1]; s2 = A.sun[g * 3 + 2]; }
-            if constexpr (VARIANT == 0) {
-                if (A.classes) {
-#pragma unroll
-                    for (int c = 0; c < C_MAX; ++c) if (c < C) pcls[c] = A.classes[g * C + c];
-                }
-            }
+            if constexpr (VARIANT == 3) raysum_point(rs, A, tile, 4, wave, pass, lane, x0, x1, x2);
+            else field_point(A, nc, x0, x1, x2);
+            float s0, s1, s2, pcls[C_MAX];
+            field_tile_inputs<VARIANT>(A, g, s0, s1, s2, pcls);
             Frag pe[PEPOS_KS];
             make_pe_pos(x0, x1, x2, h, pe);
 
@@ -232,12 +195,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
 #undef LAYER
             // ---- output non-linearities (T_NeRF_net_v2.py:91-98), lane-half 0 holds the head rows
             if constexpr (VARIANT == 3) {
-                raysum_add(rs, A, tile, 4, wave, pass, lane, rho_raw, x0, x1, x2);
-                if (++pass == passes || raysum_saturated(rs, A, tile * 4 + wave, wave, 4, lane, (__attribute__((address_space(3))) float*)(bias_lds + A.bias_floats))) {
-                    raysum_end(rs, A, tile, 4, wave, lane);
-                    pass = 0;
-                    tile += gridDim.x;
-                }
+                RAYSUM_PASS_END(rs, A, tile, pass, passes, 4, wave, wave, 4, true, lane, rho_raw, x0, x1, x2, bias_lds + A.bias_floats);
             } else {
                 if (h == 0 && valid) store_field_outputs<VARIANT>(A.out, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, sv_raw, adj, pcls);
                 tile += gridDim.x;
@@ -665,17 +623,20 @@ hipError_t launch_ray_grid(const RayGridArgs& a, hipStream_t st) {
 
 // =====================================================================================================
 // launchers
-template <int PROG, int W, int VARIANT, bool FAST = false>
-static hipError_t launch_mlp_t(const MlpArgs& a, int n_cu, hipStream_t st) {
-    const int lds_bytes = RING_BYTES + a.bias_floats * 4 + kVoteBytes;
-    const int64_t n_tiles = VARIANT == 3 ? (a.n + 3) / 4 : (a.n + TILE_PTS - 1) / TILE_PTS;
+hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st) {
     int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
     if (grid < 1) grid = 1;
-    auto k = mlp_kernel<PROG, W, VARIANT, FAST>;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_bytes, st, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, st, a);
     return hipGetLastError();
+}
+
+int mlp_lds_bytes(int bias_floats) { return RING_BYTES + bias_floats * 4 + kVoteBytes; }
+
+template <int PROG, int W, int VARIANT, bool FAST = false>
+static hipError_t launch_mlp_t(const MlpArgs& a, int n_cu, hipStream_t st) {
+    return launch_fused(mlp_kernel<PROG, W, VARIANT, FAST>, field_tiles(a.n, VARIANT, TILE_PTS, 4), 256, mlp_lds_bytes(a.bias_floats), a, n_cu, st);
 }
 
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st) {
@@ -697,14 +658,12 @@ hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a,
     return hipErrorInvalidValue;
 }
 
-int mlp_lds_bytes(int bias_floats) { return RING_BYTES + bias_floats * 4 + kVoteBytes; }
 int mlp_tile_points() { return TILE_PTS; }
 const char* mlp_kernel_name() { return "mlp_kernel"; }
 
 // chunks consumed per tile by a variant of the field program (the DMA stream is cyclic over exactly these)
 int field_variant_chunks(int W, int C, int variant) {
-    const int last = variant == 0 ? (int)F_NUM : variant == 1 ? (int)F_A1 : (int)F_S1;      // variant 3 = the layers of variant 2
-    return prog_chunk_start(PROG_FIELD, W, C, last);
+    return prog_chunk_start(PROG_FIELD, W, C, field_variant_layers(variant));
 }
 
 hipError_t launch_composite(const CompArgs& a, hipStream_t st) {

@@ -222,6 +222,7 @@ constexpr int ring_depth8(int W) { return W > 256 ? 5 : RING_D; }    // W = 512:
 
 template <int PROG, int W, int VARIANT>
 __global__ __launch_bounds__(256, 1) void mlp_i8_kernel(const MlpArgs A) {
+    static_assert(PROG == PROG_FIELD, "the per-ray networks have no int8 instance");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
@@ -236,25 +237,11 @@ __global__ __launch_bounds__(256, 1) void mlp_i8_kernel(const MlpArgs A) {
 
     for (int i = threadIdx.x; i < A.bias_floats; i += 256) tab_lds[i] = A.bias[i];
 
-    Ring rg;
-    rg.rd = 0;
-    rg.cur = 0;
-    rg.goff = 0;
-    {
-        uint32_t wr = 0;
-#pragma unroll
-        for (int c = 0; c < D - 2; ++c) {
-            dma_chunk(A.stream, rg.goff, lds, wr, wave, lane);
-            rg.goff += kChunkBytes;
-            if (rg.goff >= A.stream_bytes) rg.goff = 0;
-            wr += kChunkBytes;
-        }
-        rg.wr = wr;
-    }
+    RING_PROLOGUE(rg, D, A, lds, wave, lane)
     __syncthreads();
 
-    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 4 rays (one per wave), walked in `passes` steps of 32 samples
-    const int64_t n_tiles = VARIANT == 3 ? (A.n + 3) / 4 : (A.n + TILE_PTS - 1) / TILE_PTS;
+    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 4 rays (one per wave), walked in passes of 32 samples
+    const int64_t n_tiles = field_tiles(A.n, VARIANT, TILE_PTS, 4);
     const int passes = VARIANT == 3 ? (A.n_samples + 31) / 32 : 1;
     int pass = 0;
     RaySum rs;
@@ -264,80 +251,11 @@ __global__ __launch_bounds__(256, 1) void mlp_i8_kernel(const MlpArgs A) {
         const int64_t nc = valid ? n : A.n - 1;
         const int64_t g = VARIANT == 3 ? 0 : nc / A.group_size;
 
-        if constexpr (PROG == PROG_GROUP) {
-            // ---- group program: class softmax (T_NeRF_net_v2.py:77-78) and sky colour (G_NeRF.py:110-111); used where the
-            // bf16 group kernel has no instance (W = 512: its activations do not fit the register file)
-            constexpr int KW = W / 32, W4P = pad32(W / 4), KW4 = W4P / 32;
-            f32x16 raw;
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                                 \
-    run_layer8<NBv, K0, K1, SINv, D>(rg, A.stream, A.stream_bytes, lds, tab_lds + prog_table_start(PROG_GROUP, W, C_MAX, L), \
-                                     IN0, IN1, OUT, RAW, wave, lane)
-#define LAYER_RAW(L, NBv, K0, K1, IN0, IN1, OUT, RX)                                                                    \
-    run_layer8<NBv, K0, K1, true, D, -1, -1, false, true>(rg, A.stream, A.stream_bytes, lds,                             \
-        tab_lds + prog_table_start(PROG_GROUP, W, C_MAX, L), IN0, IN1, OUT, nullptr, wave, lane, RX)
-            const float t0 = A.time[nc * 4], t1 = A.time[nc * 4 + 1];
-            const float s0 = A.sun[nc * 3], s1 = A.sun[nc * 3 + 1], s2 = A.sun[nc * 3 + 2];
-            Frag8 pt[PETIME_KS8];
-            make_pe_time8(t0, t1, h, pt);
-            Frag8 hA[KW], hB[KW];
-            const float rx_t[3] = {t0, t1, 0.f}, rx_s[3] = {s0, s1, s2};
-            LAYER_RAW(G_T1, W / 32, PETIME_KS8, 0, pt, nullptr, hA, rx_t);
-            LAYER(G_T2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-            LAYER(G_CL, 1, KW, 0, false, hB, nullptr, nullptr, &raw);
-            float logit[C_MAX];
-#pragma unroll
-            for (int c = 0; c < C_MAX; ++c) logit[c] = raw[c];
-            Frag8 ps[PESUN_KS8];
-            make_pe_sun8(s0, s1, s2, h, ps);
-            Frag8 kA[KW4];
-            LAYER_RAW(G_K1, W4P / 32, PESUN_KS8, 0, ps, nullptr, kA, rx_s);
-            LAYER(G_K2, 1, KW4, 0, false, kA, nullptr, nullptr, &raw);
-#undef LAYER
-#undef LAYER_RAW
-            if (h == 0 && valid) {
-                float m = -3.0e38f;
-#pragma unroll
-                for (int c = 0; c < C_MAX; ++c) if (c < C) m = fmaxf(m, logit[c]);
-                float e[C_MAX], sum = 0.f;
-#pragma unroll
-                for (int c = 0; c < C_MAX; ++c) { e[c] = c < C ? expf(logit[c] - m) : 0.f; sum += e[c]; }
-#pragma unroll
-                for (int c = 0; c < C_MAX; ++c) if (c < C && A.g_classes) A.g_classes[n * C + c] = e[c] / sum;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (A.g_sky_raw) A.g_sky_raw[n * 3 + k] = raw[k];
-                    if (A.g_sky) A.g_sky[n * 3 + k] = sigmoid_f(raw[k]);
-                }
-            }
-            tile += gridDim.x;
-            continue;
-        }
-        // ---- sample position (misc.py:234-247 fused): top*(1-t) + bot*t, two roundings + one add, no fma
         float x0, x1, x2;
-        if constexpr (VARIANT == 3) {
-            raysum_point(rs, A, tile, 4, wave, pass, lane, x0, x1, x2);
-        } else if (A.points) {
-            x0 = A.points[nc * 3]; x1 = A.points[nc * 3 + 1]; x2 = A.points[nc * 3 + 2];
-        } else {
-            const int64_t r = nc / A.n_samples;
-            const int s = (int)(nc - r * A.n_samples);
-            const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-            x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-            x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-            x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
-        }
-        // every per-tile input is loaded before the MFMA chain (a plain load inside it drains the LDS-DMA pipeline)
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        float pcls[C_MAX];
-#pragma unroll
-        for (int c = 0; c < C_MAX; ++c) pcls[c] = 0.f;
-        if constexpr (VARIANT <= 1) { s0 = A.sun[g * 3]; s1 = A.sun[g * 3 + 1]; s2 = A.sun[g * 3 + 2]; }
-        if constexpr (VARIANT == 0) {
-            if (A.classes) {
-#pragma unroll
-                for (int c = 0; c < C_MAX; ++c) if (c < C) pcls[c] = A.classes[g * C + c];
-            }
-        }
+        if constexpr (VARIANT == 3) raysum_point(rs, A, tile, 4, wave, pass, lane, x0, x1, x2);
+        else field_point(A, nc, x0, x1, x2);
+        float s0, s1, s2, pcls[C_MAX];
+        field_tile_inputs<VARIANT>(A, g, s0, s1, s2, pcls);
         Frag8 pe[PEPOS_KS8];
         make_pe_pos8<VARIANT == 3>(x0, x1, x2, h, pe);
 
@@ -399,12 +317,7 @@ __global__ __launch_bounds__(256, 1) void mlp_i8_kernel(const MlpArgs A) {
 #undef LAYER
 #undef LAYER_RAW
         if constexpr (VARIANT == 3) {
-            raysum_add(rs, A, tile, 4, wave, pass, lane, rho_raw, x0, x1, x2);
-            if (++pass == passes || raysum_saturated(rs, A, tile * 4 + wave, wave, 4, lane, (__attribute__((address_space(3))) float*)(tab_lds + A.bias_floats))) {
-                raysum_end(rs, A, tile, 4, wave, lane);
-                pass = 0;
-                tile += gridDim.x;
-            }
+            RAYSUM_PASS_END(rs, A, tile, pass, passes, 4, wave, wave, 4, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
         } else {
             if (h == 0 && valid) store_field_outputs<VARIANT>(A.out, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, sv_raw, adj, pcls);
             tile += gridDim.x;
@@ -413,17 +326,10 @@ __global__ __launch_bounds__(256, 1) void mlp_i8_kernel(const MlpArgs A) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
 }
 
-template <int PROG, int W, int VARIANT>
+template <int W, int VARIANT>
 static hipError_t launch_mlp_i8_t(const MlpArgs& a, int n_cu, hipStream_t st) {
-    const int lds_bytes = ring_depth8(W) * kChunkBytes + a.bias_floats * 4 + kVoteBytes;
-    const int64_t n_tiles = VARIANT == 3 ? (a.n + 3) / 4 : (a.n + TILE_PTS - 1) / TILE_PTS;
-    int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
-    if (grid < 1) grid = 1;
-    auto k = mlp_i8_kernel<PROG, W, VARIANT>;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_fused(mlp_i8_kernel<PROG_FIELD, W, VARIANT>, field_tiles(a.n, VARIANT, TILE_PTS, 4), 256,
+                        ring_depth8(W) * kChunkBytes + a.bias_floats * 4 + kVoteBytes, a, n_cu, st);
 }
 
 // The W = 512 field instances are compiled in their own translation unit (kernels_i8_w512.hip: this file again, with
@@ -432,37 +338,32 @@ static hipError_t launch_mlp_i8_t(const MlpArgs& a, int n_cu, hipStream_t st) {
 hipError_t launch_mlp_i8_w512(int variant, const MlpArgs& a, int n_cu, hipStream_t st);
 #ifdef SNERF_I8_W512_TU
 hipError_t launch_mlp_i8_w512(int variant, const MlpArgs& a, int n_cu, hipStream_t st) {
-    if (variant == 0) return launch_mlp_i8_t<PROG_FIELD, 512, 0>(a, n_cu, st);
-    if (variant == 1) return launch_mlp_i8_t<PROG_FIELD, 512, 1>(a, n_cu, st);
-    if (variant == 3) return launch_mlp_i8_t<PROG_FIELD, 512, 3>(a, n_cu, st);
-    return launch_mlp_i8_t<PROG_FIELD, 512, 2>(a, n_cu, st);
+    if (variant == 0) return launch_mlp_i8_t<512, 0>(a, n_cu, st);
+    if (variant == 1) return launch_mlp_i8_t<512, 1>(a, n_cu, st);
+    if (variant == 3) return launch_mlp_i8_t<512, 3>(a, n_cu, st);
+    return launch_mlp_i8_t<512, 2>(a, n_cu, st);
 }
 #else
-hipError_t launch_mlp_i8(int prog, int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st) {
+// the per-ray networks have no int8 instance: one row per ray, their error is not averaged over a ray's samples
+// (kernels_ks.hip mlp_ks_group_kernel and api.cpp group_forward_f32 run them at W = 512)
+hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st) {
 #define CASE(Wv)                                                                          \
     if (W == Wv) {                                                                        \
-        if (prog != PROG_FIELD) return hipErrorInvalidValue;                              \
-        if (variant == 0) return launch_mlp_i8_t<PROG_FIELD, Wv, 0>(a, n_cu, st);         \
-        if (variant == 1) return launch_mlp_i8_t<PROG_FIELD, Wv, 1>(a, n_cu, st);         \
-        if (variant == 3) return launch_mlp_i8_t<PROG_FIELD, Wv, 3>(a, n_cu, st);         \
-        return launch_mlp_i8_t<PROG_FIELD, Wv, 2>(a, n_cu, st);                           \
+        if (variant == 0) return launch_mlp_i8_t<Wv, 0>(a, n_cu, st);                     \
+        if (variant == 1) return launch_mlp_i8_t<Wv, 1>(a, n_cu, st);                     \
+        if (variant == 3) return launch_mlp_i8_t<Wv, 3>(a, n_cu, st);                     \
+        return launch_mlp_i8_t<Wv, 2>(a, n_cu, st);                                       \
     }
     CASE(64)
     CASE(256)
 #undef CASE
-    if (W == 512) {
-        // the per-ray networks have no int8 instance: one row per ray, their error is not averaged over a ray's samples
-        // (api.cpp group_forward_f32 runs them in exact fp32 at this width)
-        if (prog != PROG_FIELD) return hipErrorInvalidValue;
-        return launch_mlp_i8_w512(variant, a, n_cu, st);
-    }
+    if (W == 512) return launch_mlp_i8_w512(variant, a, n_cu, st);
     return hipErrorInvalidValue;
 }
 
 // chunks consumed per tile by a variant of the int8 field program (the DMA stream is cyclic over exactly these)
 int field_variant_chunks_i8(int W, int C, int variant) {
-    const int last = variant == 0 ? (int)F_NUM : variant == 1 ? (int)F_A1 : (int)F_S1;      // variant 3 = the layers of variant 2
-    return prog_chunk_start(PROG_FIELD, W, C, last, FMT_I8);
+    return prog_chunk_start(PROG_FIELD, W, C, field_variant_layers(variant), FMT_I8);
 }
 #endif
 

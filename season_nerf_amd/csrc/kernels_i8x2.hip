@@ -368,8 +368,8 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
     constexpr int W2 = W / 2;
     const int h = lane >> 5;
     const int C = A.n_classes;
-    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of NW2 rays, walked in `passes` steps of 32 samples
-    const int64_t n_tiles = VARIANT == 3 ? (A.n + NW2 - 1) / NW2 : (A.n + TILE2 - 1) / TILE2;
+    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of NW2 rays, walked in passes of 32 samples
+    const int64_t n_tiles = field_tiles(A.n, VARIANT, TILE2, NW2);
     const int passes = VARIANT == 3 ? (A.n_samples + 31) / 32 : 1;
     int pass = 0;
     RaySum rs;
@@ -379,32 +379,11 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
         const int64_t nc = valid ? n : A.n - 1;
         const int64_t g = VARIANT == 3 ? 0 : nc / A.group_size;
 
-        // ---- sample position (misc.py:234-247 fused): top*(1-t) + bot*t, two roundings + one add, no fma
         float x0, x1, x2;
-        if constexpr (VARIANT == 3) {
-            raysum_point(rs, A, tile, NW2, wave, pass, lane, x0, x1, x2);
-        } else if (A.points) {
-            x0 = A.points[nc * 3]; x1 = A.points[nc * 3 + 1]; x2 = A.points[nc * 3 + 2];
-        } else {
-            const int64_t r = nc / A.n_samples;
-            const int s = (int)(nc - r * A.n_samples);
-            const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-            x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-            x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-            x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
-        }
-        // every per-tile input is loaded before the MFMA chain (a plain load inside it drains the LDS-DMA pipeline)
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        float pcls[C_MAX];
-#pragma unroll
-        for (int c = 0; c < C_MAX; ++c) pcls[c] = 0.f;
-        if constexpr (VARIANT <= 1) { s0 = A.sun[g * 3]; s1 = A.sun[g * 3 + 1]; s2 = A.sun[g * 3 + 2]; }
-        if constexpr (VARIANT == 0) {
-            if (A.classes) {
-#pragma unroll
-                for (int c = 0; c < C_MAX; ++c) if (c < C) pcls[c] = A.classes[g * C + c];
-            }
-        }
+        if constexpr (VARIANT == 3) raysum_point(rs, A, tile, NW2, wave, pass, lane, x0, x1, x2);
+        else field_point(A, nc, x0, x1, x2);
+        float s0, s1, s2, pcls[C_MAX];
+        field_tile_inputs<VARIANT>(A, g, s0, s1, s2, pcls);
 #ifdef SNERF_STAMP
         const bool stamp_on = blockIdx.x == 0 && tile == (int64_t)blockIdx.x + gridDim.x;      // the workgroup's second tile
 #endif
@@ -464,12 +443,7 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
 #undef LAYER
 #undef LAYER_RAW
         if constexpr (VARIANT == 3) {
-            raysum_add(rs, A, tile, NW2, wave, pass, lane, rho_raw, x0, x1, x2);
-            if (++pass == passes || raysum_saturated(rs, A, tile * NW2 + wave, wave, NW2, lane, (__attribute__((address_space(3))) float*)(tab_lds + A.bias_floats))) {
-                raysum_end(rs, A, tile, NW2, wave, lane);
-                pass = 0;
-                tile += gridDim.x;
-            }
+            RAYSUM_PASS_END(rs, A, tile, pass, passes, NW2, wave, wave, NW2, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
         } else {
             if (h == 0 && valid) store_field_outputs<VARIANT>(A.out, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, sv_raw, adj, pcls);
             tile += gridDim.x;
@@ -481,15 +455,8 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
 
 template <int W, int VARIANT>
 static hipError_t launch_mlp_i8x2_t(const MlpArgs& a, int n_cu, hipStream_t st) {
-    const int lds_bytes = RING2_D * kChunkBytes + a.bias_floats * 4 + kVoteBytes;
-    const int64_t n_tiles = VARIANT == 3 ? (a.n + NW2 - 1) / NW2 : (a.n + TILE2 - 1) / TILE2;
-    int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
-    if (grid < 1) grid = 1;
-    auto k = mlp_i8x2_kernel<W, VARIANT>;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NW2), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_fused(mlp_i8x2_kernel<W, VARIANT>, field_tiles(a.n, VARIANT, TILE2, NW2), 64 * NW2,
+                        RING2_D * kChunkBytes + a.bias_floats * 4 + kVoteBytes, a, n_cu, st);
 }
 
 hipError_t launch_mlp_i8x2(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st) {

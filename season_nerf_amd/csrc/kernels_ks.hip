@@ -315,28 +315,14 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
     }
     __attribute__((address_space(3))) float* vote_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + (A.bias_floats + 32) * 4 + 4 * KS_XBUF_BYTES);
 
-    Ring rg;
     Pend pd;
     pd.goff = 0;
     pd.wr = 0;
-    rg.rd = 0;
-    rg.cur = 0;
-    rg.goff = 0;
-    {
-        uint32_t wr = 0;
-#pragma unroll
-        for (int c = 0; c < RING_D - 2; ++c) {
-            dma_chunk(A.stream, rg.goff, lds, wr, wave, lane);
-            rg.goff += kChunkBytes;
-            if (rg.goff >= A.stream_bytes) rg.goff = 0;
-            wr += kChunkBytes;
-        }
-        rg.wr = wr;
-    }
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
     __syncthreads();
 
-    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 2 rays (one per wave pair), walked in `passes` steps of 32 samples
-    const int64_t n_tiles = VARIANT == 3 ? (A.n + 1) / 2 : (A.n + KS_TILE_PTS - 1) / KS_TILE_PTS;
+    // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 2 rays (one per wave pair), walked in passes of 32 samples
+    const int64_t n_tiles = field_tiles(A.n, VARIANT, KS_TILE_PTS, 2);
     const int passes = VARIANT == 3 ? (A.n_samples + 31) / 32 : 1;
     int pass = 0;
     RaySum rs;
@@ -347,29 +333,10 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
         const int64_t g = VARIANT == 3 ? 0 : nc / A.group_size;
 
         float x0, x1, x2;
-        if constexpr (VARIANT == 3) {
-            raysum_point(rs, A, tile, 2, pair, pass, lane, x0, x1, x2);
-        } else if (A.points) {
-            x0 = A.points[nc * 3]; x1 = A.points[nc * 3 + 1]; x2 = A.points[nc * 3 + 2];
-        } else {
-            const int64_t r = nc / A.n_samples;
-            const int s = (int)(nc - r * A.n_samples);
-            const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-            x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-            x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-            x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
-        }
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        float pcls[C_MAX];
-#pragma unroll
-        for (int c = 0; c < C_MAX; ++c) pcls[c] = 0.f;
-        if constexpr (VARIANT <= 1) { s0 = A.sun[g * 3]; s1 = A.sun[g * 3 + 1]; s2 = A.sun[g * 3 + 2]; }
-        if constexpr (VARIANT == 0) {
-            if (A.classes) {
-#pragma unroll
-                for (int c = 0; c < C_MAX; ++c) if (c < C) pcls[c] = A.classes[g * C + c];
-            }
-        }
+        if constexpr (VARIANT == 3) raysum_point(rs, A, tile, 2, pair, pass, lane, x0, x1, x2);
+        else field_point(A, nc, x0, x1, x2);
+        float s0, s1, s2, pcls[C_MAX];
+        field_tile_inputs<VARIANT>(A, g, s0, s1, s2, pcls);
         Frag pe[PEPOS_KS];
         make_pe_pos(x0, x1, x2, h, pe);
 
@@ -422,13 +389,8 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
 #undef LAYER
 #undef HEADL
 #undef OWNB
-        if constexpr (VARIANT == 3) {
-            raysum_add(rs, A, tile, 2, pair, pass, lane, rho_raw, x0, x1, x2);
-            if (++pass == passes || raysum_saturated(rs, A, tile * 2 + pair, wave, 4, lane, vote_lds)) {      // both waves of a pair hold the same sum and vote alike
-                if (par == 0) raysum_end(rs, A, tile, 2, pair, lane);
-                pass = 0;
-                tile += gridDim.x;
-            }
+        if constexpr (VARIANT == 3) {      // both waves of a pair hold the same sum and vote alike; wave 0 of the pair stores
+            RAYSUM_PASS_END(rs, A, tile, pass, passes, 2, pair, wave, 4, par == 0, lane, rho_raw, x0, x1, x2, vote_lds);
         } else {
             if (par == 0 && h == 0 && valid) store_field_outputs<VARIANT>(A.out, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, sv_raw, adj, pcls);
             tile += gridDim.x;
@@ -462,24 +424,10 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_group_kernel(const MlpArgs A) {
         cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
         cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
     }
-    Ring rg;
     Pend pd;
     pd.goff = 0;
     pd.wr = 0;
-    rg.rd = 0;
-    rg.cur = 0;
-    rg.goff = 0;
-    {
-        uint32_t wr = 0;
-#pragma unroll
-        for (int c = 0; c < RING_D - 2; ++c) {
-            dma_chunk(A.stream, rg.goff, lds, wr, wave, lane);
-            rg.goff += kChunkBytes;
-            if (rg.goff >= A.stream_bytes) rg.goff = 0;
-            wr += kChunkBytes;
-        }
-        rg.wr = wr;
-    }
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
     __syncthreads();
     const int64_t n_tiles = (A.n + KS_TILE_PTS - 1) / KS_TILE_PTS;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -533,15 +481,7 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_group_kernel(const MlpArgs A) {
 
 hipError_t launch_mlp_ks_group(int W, const MlpArgs& a, int n_cu, hipStream_t st) {
     if (W != 512) return hipErrorInvalidValue;
-    const int lds_bytes = ks_lds_bytes(a.bias_floats);
-    const int64_t n_tiles = (a.n + KS_TILE_PTS - 1) / KS_TILE_PTS;
-    int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
-    if (grid < 1) grid = 1;
-    auto k = mlp_ks_group_kernel<512>;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_fused(mlp_ks_group_kernel<512>, (a.n + KS_TILE_PTS - 1) / KS_TILE_PTS, 256, ks_lds_bytes(a.bias_floats), a, n_cu, st);
 }
 int group_chunks_ks(int W, int C) { return ks_chunk_start_g(W, C, G_NUM); }
 
@@ -549,14 +489,7 @@ template <int W, int VARIANT>
 static hipError_t launch_ks_t(const MlpArgs& a, int n_cu, hipStream_t st) {
     const int lds_bytes = ks_lds_bytes(a.bias_floats);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    const int64_t n_tiles = VARIANT == 3 ? (a.n + 1) / 2 : (a.n + KS_TILE_PTS - 1) / KS_TILE_PTS;
-    int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
-    if (grid < 1) grid = 1;
-    auto k = mlp_ks_kernel<W, VARIANT>;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_fused(mlp_ks_kernel<W, VARIANT>, field_tiles(a.n, VARIANT, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
 }
 
 hipError_t launch_mlp_ks(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st) {
@@ -572,8 +505,7 @@ hipError_t launch_mlp_ks(int W, int variant, const MlpArgs& a, int n_cu, hipStre
 
 // chunks consumed per tile by a variant (the DMA stream is cyclic over exactly these); variant 3 = the layers of variant 2
 int field_variant_chunks_ks(int W, int C, int variant) {
-    const int last = variant == 0 ? (int)F_NUM : variant == 1 ? (int)F_A1 : (int)F_S1;
-    return ks_chunk_start(W, C, last);
+    return ks_chunk_start(W, C, field_variant_layers(variant));
 }
 int mlp_ks_lds_bytes(int bias_floats) { return ks_lds_bytes(bias_floats); }
 int mlp_ks_tile_points() { return KS_TILE_PTS; }

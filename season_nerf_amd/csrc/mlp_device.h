@@ -1,5 +1,6 @@
-// Device helpers shared by the fused-MLP kernels (kernels.hip: bf16 split products; kernels_i8.hip: int8 digits):
-// vector types, the LDS-DMA weight ring, the exact positional-encoding argument reduction, output non-linearities.
+// Device helpers shared by the fused field kernels of all four families (kernels.hip, kernels_ks.hip: bf16 split products; kernels_i8.hip,
+// kernels_i8x2.hip: int8 digits): vector types, the LDS-DMA weight ring and its prologue, the exact positional-encoding argument reduction,
+// the work of a tile around each family's layer walk (sample position, per-tile inputs, the ray-visibility pass end), output non-linearities.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,6 +82,25 @@ __device__ __forceinline__ void dma_chunk(const uint8_t* stream, uint32_t goff, 
     }
 }
 
+// Ring `rg` with its prologue issued: D-2 chunks in flight (the refill target trails the consumer by two slots; rg.wr = (D-2)*chunk is,
+// at the step that publishes chunk k, the slot of chunk k-2).  A macro, not a function: hipcc simplifies an inlined function's body before
+// the kernel's, and a function here (Ring by reference or by value) changed the address arithmetic of the prologue's DMAs.
+#define RING_PROLOGUE(rg, D, A, lds, wave, lane)                                                          \
+    Ring rg;                                                                                             \
+    rg.rd = 0;                                                                                           \
+    rg.cur = 0;                                                                                          \
+    rg.goff = 0;                                                                                         \
+    {                                                                                                    \
+        uint32_t wr = 0;                                                                                 \
+        _Pragma("unroll") for (int c = 0; c < (D) - 2; ++c) {                                            \
+            dma_chunk((A).stream, rg.goff, lds, wr, wave, lane);                                         \
+            rg.goff += kChunkBytes;                                                                      \
+            if (rg.goff >= (A).stream_bytes) rg.goff = 0;                                                \
+            wr += kChunkBytes;                                                                           \
+        }                                                                                                \
+        rg.wr = wr;                                                                                      \
+    }
+
 template <int D = RING_D>
 __device__ __forceinline__ uint32_t ring_next(uint32_t off) {
     off += kChunkBytes;
@@ -140,6 +160,37 @@ __device__ __forceinline__ void pe_sincos(const PeArg& a, double scale, float& c
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // torch Softplus(beta 1, thr 20)
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ---- the field program's per-tile work around the layer walk (the same in every fused field kernel)
+// sample position of field point nc (VARIANTs 0-2): given, or sample nc % S of ray nc / S (misc.py:234-247 fused: top*(1-t) + bot*t,
+// two roundings + one add, no fma)
+__device__ __forceinline__ void field_point(const MlpArgs& A, int64_t nc, float& x0, float& x1, float& x2) {
+    if (A.points) {
+        x0 = A.points[nc * 3]; x1 = A.points[nc * 3 + 1]; x2 = A.points[nc * 3 + 2];
+    } else {
+        const int64_t r = nc / A.n_samples;
+        const int s = (int)(nc - r * A.n_samples);
+        const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
+        x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
+        x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
+        x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
+    }
+}
+// the per-tile inputs of group g: sun direction (VARIANT <= 1), class probabilities (VARIANT 0), zero where the variant has none.
+// Every per-tile input is loaded before the MFMA chain: a plain load in the middle of the chain makes hipcc drain the LDS-DMA pipeline with vmcnt(0).
+template <int VARIANT>
+__device__ __forceinline__ void field_tile_inputs(const MlpArgs& A, int64_t g, float& s0, float& s1, float& s2, float* pcls) {
+    s0 = 0.f; s1 = 0.f; s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) pcls[c] = 0.f;
+    if constexpr (VARIANT <= 1) { s0 = A.sun[g * 3]; s1 = A.sun[g * 3 + 1]; s2 = A.sun[g * 3 + 2]; }
+    if constexpr (VARIANT == 0) {
+        if (A.classes) {
+#pragma unroll
+            for (int c = 0; c < kMaxClasses; ++c) if (c < A.n_classes) pcls[c] = A.classes[g * A.n_classes + c];
+        }
+    }
+}
 
 // VARIANT 3 ("ray visibility", Eval_Tools_2.py:255-271 / mg_Img_Eval.py:57-70): the density-only program over the samples of a ray, the
 // optical depth sum_{j < S-1} rho_j delta_j kept in a register across the ray's ceil(S / 32) passes, one float out per ray:
@@ -212,6 +263,19 @@ __device__ __forceinline__ void raysum_end(RaySum& q, const MlpArgs& A, int64_t 
     const int64_t ray = group * waves + wave;
     if (lane == 0 && ray < A.n) A.out.vis[ray] = expf(-v);
 }
+// The end of a pass: add its samples; once the ray is done (its last of `passes`, or a workgroup that voted itself saturated) store its
+// visibility (`writer`: this wave stores for its ray), then set `pass` back to 0 and advance the persistent loop's `tile`.  `rays`: rays per
+// tile; `ray_wave`: the ray of the tile this wave walks; `slot` / `n_slots`: as raysum_saturated.  A macro for the reason RING_PROLOGUE is
+// one: as a function (tile and pass by reference) it changed the code around the vote.
+#define RAYSUM_PASS_END(q, A, tile, pass, passes, rays, ray_wave, slot, n_slots, writer, lane, rho_raw, x0, x1, x2, vote)           \
+    {                                                                                                                           \
+        raysum_add(q, A, tile, rays, ray_wave, pass, lane, rho_raw, x0, x1, x2);                                                \
+        if (++pass == (passes) || raysum_saturated(q, A, tile * (rays) + (ray_wave), slot, n_slots, lane, vote)) {              \
+            if (writer) raysum_end(q, A, tile, rays, ray_wave, lane);                                                           \
+            pass = 0;                                                                                                           \
+            tile += gridDim.x;                                                                                                  \
+        }                                                                                                                       \
+    }
 
 // output non-linearities of the field program (T_NeRF_net_v2.py:91-98) for one point; called by the lanes that hold the head rows
 template <int VARIANT>

@@ -142,17 +142,4 @@ __device__ __forceinline__ void make_pe_sun8(float x0, float x1, float x2, int h
     pack16(v, pe[0]);
 }
 
-// PE(time[:,0:2]): lane-half h owns coordinate h (petime_feature), one k-step
-__device__ __forceinline__ void make_pe_time8(float t0, float t1, int h, Frag8* pe) {
-    float v[16];
-    const float x = h ? t1 : t0;
-    const PeArg a = pe_arg(x);
-    v[0] = x;
-    pe_sincos(a, 1.0, v[1], v[2]);
-    pe_sincos(a, 2.0, v[3], v[4]);
-#pragma unroll
-    for (int i = 5; i < 16; ++i) v[i] = 0.f;
-    pack16(v, pe[0]);
-}
-
 }  // namespace snerf

@@ -115,6 +115,9 @@ __host__ __device__ constexpr int prog_chunk_start(int prog, int W, int C, int l
     for (int i = 0; i < l; ++i) c += prog_layer(prog, W, C, i, fmt).chunks();
     return c;
 }
+// the layers a variant of the field program runs are the first field_variant_layers(variant) of the list: all (0), no adjust branch (1),
+// trunk + head (2, and 3 = the density of 2 summed along a ray)
+__host__ __device__ constexpr int field_variant_layers(int variant) { return variant == 0 ? (int)F_NUM : variant == 1 ? (int)F_A1 : (int)F_S1; }
 __host__ __device__ constexpr int prog_bias_start(int prog, int W, int C, int l) {
     int c = 0;
     for (int i = 0; i < l; ++i) c += prog_layer(prog, W, C, i).n_out;
