@@ -276,7 +276,12 @@ int snerf_trainer_set_allreduce(snerf_trainer* t, snerf_allreduce_fn fn, void* u
  * stand-alone calls - the building blocks of the training engine, exposed for tests and for callers that schedule layers
  * themselves.  Row-major fp32, leading dimensions in floats; weight is the [n_out, n_in] nn.Linear matrix.
  * precision: 1 = error-compensated bf16x3 MFMA (~1e-5 relative, needs d_scratch of snerf_linear_scratch_bytes), 0 = exact
- * fp32 MFMA.
+ * fp32 MFMA.  Thin heads: with precision == 1, n_out <= 4 and n_points >= 1024, forward and wgrad do not use the MFMA kernels but
+ * stream over `in` in EXACT fp32, as the training engine does for its colour / density / visibility heads.  The forward does
+ * so only when a bias is given and d_stats is NULL (the stream always adds the bias and has no statistics epilogue).  Both do
+ * so only where the stream takes the layout (n_in a multiple of 4, at most 256 for the forward and 1024 for wgrad; `in` 16-byte
+ * aligned; ld_in a multiple of 4) and while SNERF_FUSED_HEADS (forward) / SNERF_THIN_WGRAD (wgrad) is not 0; otherwise bf16x3 as
+ * above.  dgrad never streams.  Arguments are checked the same way on every route, before one is chosen.
  *   forward: out[m, o] = alpha * (sum_i in[m, i] * weight[o, i] + bias[o]);  d_stats (optional, bf16x3 only, caller-zeroed
  *            double[2][n_out]) += sum_m (out - alpha*bias), sum_m (out - alpha*bias)^2   (train-mode BatchNorm statistics)
  *   dgrad:   grad_in[m, i] (+)= alpha * sum_o grad_out[m, o] * weight[o, i]   for i < n_cols

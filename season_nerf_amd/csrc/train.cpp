@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "linear_product.h"
 #include "train.h"
 
 // Every device-to-device copy and zero-fill of the engine is a KERNEL of ours, never hipMemcpyAsync / hipMemsetAsync.  Inside a captured training step a
@@ -24,10 +25,7 @@
 // nodes only, 0 of 68 driver runs differ from the eager run; with the memory operations back (SNERF_TRAIN_MEMOPS=1, kept for the reproduction:
 // tools/graph_wait_probe4.py) 29 of 29 do; with the memory operations AND packet capture off, 0 of 6.  The defect is the runtime's and reproduces without any
 // code of this repository: tools/graph_memset_min.py (25 lines), profiles/r6/graph_memop_repro.txt.
-static bool train_memops() {
-    static const bool on = [] { const char* e = getenv("SNERF_TRAIN_MEMOPS"); return e && e[0] == '1'; }();
-    return on;
-}
+static bool train_memops() { return snerf::switches().memops; }
 static hipError_t snerf_zero_async(void* p, int value, size_t bytes, hipStream_t st) {
     if (train_memops()) return hipMemsetAsync(p, value, bytes, st);
     if (value != 0) return hipErrorInvalidValue;                     // (the engine only ever zeroes)
@@ -94,6 +92,7 @@ struct snerf_trainer {
         Act Hc[9], Hac[3], Hsc[3], In5c, In_s1c, Zc3, Zc8;
         float* tabs = nullptr;      // [15 layers][2][W] activation-on-load tables of this pass
         bool aol = false;
+        float* tab(int slot, int W) const { return aol ? tabs + (int64_t)slot * 2 * W : nullptr; }      // slots: 0-8 trunk, 9-11 adjust, 12-14 solar
     } img, sol;
     Act dA, dB, dX1;
     float *d_head, *d_adj, *d_rho, *d_col, *d_sky, *d_cls, *d_sv_raw, *rayA, *rayB, *bn_bwd;   // bn_bwd: [2][W]
@@ -236,135 +235,49 @@ static size_t carve(snerf_trainer* t, char* base, int64_t R, int64_t Rs, int S) 
         hipError_t _e = (x);                                                                       \
         if (_e != hipSuccess) return snerf_set_error(SNERF_E_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); \
     } while (0)
+#define RC(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
-// bf16x3 row-owner kernel usable for an [M x K] x [K x N] product?
-static bool rows_ok(const snerf_trainer* t, int64_t M, int K, int N) {
-    // thin layers included (heads with 1..12 outputs): the kernels mask partial tiles, and every such GEMM is a single pass
-    // over a [points x W] activation - HBM-bound either way
-    return t->gemm_mode == 1 && M >= 1024 && K >= 1 && N >= 1 && gemm_rows_group_tiles((K + 15) / 16) > 0;
+// ---- the engine's side of linear_product.h.  The engine as a caller: small (per-ray) batches go to exact fp32; `head`: a plain Linear (its forward may stream)
+static Policy engine_policy(const snerf_trainer* t, bool head = false) { return Policy{t->gemm_mode == 1, 1024, head, true}; }
+// layer L on input In; Y is its output (forward) or the gradient with respect to it (backward)
+static Product product_of(const snerf_trainer* t, const LayerP& L, const Act& In, int64_t M, float* Y, int64_t ldy, float alpha) {
+    Product p;
+    p.M = M; p.n_in = L.n_in; p.n_out = L.n_out; p.alpha = alpha; p.W = t->params + L.w; p.bias = t->params + L.b; p.dW = t->grads + L.w;
+    p.X = In.p; p.ldx = In.ld; p.tab = In.tab; p.tab_cols = In.tab ? In.cols : 0; p.x_padded = In.padded; p.Y = Y; p.ldy = ldy; p.frag = t->w_frag;
+    return p;
 }
-#define RCI(x)                 \
-    do {                      \
-        int _rci = (x);       \
-        if (_rci) return _rci; \
-    } while (0)
+// `below` (optional): the SineLayer whose output gradient a dgrad produces.  When that layer's [a | b] table exists (activation on load) and the dgrad covers
+// all of its columns, its activation backward (x cos, column sums into t->bn_stats) happens in the dgrad's epilogue on the thin and row routes; the
+// consumer then skips its own reduction sweep.
+struct ActBelow { const LayerP* L; Act Z; const float* tab; float* bnslot; };
+static Epilogue epilogue_of(const snerf_trainer* t, const ActBelow* below, int n_cols) {
+    Epilogue e;
+    if (!below || !below->tab || below->L->n_out != n_cols) return e;
+    e.z = below->Z.p; e.ld = below->Z.ld; e.tab = below->tab; e.sums = t->bn_stats;
+    if (below->L->bn) { e.mu = below->bnslot + 2 * t->W; e.istd = below->bnslot + 3 * t->W; }
+    return e;
+}
 
-// Z[M, n_out] = alpha * (In[M, K] W^T + b);  colsum (fp32 path) / stats (bf16x3 path) optional
-static hipError_t linear_fwd(snerf_trainer* t, const LayerP& L, Act InA, int64_t M, float* Z, int64_t ldz,
-                             float alpha, float* colsum, hipStream_t st, double* stats = nullptr) {
-    const float* In = InA.p;
-    const int64_t ld_in = InA.ld;
-    if (InA.tab && !rows_ok(t, M, L.n_in, L.n_out)) return hipErrorInvalidValue;        // activation on load needs the row kernel
-    if (rows_ok(t, M, L.n_in, L.n_out)) {
-        GemmX x{};
-        x.n_tiles = (L.n_out + 31) / 32; x.ksteps = (L.n_in + 15) / 16;
-        x.W = t->params + L.w; x.w_rows = L.n_out; x.w_cols = L.n_in; x.w_transpose = 0;      // split by the launcher, in its kernel's fragment order
-        x.A = In; x.frag = t->w_frag; x.C = Z; x.M = M; x.N = L.n_out; x.K = L.n_in; x.lda = ld_in; x.ldc = ldz;
-        x.alpha = alpha; x.bias = t->params + L.b; x.stats = stats; x.accumulate = 0;
-        x.act_tab = InA.tab; x.act_cols = InA.tab ? InA.cols : 0;
-        x.a_padded = (InA.padded && ld_in >= (int64_t)x.ksteps * 16) ? 1 : 0;
-        return launch_gemm_bf16x3(x, st);
-    }
-    GemmArgs g{};
-    g.A = In; g.B = t->params + L.w; g.C = Z;
-    g.M = M; g.N = L.n_out; g.K = L.n_in;
-    g.sAm = ld_in; g.sAk = 1; g.sBk = 1; g.sBn = L.n_in; g.ldc = ldz;
-    g.alpha = alpha; g.bias = t->params + L.b; g.colsum = colsum; g.flags = 0; g.splitk = 1;
-    return launch_gemm(g, st);
+// Z[M, n_out] = alpha * (In[M, K] W^T + b);  colsum (fp32 route) / stats (row route) optional
+static hipError_t linear_fwd(snerf_trainer* t, const LayerP& L, Act In, int64_t M, float* Z, int64_t ldz, float alpha, float* colsum, hipStream_t st, double* stats = nullptr, bool head = false) {
+    Product p = product_of(t, L, In, M, Z, ldz, alpha);
+    p.colsum = colsum; p.stats = stats;
+    return run_fwd(p, route_fwd(p, engine_policy(t, head)), st);
 }
-// dIn[M, n_cols] (+)= alpha * dZ[M, n_out] W[:, :n_cols]
-// `below` (optional): the SineLayer whose output gradient dIn is.  When the bf16x3 kernel runs and that layer's [a | b] table
-// exists (activation on load), its activation backward (x cos, column sums into t->bn_stats) happens in the epilogue and
-// *fused reports it: the consumer then skips its own reduction sweep.
-struct ActBelow {
-    const LayerP* L;
-    Act Z;
-    const float* tab;
-    float* bnslot;
-};
-static hipError_t linear_dgrad(snerf_trainer* t, const LayerP& L, const float* dZ, int64_t ldz, int64_t M, float* dIn, int64_t ld_in,
-                               int n_cols, float alpha, bool accumulate, hipStream_t st, const ActBelow* below = nullptr,
-                               bool* fused = nullptr) {
-    if (fused) *fused = false;
-    static const int thin = [] { const char* e = getenv("SNERF_THIN_DGRAD"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (thin && t->gemm_mode == 1 && M >= 1024 && L.n_out <= 4) {      // a thin head: a rank-K update of dIn, streamed (exact fp32)
-        ThinDgradArgs a{};
-        a.D = dZ; a.ldd = ldz; a.W = t->params + L.w; a.ldw = L.n_in; a.C = dIn; a.ldc = ld_in; a.M = M; a.K = L.n_out; a.N = n_cols;
-        a.accumulate = accumulate ? 1 : 0; a.alpha = alpha;
-        const bool act = below && below->tab && below->L->n_out == n_cols;
-        if (act) {
-            a.ez = below->Z.p; a.eld = below->Z.ld; a.etab = below->tab; a.stats = t->bn_stats;
-            if (below->L->bn) { a.emu = below->bnslot + 2 * t->W; a.eistd = below->bnslot + 3 * t->W; }
-        }
-        if (thin_dgrad_ok(a)) {
-            if (act && fused) *fused = true;
-            return launch_thin_dgrad(a, st);
-        }
-    }
-    if (rows_ok(t, M, L.n_out, n_cols)) {
-        GemmX x{};
-        x.n_tiles = (n_cols + 31) / 32; x.ksteps = (L.n_out + 15) / 16;
-        // Bt[n = input feature][k = output feature] = W[k][n]: transposed split
-        x.W = t->params + L.w; x.w_rows = L.n_out; x.w_cols = L.n_in; x.w_transpose = 1;
-        x.A = dZ; x.frag = t->w_frag; x.C = dIn; x.M = M; x.N = n_cols; x.K = L.n_out; x.lda = ldz; x.ldc = ld_in;
-        x.alpha = alpha; x.bias = nullptr; x.stats = nullptr; x.accumulate = accumulate ? 1 : 0;
-        if (below && below->tab && below->L->n_out == n_cols) {      // with `accumulate` the caller guarantees this is the last producer
-            x.stats = t->bn_stats; x.ez = below->Z.p; x.eld = below->Z.ld; x.etab = below->tab;      // sums: zero here (cleared by their last consumer)
-            if (below->L->bn) { x.emu = below->bnslot + 2 * t->W; x.eistd = below->bnslot + 3 * t->W; }
-            if (fused) *fused = true;
-        }
-        return launch_gemm_bf16x3(x, st);
-    }
-    GemmArgs g{};
-    g.A = dZ; g.B = t->params + L.w; g.C = dIn;
-    g.M = M; g.N = n_cols; g.K = L.n_out;
-    g.sAm = ldz; g.sAk = 1; g.sBk = L.n_in; g.sBn = 1; g.ldc = ld_in;
-    g.alpha = alpha; g.bias = nullptr; g.colsum = nullptr; g.flags = accumulate ? GEMM_ACCUM : 0; g.splitk = 1;
-    return launch_gemm(g, st);
+// dIn[M, n_cols] (+)= alpha * dZ[M, n_out] W[:, :n_cols];  *fused reports that the epilogue of `below` was applied
+static hipError_t linear_dgrad(snerf_trainer* t, const LayerP& L, float* dZ, int64_t ldz, int64_t M, float* dIn, int64_t ld_in, int n_cols, float alpha, bool accumulate, hipStream_t st,
+                               const ActBelow* below = nullptr, bool* fused = nullptr) {
+    Product p = product_of(t, L, Act{}, M, dZ, ldz, alpha);
+    p.dX = dIn; p.lddx = ld_in; p.n_cols = n_cols; p.accumulate = accumulate; p.below = epilogue_of(t, below, n_cols);
+    const Route r = route_dgrad(p, engine_policy(t));
+    if (fused) *fused = p.below.z && r != Route::Fp32;
+    return run_dgrad(p, r, st);
 }
-// dW[n_out, n_in] += alpha * dZ^T In   (split over the point dimension, fp32 atomics)
-// can the BatchNorm dZ pass ride in the weight-gradient kernel?  (bf16x3 path, one block column over the inputs: in-place dZ)
-// A layer with more than 256 inputs (fc5: [fc4 | PE]) goes as two launches: the first 256 input columns with the dZ pass, then the
-// rest on the finished dZ.
-static bool wgrad_bn_ok(const snerf_trainer* t, const LayerP& L, int64_t M, const Act& In) {
-    (void)L; (void)In;
-    return t->gemm_mode == 1 && M >= 1024;
-}
-static hipError_t linear_wgrad(snerf_trainer* t, const LayerP& L, float* dZ, int64_t ldz, Act InA, int64_t M, float alpha, hipStream_t st,
-                               const WgradBN* bn = nullptr) {
-    const float* In = InA.p;
-    const int64_t ld_in = InA.ld;
-    static const int thin = [] { const char* e = getenv("SNERF_THIN_WGRAD"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (thin && !bn && t->gemm_mode == 1 && M >= 1024 && L.n_out <= 4) {      // a thin head: K x n_in sums, streamed over the input (exact fp32)
-        ThinWgradArgs a{};
-        a.D = dZ; a.ldd = ldz; a.In = In; a.ldi = ld_in; a.M = M; a.K = L.n_out; a.N = L.n_in; a.alpha = alpha;
-        a.dW = t->grads + L.w; a.ldw = L.n_in; a.tab = InA.tab; a.tab_cols = InA.tab ? InA.cols : 0; a.tab_stride = a.tab_cols;
-        if (thin_wgrad_ok(a)) return launch_thin_wgrad(a, st);
-    }
-    if (t->gemm_mode == 1 && M >= 1024) {
-        if (bn && L.n_in > 256) {
-            // the activation-on-load table covers the first tc input columns: each launch gets its window of it ([a | b], b at distance tc)
-            const int n0 = 256, tc = InA.tab ? InA.cols : 0;
-            hipError_t e = launch_wgrad_bf16x3(dZ, ldz, In, ld_in, M, L.n_out, n0, alpha, t->grads + L.w, L.n_in, st, InA.tab, tc < n0 ? tc : n0, bn, tc);
-            if (e != hipSuccess) return e;
-            const int rest = tc > n0 ? tc - n0 : 0;
-            return launch_wgrad_bf16x3(dZ, ldz, In + n0, ld_in, M, L.n_out, L.n_in - n0, alpha, t->grads + L.w + n0, L.n_in, st,
-                                       rest ? InA.tab + n0 : nullptr, rest, nullptr, tc);
-        }
-        return launch_wgrad_bf16x3(dZ, ldz, In, ld_in, M, L.n_out, L.n_in, alpha, t->grads + L.w, L.n_in, st, InA.tab, InA.tab ? InA.cols : 0, bn);
-    }
-    if (bn) return hipErrorInvalidValue;
-    if (InA.tab) return hipErrorInvalidValue;
-    GemmArgs g{};
-    g.A = dZ; g.B = In; g.C = t->grads + L.w;
-    g.M = L.n_out; g.N = L.n_in; g.K = M;
-    g.sAm = 1; g.sAk = ldz; g.sBk = ld_in; g.sBn = 1; g.ldc = L.n_in;
-    g.alpha = alpha; g.bias = nullptr; g.colsum = nullptr; g.flags = GEMM_ATOMIC;
-    int64_t sk = (M + 2047) / 2048;
-    if (sk > 1024) sk = 1024;
-    if (sk < 1) sk = 1;
-    g.splitk = (int)sk;
-    return launch_gemm(g, st);
+// dW[n_out, n_in] += alpha * dZ^T In;  bn (optional, needs wgrad_rows_ok): the BatchNorm dZ pass rides in the weight-gradient kernel
+static hipError_t linear_wgrad(snerf_trainer* t, const LayerP& L, float* dZ, int64_t ldz, Act In, int64_t M, float alpha, hipStream_t st, const WgradBN* bn = nullptr) {
+    Product p = product_of(t, L, In, M, dZ, ldz, alpha);
+    p.bn = bn;
+    return run_wgrad(p, route_wgrad(p, engine_policy(t)), st);
 }
 
 // SineLayer forward in train mode: Z = 30(In W^T + b) [stashed], H = sin(BN_batch(Z)) or sin(Z)
@@ -375,23 +288,23 @@ static int sine_fwd(snerf_trainer* t, const LayerP& L, Act In, int64_t M, Act Z,
     const int64_t Mg = M * (t->ar_fn ? t->world : 1);      // rows of the global batch (equal shards per rank)
     if (L.bn) {
         float *colsum = bnslot, *m2 = bnslot + t->W, *mean = bnslot + 2 * t->W, *istd = bnslot + 3 * t->W;
-        if (train_bn && rows_ok(t, M, L.n_in, L.n_out)) {
+        if (train_bn && rows_ok(engine_policy(t), M, L.n_in, L.n_out)) {
             // batch statistics from the GEMM epilogue: shifted sums (shift = 30 b) in double, no extra pass over Z
             // t->bn_stats is zero here: every consumer of the sums clears them (and each pass starts with one memset)
             HIPCK(linear_fwd(t, L, In, M, Z.p, Z.ld, 30.f, nullptr, st, t->bn_stats));
-            RCI(all_reduce(t, t->bn_stats, 2 * C, true, st));          // the shift 30 b is the same on every rank: the sums add
+            RC(all_reduce(t, t->bn_stats, 2 * C, true, st));          // the shift 30 b is the same on every rank: the sums add
             HIPCK(launch_bn_finalize_shifted(t->bn_stats, t->params + L.b, 30.f, Mg, C, mean, istd, t->buffers + L.rm, t->buffers + L.rv,
                                              t->params + L.g, t->params + L.beta, tab_out, st));
             if (tab_out) return SNERF_OK;                               // the table is written; no sin pass with activation on load
         } else if (train_bn) {
             HIPCK(snerf_zero_async(bnslot, 0, 2 * t->W * sizeof(float), st));
             HIPCK(linear_fwd(t, L, In, M, Z.p, Z.ld, 30.f, colsum, st));
-            RCI(all_reduce(t, colsum, C, false, st));
+            RC(all_reduce(t, colsum, C, false, st));
             HIPCK(launch_bn_finalize(colsum, m2, Mg, C, mean, istd, nullptr, nullptr, 0, st));
             ColArgs ca{};
             ca.mode = 0; ca.M = M; ca.C = C; ca.ld = Z.ld; ca.Z = Z.p; ca.mu = mean; ca.out0 = m2; ca.alpha0 = 1.f;
             HIPCK(launch_colreduce(ca, st));
-            RCI(all_reduce(t, m2, C, false, st));
+            RC(all_reduce(t, m2, C, false, st));
             HIPCK(launch_bn_finalize(colsum, m2, Mg, C, mean, istd, t->buffers + L.rm, t->buffers + L.rv, 1, st));
         } else {      // eval-mode statistics (running estimates)
             HIPCK(linear_fwd(t, L, In, M, Z.p, Z.ld, 30.f, nullptr, st));
@@ -420,8 +333,9 @@ static int sine_bwd(snerf_trainer* t, const LayerP& L, Act D, Act Z, Act In, int
     if (fused_below) *fused_below = false;
     // EXPERIMENT (never on by default): the inter-layer gradient as bf16.  Rounds dL/dY (as the dgrad above would have stored it) and, behind the
     // weight-gradient kernel, dL/dZ (as it would be written back) to bf16 precision in place: the accuracy side of the idea on the real kernels.
-    static const bool dy_bf16 = getenv("SNERF_TRAIN_DY_BF16") != nullptr;
+    const bool dy_bf16 = switches().dy_bf16;
     if (dy_bf16 && pre_activated) HIPCK(launch_round_bf16(D.p, D.ld, M, C, st));
+    WgradBN bn{}, *ride = nullptr;      // ride set: the BatchNorm dZ pass rides in the weight-gradient kernel
     if (L.bn) {
         float *mean = bnslot + 2 * t->W, *istd = bnslot + 3 * t->W;
         float *sdy = t->bn_bwd, *sdyx = t->bn_bwd + t->W;
@@ -440,18 +354,12 @@ static int sine_bwd(snerf_trainer* t, const LayerP& L, Act D, Act Z, Act In, int
             HIPCK(launch_copy_cols(sdy, C, t->grads + L.beta, C, 1, C, true, st));       // parameter gradients stay per-rank sums
             HIPCK(launch_copy_cols(sdyx, C, t->grads + L.g, C, 1, C, true, st));
         }
-        RCI(all_reduce(t, t->bn_bwd, 2 * t->W, false, st));                               // the BatchNorm backward means are global
+        RC(all_reduce(t, t->bn_bwd, 2 * t->W, false, st));                               // the BatchNorm backward means are global
         const int64_t Mg = M * (t->ar_fn ? t->world : 1);
-        if (pre_activated && wgrad_bn_ok(t, L, M, In)) {
-            // D holds dL/dY: the dZ sweep rides in the weight-gradient kernel (dY -> dZ in registers, written back in place)
-            WgradBN bn{Z.p, Z.ld, t->params + L.g, mean, istd, sdy, sdyx, 1.f / (float)Mg, 30.f, t->grads + L.b};
-            HIPCK(linear_wgrad(t, L, D.p, D.ld, In, M, 30.f, st, &bn));
-            if (dy_bf16) HIPCK(launch_round_bf16(D.p, D.ld, M, C, st));
-            if (dIn.p) HIPCK(linear_dgrad(t, L, D.p, D.ld, M, dIn.p, dIn.ld, n_in_cols, 30.f, accumulate_in, st, below, fused_below));
-            return SNERF_OK;
-        }
-        HIPCK(launch_bn_bwd2(Z.p, D.p, M, C, Z.ld, D.ld, mean, istd, t->params + L.g, t->params + L.beta, sdy, sdyx, t->grads + L.b, 30.f,
-                             Mg, st, pre_activated));
+        // D holds dL/dY: the dZ sweep rides in the weight-gradient kernel (dY -> dZ in registers, written back in place) or is a pass of its own
+        bn = WgradBN{Z.p, Z.ld, t->params + L.g, mean, istd, sdy, sdyx, 1.f / (float)Mg, 30.f, t->grads + L.b};
+        if (pre_activated && wgrad_rows_ok(engine_policy(t), M)) ride = &bn;
+        else HIPCK(launch_bn_bwd2(Z.p, D.p, M, C, Z.ld, D.ld, mean, istd, t->params + L.g, t->params + L.beta, sdy, sdyx, t->grads + L.b, 30.f, Mg, st, pre_activated));
     } else if (pre_activated) {
         HIPCK(launch_act_sums_finalize(t->bn_stats, C, 30.f, nullptr, nullptr, t->grads + L.b, nullptr, st));     // d bias = 30 * sum dZ
     } else {
@@ -459,22 +367,25 @@ static int sine_bwd(snerf_trainer* t, const LayerP& L, Act D, Act Z, Act In, int
         ca.mode = 2; ca.M = M; ca.C = C; ca.ld = Z.ld; ca.ldd = D.ld; ca.Z = Z.p; ca.D = D.p; ca.out0 = t->grads + L.b; ca.alpha0 = 30.f;
         HIPCK(launch_colreduce(ca, st));
     }
-    HIPCK(linear_wgrad(t, L, D.p, D.ld, In, M, 30.f, st));
+    HIPCK(linear_wgrad(t, L, D.p, D.ld, In, M, 30.f, st, ride));
+    if (ride && dy_bf16) HIPCK(launch_round_bf16(D.p, D.ld, M, C, st));
     if (dIn.p) HIPCK(linear_dgrad(t, L, D.p, D.ld, M, dIn.p, dIn.ld, n_in_cols, 30.f, accumulate_in, st, below, fused_below));
     return SNERF_OK;
 }
 
+// The colour head (3 outputs) and the density head (1) read the same input X1, and their outputs - and output gradients - sit side by side in an [N, 4]
+// buffer Y: one K = 4 product on the thin route (row 3 of the weights / results at the density head's addresses; input gradient added to dX1).  false: the layers do not fit.
+static bool heads_product(const snerf_trainer* t, const Act& X1, int64_t N, float* Y, Product* p) {
+    const LayerP &Lc = t->layers[L_COL], &Ld = t->layers[L_SIG];
+    if (Lc.n_out != 3 || Ld.n_out != 1 || Lc.n_in != Ld.n_in) return false;
+    *p = product_of(t, Lc, X1, N, Y, 4, 1.f);
+    p->n_out = 4; p->W3 = t->params + Ld.w; p->bias3 = t->params + Ld.b; p->dW3 = t->grads + Ld.w;
+    p->dX = t->dX1.p; p->lddx = t->W2; p->n_cols = Lc.n_in; p->accumulate = true;
+    return true;
+}
 // plain Linear (heads): Out[M, n_out] = In W^T + b
-static int plain_fwd(snerf_trainer* t, const LayerP& L, Act In, int64_t M, float* Out, int64_t ldo, hipStream_t st) {
-    static const int thin = [] { const char* e = getenv("SNERF_FUSED_HEADS"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (thin && t->gemm_mode == 1 && M >= 1024 && L.n_out <= 4) {      // a head with at most four outputs: a stream over its input (thin_fwd_kernel), not a 32-column MFMA tile
-        ThinFwdArgs f{};
-        f.In = In.p; f.ldi = In.ld; f.M = M; f.K = L.n_out; f.N = L.n_in; f.alpha = 1.f; f.Out = Out; f.ldo = ldo;
-        f.W = t->params + L.w; f.ldw = L.n_in; f.bias = t->params + L.b; f.tab = In.tab; f.tab_cols = In.tab ? In.cols : 0; f.tab_stride = f.tab_cols;
-        if (thin_fwd_ok(f)) { HIPCK(launch_thin_fwd(f, st)); return SNERF_OK; }
-    }
-    HIPCK(linear_fwd(t, L, In, M, Out, ldo, 1.f, nullptr, st));
-    return SNERF_OK;
+static hipError_t plain_fwd(snerf_trainer* t, const LayerP& L, Act In, int64_t M, float* Out, int64_t ldo, hipStream_t st) {
+    return linear_fwd(t, L, In, M, Out, ldo, 1.f, nullptr, st, nullptr, true);
 }
 static int plain_bwd(snerf_trainer* t, const LayerP& L, float* dOut, int64_t ldo, Act In, int64_t M,
                      float* dIn, int64_t ld_din, bool accumulate, hipStream_t st, const ActBelow* below = nullptr, bool* fused_below = nullptr) {
@@ -484,12 +395,6 @@ static int plain_bwd(snerf_trainer* t, const LayerP& L, float* dOut, int64_t ldo
     if (dIn) HIPCK(linear_dgrad(t, L, dOut, ldo, M, dIn, ld_din, L.n_in, 1.f, accumulate, st, below, fused_below));
     return SNERF_OK;
 }
-
-#define RC(x)                 \
-    do {                      \
-        int _rc = (x);        \
-        if (_rc) return _rc;  \
-    } while (0)
 
 static int forward_pass(snerf_trainer* t, snerf_trainer::Pass& P, bool solar, int64_t R, int S, const float* top, const float* bot,
                         const float* tvals, const float* sun, const float* time, bool train_bn, hipStream_t st,
@@ -508,10 +413,9 @@ static int forward_pass(snerf_trainer* t, snerf_trainer::Pass& P, bool solar, in
     HIPCK(launch_pe_points(pa, st));
     // Activation on load (per-point layers): store only the pre-activations Z; every consumer applies sin(BN(.)) while loading.
     // Needs the bf16x3 kernels for every consumer (K <= 512, widths multiples of 16) and enough points for them to be used.
-    const bool aol = t->aol_mode == 1 && t->gemm_mode == 1 && N >= 1024 && W % 16 == 0 && gemm_rows_group_tiles((W + 64 + 15) / 16) > 0;
+    const bool aol = t->aol_mode == 1 && W % 16 == 0 && rows_ok(engine_policy(t), N, W + 64, 1);
     P.aol = aol;
-    auto tab_of = [&](int slot) { return aol ? P.tabs + (int64_t)slot * 2 * W : (float*)nullptr; };       // slots: 0-8 trunk, 9-11 adjust, 12-14 solar
-    auto view = [&](Act Z, Act H, int slot, int n) { return aol ? Act{Z.p, Z.ld, tab_of(slot), n} : H; };
+    auto view = [&](Act Z, Act H, int slot, int n) { return aol ? Act{Z.p, Z.ld, P.tab(slot, W), n} : H; };
     // fc4's output lives inside fc5's concat input [ . | PE]: its H without, its Z with activation on load
     // likewise fc9's inside fc_solar_1's concat input [ . | PE(sun)]
     P.Zc3 = aol ? Act{P.In5.p, W + 64} : P.Z[3];
@@ -519,52 +423,48 @@ static int forward_pass(snerf_trainer* t, snerf_trainer::Pass& P, bool solar, in
     auto zof = [&](int l) { return l == 3 ? P.Zc3 : (l == 8 ? P.Zc8 : P.Z[l]); };
     for (int l = 0; l < 9; ++l) P.Hc[l] = view(zof(l), P.H[l], l, l == 8 ? W2 : W);
     for (int l = 0; l < 3; ++l) { P.Hac[l] = view(P.Za[l], P.Ha[l], 9 + l, W); P.Hsc[l] = view(P.Zs[l], P.Hs[l], 12 + l, W2); }
-    P.In5c = aol ? Act{P.In5.p, W + 64, tab_of(3), W, true} : Act{P.In5.p, W + 64, nullptr, 0, true};      // column W+63 is the PE's zero pad
-    P.In_s1c = aol ? Act{P.In_s1.p, P.In_s1.ld, tab_of(8), W2, true} : Act{P.In_s1.p, P.In_s1.ld, nullptr, 0, true};
+    P.In5c = aol ? Act{P.In5.p, W + 64, P.tab(3, W), W, true} : Act{P.In5.p, W + 64, nullptr, 0, true};      // column W+63 is the PE's zero pad
+    P.In_s1c = aol ? Act{P.In_s1.p, P.In_s1.ld, P.tab(8, W), W2, true} : Act{P.In_s1.p, P.In_s1.ld, nullptr, 0, true};
     // trunk (G_NeRF.py:80-91)
-    RC(sine_fwd(t, Ls[L_FC1], Act{P.E.p, 64, nullptr, 0, true}, N, P.Z[0], P.H[0], nullptr, train_bn, st, tab_of(0)));
+    RC(sine_fwd(t, Ls[L_FC1], Act{P.E.p, 64, nullptr, 0, true}, N, P.Z[0], P.H[0], nullptr, train_bn, st, P.tab(0, W)));
     for (int l = 1; l < 9; ++l) {
         const Act In = l == 4 ? P.In5c : P.Hc[l - 1];
-        RC(sine_fwd(t, Ls[L_FC1 + l], In, N, zof(l), P.H[l], P.bn + (l - 1) * 4 * W, train_bn, st, tab_of(l)));
+        RC(sine_fwd(t, Ls[L_FC1 + l], In, N, zof(l), P.H[l], P.bn + (l - 1) * 4 * W, train_bn, st, P.tab(l, W)));
     }
     const Act X1 = P.Hc[8];
-    {   // colour (3) and density (1) heads: one stream over X1 for both where it applies (thin_fwd_kernel), else one row GEMM each
-        static const int fused = [] { const char* e = getenv("SNERF_FUSED_HEADS"); return (e && e[0] == '0') ? 0 : 1; }();
-        ThinFwdArgs f{};
-        f.In = X1.p; f.ldi = X1.ld; f.M = N; f.K = 4; f.N = Ls[L_COL].n_in; f.alpha = 1.f; f.Out = P.head.p; f.ldo = 4;
-        f.W = t->params + Ls[L_COL].w; f.ldw = Ls[L_COL].n_in; f.W3 = t->params + Ls[L_SIG].w; f.bias = t->params + Ls[L_COL].b; f.bias3 = t->params + Ls[L_SIG].b;
-        f.tab = X1.tab; f.tab_cols = X1.tab ? X1.cols : 0; f.tab_stride = f.tab_cols;
-        if (fused && t->gemm_mode == 1 && N >= 1024 && Ls[L_COL].n_out == 3 && Ls[L_SIG].n_out == 1 && Ls[L_SIG].n_in == f.N && thin_fwd_ok(f)) {
-            HIPCK(launch_thin_fwd(f, st));
+    {   // colour (3) and density (1) heads: one stream over X1 for both where it applies (thin_fwd_kernel), else one product each
+        Product hp;
+        if (heads_product(t, X1, N, P.head.p, &hp) && route_fwd(hp, engine_policy(t, true)) == Route::Thin) {
+            HIPCK(run_fwd(hp, Route::Thin, st));
         } else {
-            RC(plain_fwd(t, Ls[L_COL], X1, N, P.head.p, 4, st));
-            RC(plain_fwd(t, Ls[L_SIG], X1, N, P.head.p + 3, 4, st));
+            HIPCK(plain_fwd(t, Ls[L_COL], X1, N, P.head.p, 4, st));
+            HIPCK(plain_fwd(t, Ls[L_SIG], X1, N, P.head.p + 3, 4, st));
         }
     }
     // solar visibility branch (G_NeRF.py:100-108)
     HIPCK(launch_pe_small(sun, 3, 3, 4, R, P.pe_sun, 28, st));
     if (!aol) HIPCK(launch_copy_cols(X1.p, X1.ld, P.In_s1.p, P.In_s1.ld, N, W2, false, st));
     HIPCK(launch_bcast_rows(P.pe_sun, 28, P.In_s1.p, P.In_s1.ld, W2, N, S, st));
-    RC(sine_fwd(t, Ls[L_S1], P.In_s1c, N, P.Zs[0], P.Hs[0], nullptr, train_bn, st, tab_of(12)));
-    RC(sine_fwd(t, Ls[L_S2], P.Hsc[0], N, P.Zs[1], P.Hs[1], nullptr, train_bn, st, tab_of(13)));
-    RC(sine_fwd(t, Ls[L_S3], P.Hsc[1], N, P.Zs[2], P.Hs[2], nullptr, train_bn, st, tab_of(14)));
-    RC(plain_fwd(t, Ls[L_S4], P.Hsc[2], N, P.sv_raw.p, 1, st));
+    RC(sine_fwd(t, Ls[L_S1], P.In_s1c, N, P.Zs[0], P.Hs[0], nullptr, train_bn, st, P.tab(12, W)));
+    RC(sine_fwd(t, Ls[L_S2], P.Hsc[0], N, P.Zs[1], P.Hs[1], nullptr, train_bn, st, P.tab(13, W)));
+    RC(sine_fwd(t, Ls[L_S3], P.Hsc[1], N, P.Zs[2], P.Hs[2], nullptr, train_bn, st, P.tab(14, W)));
+    HIPCK(plain_fwd(t, Ls[L_S4], P.Hsc[2], N, P.sv_raw.p, 1, st));
     // sky colour head (G_NeRF.py:110-111), per ray
     RC(sine_fwd(t, Ls[L_K1], Act{P.pe_sun, 28}, R, Act{P.Zk1, W4}, Act{P.Hk1, W4}, nullptr, train_bn, st));
-    RC(plain_fwd(t, Ls[L_K2], Act{P.Hk1, W4}, R, P.sky_raw, 3, st));
+    HIPCK(plain_fwd(t, Ls[L_K2], Act{P.Hk1, W4}, R, P.sky_raw, 3, st));
     HIPCK(launch_sigmoid(P.sky_raw, P.sky, R * 3, st));
     PointOutArgs po{};
     po.n = N; po.n_samples = S; po.C = C; po.head = P.head.p; po.sv_raw = P.sv_raw.p; po.rho = P.rho; po.sv = P.sv;
     if (!solar) {
         // seasonal colour-adjust branch (T_NeRF_net_v2.py:83-88) and time -> class softmax (:77-78, per ray)
-        RC(sine_fwd(t, Ls[L_A1], X1, N, P.Za[0], P.Ha[0], nullptr, train_bn, st, tab_of(9)));
-        RC(sine_fwd(t, Ls[L_A2], P.Hac[0], N, P.Za[1], P.Ha[1], nullptr, train_bn, st, tab_of(10)));
-        RC(sine_fwd(t, Ls[L_A3], P.Hac[1], N, P.Za[2], P.Ha[2], nullptr, train_bn, st, tab_of(11)));
-        RC(plain_fwd(t, Ls[L_AC], P.Hac[2], N, P.adj.p, 3 * C, st));
+        RC(sine_fwd(t, Ls[L_A1], X1, N, P.Za[0], P.Ha[0], nullptr, train_bn, st, P.tab(9, W)));
+        RC(sine_fwd(t, Ls[L_A2], P.Hac[0], N, P.Za[1], P.Ha[1], nullptr, train_bn, st, P.tab(10, W)));
+        RC(sine_fwd(t, Ls[L_A3], P.Hac[1], N, P.Za[2], P.Ha[2], nullptr, train_bn, st, P.tab(11, W)));
+        HIPCK(plain_fwd(t, Ls[L_AC], P.Hac[2], N, P.adj.p, 3 * C, st));
         HIPCK(launch_pe_small(time, 4, 2, 2, R, P.pe_time, 12, st));
         RC(sine_fwd(t, Ls[L_T1], Act{P.pe_time, 12}, R, Act{P.Zt1, W}, Act{P.Ht1, W}, nullptr, train_bn, st));
         RC(sine_fwd(t, Ls[L_T2], Act{P.Ht1, W}, R, Act{P.Zt2, W}, Act{P.Ht2, W}, nullptr, train_bn, st));
-        RC(plain_fwd(t, Ls[L_CL], Act{P.Ht2, W}, R, P.logits, C, st));
+        HIPCK(plain_fwd(t, Ls[L_CL], Act{P.Ht2, W}, R, P.logits, C, st));
         HIPCK(launch_softmax(P.logits, P.cls, R, C, st));
         po.adj = P.adj.p; po.cls = P.cls; po.col = P.col; po.adjust_col = adjust_col_out;
     }
@@ -770,32 +670,25 @@ int snerf_trainer_backward_points(snerf_trainer* t, const float* d_g_rho, const 
     return network_backward_image(t, d_g_solar_vis != nullptr, d_g_classes, st);
 }
 
-// The colour head (3 outputs) and the density head (1) read the same input X1 and their output gradients sit side by side in d_head [N, 4]: ONE stream over X1
-// for both weight gradients and ONE read-modify-write of dX1 for both input gradients (K = 4, row 3 of the weights / of the result at the density head's
-// address) instead of two of each.  Returns false - nothing launched - where the streams do not apply (SNERF_FUSED_HEADS=0, small batches, exact-fp32 mode).
-static bool heads_bwd_fused(snerf_trainer* t, const Act& X1, int64_t N, const ActBelow* below, bool* fused_below, hipStream_t st) {
-    static const int on = [] { const char* e = getenv("SNERF_FUSED_HEADS"); return (e && e[0] == '0') ? 0 : 1; }();
-    const LayerP &Lc = t->layers[L_COL], &Ls_ = t->layers[L_SIG];
-    if (fused_below) *fused_below = false;
-    if (!on || t->gemm_mode != 1 || N < 1024 || Lc.n_out != 3 || Ls_.n_out != 1 || Lc.n_in != Ls_.n_in) return false;
-    ThinWgradArgs w{};
-    w.D = t->d_head; w.ldd = 4; w.In = X1.p; w.ldi = X1.ld; w.M = N; w.K = 4; w.N = Lc.n_in; w.alpha = 1.f;
-    w.dW = t->grads + Lc.w; w.ldw = Lc.n_in; w.dW3 = t->grads + Ls_.w; w.tab = X1.tab; w.tab_cols = X1.tab ? X1.cols : 0; w.tab_stride = w.tab_cols;
-    ThinDgradArgs a{};
-    a.D = t->d_head; a.ldd = 4; a.W = t->params + Lc.w; a.W3 = t->params + Ls_.w; a.ldw = Lc.n_in; a.C = t->dX1.p; a.ldc = t->W2; a.M = N; a.K = 4; a.N = Lc.n_in;
-    a.accumulate = 1; a.alpha = 1.f;
-    const bool act = below && below->tab && below->L->n_out == Lc.n_in;
-    if (act) {
-        a.ez = below->Z.p; a.eld = below->Z.ld; a.etab = below->tab; a.stats = t->bn_stats;
-        if (below->L->bn) { a.emu = below->bnslot + 2 * t->W; a.eistd = below->bnslot + 3 * t->W; }
+// Backward of the colour and density heads: where the K = 4 form applies (heads_product; SNERF_FUSED_HEADS, bf16x3 mode, enough rows), ONE stream over X1 for
+// both weight gradients and ONE read-modify-write of dX1 for both input gradients instead of two of each.  Which form runs is decided before the first
+// launch: both accumulate into the same gradients, so a failed launch is an error, never a reason to run the other form.
+static int heads_bwd(snerf_trainer* t, const Act& X1, int64_t N, const ActBelow* below, bool* fused_below, hipStream_t st) {
+    const LayerP &Lc = t->layers[L_COL], &Ld = t->layers[L_SIG];
+    const Policy pol = engine_policy(t, true);
+    Product p;
+    const bool fits = heads_product(t, X1, N, t->d_head, &p);
+    if (fits) p.below = epilogue_of(t, below, p.n_cols);
+    if (!fits || route_wgrad(p, pol) != Route::Thin || route_dgrad(p, pol) != Route::Thin) {
+        RC(plain_bwd(t, Lc, t->d_head, 4, X1, N, t->dX1.p, t->W2, true, st));
+        return plain_bwd(t, Ld, t->d_head + 3, 4, X1, N, t->dX1.p, t->W2, true, st, below, fused_below);
     }
-    if (!thin_wgrad_ok(w) || !thin_dgrad_ok(a)) return false;
-    if (launch_thin_wgrad(w, st) != hipSuccess) return false;
-    if (launch_colsum(t->d_head, N, 3, 4, 1.f, t->grads + Lc.b, st) != hipSuccess) return false;
-    if (launch_colsum(t->d_head + 3, N, 1, 4, 1.f, t->grads + Ls_.b, st) != hipSuccess) return false;
-    if (launch_thin_dgrad(a, st) != hipSuccess) return false;
-    if (act && fused_below) *fused_below = true;
-    return true;
+    HIPCK(run_wgrad(p, Route::Thin, st));
+    HIPCK(launch_colsum(t->d_head, N, 3, 4, 1.f, t->grads + Lc.b, st));
+    HIPCK(launch_colsum(t->d_head + 3, N, 1, 4, 1.f, t->grads + Ld.b, st));
+    HIPCK(run_dgrad(p, Route::Thin, st));
+    if (fused_below) *fused_below = p.below.z != nullptr;
+    return SNERF_OK;
 }
 
 static int network_backward_image(snerf_trainer* t, bool classic, const float* d_g_classes, hipStream_t st) {
@@ -814,10 +707,9 @@ static int network_backward_image(snerf_trainer* t, bool classic, const float* d
     const Act X1 = P.Hc[8];
     // adjust branch
     // `pre`: did the dgrad that produced this layer's output gradient already apply its activation backward (ActBelow)?
-    auto tab_of = [&](int slot) { return P.aol ? P.tabs + (int64_t)slot * 2 * W : (const float*)nullptr; };   // slots as in forward_pass
     bool pre = false;
     {
-        const ActBelow b3{&Ls[L_A3], P.Za[2], tab_of(11), nullptr}, b2{&Ls[L_A2], P.Za[1], tab_of(10), nullptr}, b1{&Ls[L_A1], P.Za[0], tab_of(9), nullptr};
+        const ActBelow b3{&Ls[L_A3], P.Za[2], P.tab(11, W), nullptr}, b2{&Ls[L_A2], P.Za[1], P.tab(10, W), nullptr}, b1{&Ls[L_A1], P.Za[0], P.tab(9, W), nullptr};
         RC(plain_bwd(t, Ls[L_AC], t->d_adj, 3 * C, P.Hac[2], N, t->dA.p, W, false, st, &b3, &pre));
         RC(sine_bwd(t, Ls[L_A3], Act{t->dA.p, W}, P.Za[2], P.Hac[1], N, nullptr, Act{t->dB.p, W}, W, false, st, pre, &b2, &pre));
         RC(sine_bwd(t, Ls[L_A2], Act{t->dB.p, W}, P.Za[1], P.Hac[0], N, nullptr, Act{t->dA.p, W}, W, false, st, pre, &b1, &pre));
@@ -826,14 +718,11 @@ static int network_backward_image(snerf_trainer* t, bool classic, const float* d
     // sigma / colour heads
     // dL/dX1 is summed from the adjust branch, the two heads and (classic solar) the solar branch: the LAST of these dgrads
     // also applies fc9's activation backward in its epilogue
-    const ActBelow b9{&Ls[L_FC9], P.Zc8, tab_of(8), P.bn + 7 * 4 * W};
+    const ActBelow b9{&Ls[L_FC9], P.Zc8, P.tab(8, W), P.bn + 7 * 4 * W};
     bool pre9 = false;
-    if (!heads_bwd_fused(t, X1, N, classic ? nullptr : &b9, classic ? nullptr : &pre9, st)) {
-        RC(plain_bwd(t, Ls[L_COL], t->d_head, 4, X1, N, t->dX1.p, W2, true, st));
-        RC(plain_bwd(t, Ls[L_SIG], t->d_head + 3, 4, X1, N, t->dX1.p, W2, true, st, classic ? nullptr : &b9, classic ? nullptr : &pre9));
-    }
+    RC(heads_bwd(t, X1, N, classic ? nullptr : &b9, classic ? nullptr : &pre9, st));
     if (classic) {      // the solar-visibility branch carries gradient from the image (G_NeRF.py:100-108), on into X1
-        const ActBelow s3{&Ls[L_S3], P.Zs[2], tab_of(14), nullptr}, s2{&Ls[L_S2], P.Zs[1], tab_of(13), nullptr}, s1{&Ls[L_S1], P.Zs[0], tab_of(12), nullptr};
+        const ActBelow s3{&Ls[L_S3], P.Zs[2], P.tab(14, W), nullptr}, s2{&Ls[L_S2], P.Zs[1], P.tab(13, W), nullptr}, s1{&Ls[L_S1], P.Zs[0], P.tab(12, W), nullptr};
         RC(plain_bwd(t, Ls[L_S4], t->d_sv_raw, 1, P.Hsc[2], N, t->dA.p, W2, false, st, &s3, &pre));
         RC(sine_bwd(t, Ls[L_S3], Act{t->dA.p, W2}, P.Zs[2], P.Hsc[1], N, nullptr, Act{t->dB.p, W2}, W2, false, st, pre, &s2, &pre));
         RC(sine_bwd(t, Ls[L_S2], Act{t->dB.p, W2}, P.Zs[1], P.Hsc[0], N, nullptr, Act{t->dA.p, W2}, W2, false, st, pre, &s1, &pre));
@@ -843,7 +732,7 @@ static int network_backward_image(snerf_trainer* t, bool classic, const float* d
     float* cur = t->dA.p;
     float* nxt = t->dB.p;
     auto below_of = [&](int l) {        // trunk layer l (fc{l+1}) as the consumer of a dgrad's output
-        return ActBelow{&Ls[L_FC1 + l], l == 3 ? P.Zc3 : (l == 8 ? P.Zc8 : P.Z[l]), tab_of(l), l >= 1 ? P.bn + (l - 1) * 4 * W : nullptr};
+        return ActBelow{&Ls[L_FC1 + l], l == 3 ? P.Zc3 : (l == 8 ? P.Zc8 : P.Z[l]), P.tab(l, W), l >= 1 ? P.bn + (l - 1) * 4 * W : nullptr};
     };
     {
         const ActBelow b = below_of(7);
@@ -901,8 +790,7 @@ int snerf_trainer_backward_solar(snerf_trainer* t, const float* d_g_solar_vis, v
     PointOutArgs po{};
     po.n = N; po.n_samples = t->S; po.C = t->C; po.head = P.head.p; po.sv = P.sv; po.d_sv = d_g_solar_vis; po.d_sv_raw = t->d_sv_raw;
     HIPCK(launch_point_out(po, true, st));
-    auto tab_of = [&](int slot) { return P.aol ? P.tabs + (int64_t)slot * 2 * t->W : (const float*)nullptr; };
-    const ActBelow s3{&Ls[L_S3], P.Zs[2], tab_of(14), nullptr}, s2{&Ls[L_S2], P.Zs[1], tab_of(13), nullptr}, s1{&Ls[L_S1], P.Zs[0], tab_of(12), nullptr};
+    const ActBelow s3{&Ls[L_S3], P.Zs[2], P.tab(14, t->W), nullptr}, s2{&Ls[L_S2], P.Zs[1], P.tab(13, t->W), nullptr}, s1{&Ls[L_S1], P.Zs[0], P.tab(12, t->W), nullptr};
     bool pre = false;
     RC(plain_bwd(t, Ls[L_S4], t->d_sv_raw, 1, P.Hsc[2], N, t->dA.p, W2, false, st, &s3, &pre));
     RC(sine_bwd(t, Ls[L_S3], Act{t->dA.p, W2}, P.Zs[2], P.Hsc[1], N, nullptr, Act{t->dB.p, W2}, W2, false, st, pre, &s2, &pre));
@@ -930,44 +818,22 @@ size_t snerf_linear_scratch_bytes(int n_out, int n_in) {
     return (size_t)(((d + 31) / 32) * ((d + 15) / 16) * 2048 + 256);
 }
 
-static int linear_mode(int precision, int64_t M, int K, int N) {      // 1 = bf16x3 kernel applicable and requested
-    return (precision == 1 && M >= 1 && K >= 1 && N >= 1 && gemm_rows_group_tiles((K + 15) / 16) > 0) ? 1 : 0;
-}
-
+// a public call as a caller: bf16x3 from the first row on when asked for by `precision`; its dgrad never streams
+static Policy public_policy(int precision) { return Policy{precision == 1, 1, true, false}; }
 int snerf_linear_forward(int64_t n_points, int n_in, int n_out, const float* d_in, int64_t ld_in, const float* d_weight,
                          const float* d_bias, float alpha, float* d_out, int64_t ld_out, double* d_stats, int precision,
                          void* d_scratch, size_t scratch_bytes, const float* d_act_tab, int act_cols, void* stream) {
     if (n_points < 0 || n_in < 1 || n_out < 1) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: bad shape");
     if (n_points == 0) return SNERF_OK;
     if (!d_in || !d_weight || !d_out || ld_in < n_in || ld_out < n_out) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (precision == 1 && n_out <= 4 && n_points >= 1024 && d_bias && !d_stats) {      // a thin head: the stream the training engine uses for the colour + density heads
-        ThinFwdArgs f{};
-        f.In = d_in; f.ldi = ld_in; f.M = n_points; f.K = n_out; f.N = n_in; f.alpha = alpha; f.Out = d_out; f.ldo = ld_out;
-        f.W = d_weight; f.ldw = n_in; f.bias = d_bias; f.tab = d_act_tab; f.tab_cols = d_act_tab ? act_cols : 0; f.tab_stride = f.tab_cols;
-        static const int fused = [] { const char* e = getenv("SNERF_FUSED_HEADS"); return (e && e[0] == '0') ? 0 : 1; }();
-        if (fused && thin_fwd_ok(f)) { HIPCK(launch_thin_fwd(f, st)); return SNERF_OK; }
-    }
-    if (linear_mode(precision, n_points, n_in, n_out)) {
-        if (!d_scratch || scratch_bytes < snerf_linear_scratch_bytes(n_out, n_in)) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: scratch too small");
-        GemmX x{};
-        x.n_tiles = (n_out + 31) / 32; x.ksteps = (n_in + 15) / 16;
-        x.W = d_weight; x.w_rows = n_out; x.w_cols = n_in; x.w_transpose = 0;
-        x.A = d_in; x.frag = (const uint16_t*)d_scratch; x.C = d_out; x.M = n_points; x.N = n_out; x.K = n_in; x.lda = ld_in; x.ldc = ld_out;
-        x.alpha = alpha; x.bias = d_bias; x.stats = d_stats; x.accumulate = 0;
-        if (d_act_tab) {
-            if (act_cols < 8 || act_cols % 8 || act_cols > n_in) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: act_cols must be a multiple of 8 within n_in");
-            x.act_tab = d_act_tab; x.act_cols = act_cols;
-        }
-        HIPCK(launch_gemm_bf16x3(x, st));
-        return SNERF_OK;
-    }
-    if (d_stats || d_act_tab) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: column statistics / activation on load need the bf16x3 path");
-    GemmArgs g{};
-    g.A = d_in; g.B = d_weight; g.C = d_out; g.M = n_points; g.N = n_out; g.K = n_in;
-    g.sAm = ld_in; g.sAk = 1; g.sBk = 1; g.sBn = n_in; g.ldc = ld_out;
-    g.alpha = alpha; g.bias = d_bias; g.colsum = nullptr; g.flags = 0; g.splitk = 1;
-    HIPCK(launch_gemm(g, st));
+    if (d_act_tab && (act_cols < 8 || act_cols % 8 || act_cols > n_in)) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: act_cols must be a multiple of 8 within n_in");
+    Product p;
+    p.M = n_points; p.n_in = n_in; p.n_out = n_out; p.alpha = alpha; p.W = d_weight; p.bias = d_bias; p.frag = (const uint16_t*)d_scratch;
+    p.X = d_in; p.ldx = ld_in; p.tab = d_act_tab; p.tab_cols = d_act_tab ? act_cols : 0; p.Y = d_out; p.ldy = ld_out; p.stats = d_stats;
+    const Route r = route_fwd(p, public_policy(precision));
+    if (r == Route::Rows && (!d_scratch || scratch_bytes < snerf_linear_scratch_bytes(n_out, n_in))) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: scratch too small");
+    if (r == Route::Fp32 && (d_stats || d_act_tab)) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: column statistics / activation on load need the bf16x3 path");
+    HIPCK(run_fwd(p, r, (hipStream_t)stream));
     return SNERF_OK;
 }
 
@@ -978,28 +844,16 @@ int snerf_linear_dgrad(int64_t n_points, int n_in, int n_out, const float* d_gra
     if (n_points < 0 || n_in < 1 || n_out < 1 || n_cols < 1 || n_cols > n_in) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: bad shape");
     if (n_points == 0) return SNERF_OK;
     if (!d_grad_out || !d_weight || !d_grad_in || ld_go < n_out || ld_gi < n_cols) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (linear_mode(precision, n_points, n_out, n_cols)) {
-        if (!d_scratch || scratch_bytes < snerf_linear_scratch_bytes(n_out, n_in)) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: scratch too small");
-        GemmX x{};
-        x.n_tiles = (n_cols + 31) / 32; x.ksteps = (n_out + 15) / 16;
-        x.W = d_weight; x.w_rows = n_out; x.w_cols = n_in; x.w_transpose = 1;
-        x.A = d_grad_out; x.frag = (const uint16_t*)d_scratch; x.C = d_grad_in; x.M = n_points; x.N = n_cols; x.K = n_out; x.lda = ld_go; x.ldc = ld_gi;
-        x.alpha = alpha; x.bias = nullptr; x.stats = nullptr; x.accumulate = accumulate ? 1 : 0;
-        if (d_below_z) {
-            if (!d_below_tab || !d_sums || ld_below_z < n_cols || (!d_below_mu) != (!d_below_istd))
-                return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: the activation-backward epilogue needs table and sums");
-            x.ez = d_below_z; x.eld = ld_below_z; x.etab = d_below_tab; x.emu = d_below_mu; x.eistd = d_below_istd; x.stats = d_sums;
-        }
-        HIPCK(launch_gemm_bf16x3(x, st));
-        return SNERF_OK;
-    }
-    if (d_below_z) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: the activation-backward epilogue needs the bf16x3 path");
-    GemmArgs g{};
-    g.A = d_grad_out; g.B = d_weight; g.C = d_grad_in; g.M = n_points; g.N = n_cols; g.K = n_out;
-    g.sAm = ld_go; g.sAk = 1; g.sBk = n_in; g.sBn = 1; g.ldc = ld_gi;
-    g.alpha = alpha; g.bias = nullptr; g.colsum = nullptr; g.flags = accumulate ? GEMM_ACCUM : 0; g.splitk = 1;
-    HIPCK(launch_gemm(g, st));
+    if (d_below_z && (!d_below_tab || !d_sums || ld_below_z < n_cols || (!d_below_mu) != (!d_below_istd)))
+        return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: the activation-backward epilogue needs table and sums");
+    Product p;
+    p.M = n_points; p.n_in = n_in; p.n_out = n_out; p.alpha = alpha; p.W = d_weight; p.Y = const_cast<float*>(d_grad_out); p.ldy = ld_go;      // (Y: read-only here)
+    p.dX = d_grad_in; p.lddx = ld_gi; p.n_cols = n_cols; p.accumulate = accumulate != 0; p.frag = (const uint16_t*)d_scratch;
+    if (d_below_z) { p.below.z = d_below_z; p.below.ld = ld_below_z; p.below.tab = d_below_tab; p.below.mu = d_below_mu; p.below.istd = d_below_istd; p.below.sums = d_sums; }
+    const Route r = route_dgrad(p, public_policy(precision));
+    if (r == Route::Fp32 && d_below_z) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: the activation-backward epilogue needs the bf16x3 path");
+    if (r == Route::Rows && (!d_scratch || scratch_bytes < snerf_linear_scratch_bytes(n_out, n_in))) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: scratch too small");
+    HIPCK(run_dgrad(p, r, (hipStream_t)stream));
     return SNERF_OK;
 }
 
@@ -1009,27 +863,12 @@ int snerf_linear_wgrad(int64_t n_points, int n_in, int n_out, const float* d_gra
     if (n_points < 0 || n_in < 1 || n_out < 1) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_wgrad: bad shape");
     if (n_points == 0) return SNERF_OK;
     if (!d_grad_out || !d_in || !d_grad_weight || ld_go < n_out || ld_in < n_in) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_wgrad: bad argument");
-    hipStream_t st = (hipStream_t)stream;
     if (d_act_tab && (precision != 1 || act_cols < 1 || act_cols > n_in))
         return snerf_set_error(SNERF_E_INVALID, "snerf_linear_wgrad: activation on load needs the bf16x3 path and 1 <= act_cols <= n_in");
-    if (precision == 1) {
-        if (n_out <= 4 && n_points >= 1024) {      // the thin heads' stream, as the training engine routes them (linear_wgrad)
-            ThinWgradArgs a{};
-            a.D = d_grad_out; a.ldd = ld_go; a.In = d_in; a.ldi = ld_in; a.M = n_points; a.K = n_out; a.N = n_in; a.alpha = alpha;
-            a.dW = d_grad_weight; a.ldw = n_in; a.tab = d_act_tab; a.tab_cols = d_act_tab ? act_cols : 0; a.tab_stride = a.tab_cols;
-            static const int thin = [] { const char* e = getenv("SNERF_THIN_WGRAD"); return (e && e[0] == '0') ? 0 : 1; }();
-            if (thin && thin_wgrad_ok(a)) { HIPCK(launch_thin_wgrad(a, st)); return SNERF_OK; }
-        }
-        HIPCK(launch_wgrad_bf16x3(const_cast<float*>(d_grad_out), ld_go, d_in, ld_in, n_points, n_out, n_in, alpha, d_grad_weight, n_in, st, d_act_tab, act_cols));      // read-only without the BatchNorm option
-        return SNERF_OK;
-    }
-    GemmArgs g{};
-    g.A = d_grad_out; g.B = d_in; g.C = d_grad_weight; g.M = n_out; g.N = n_in; g.K = n_points;
-    g.sAm = 1; g.sAk = ld_go; g.sBk = ld_in; g.sBn = 1; g.ldc = n_in;
-    g.alpha = alpha; g.bias = nullptr; g.colsum = nullptr; g.flags = GEMM_ATOMIC;
-    int64_t sk = (n_points + 2047) / 2048;
-    g.splitk = (int)(sk > 1024 ? 1024 : (sk < 1 ? 1 : sk));
-    HIPCK(launch_gemm(g, st));
+    Product p;
+    p.M = n_points; p.n_in = n_in; p.n_out = n_out; p.alpha = alpha; p.dW = d_grad_weight; p.Y = const_cast<float*>(d_grad_out); p.ldy = ld_go;      // (Y: read-only without the BatchNorm option)
+    p.X = d_in; p.ldx = ld_in; p.tab = d_act_tab; p.tab_cols = d_act_tab ? act_cols : 0;
+    HIPCK(run_wgrad(p, route_wgrad(p, public_policy(precision)), (hipStream_t)stream));
     return SNERF_OK;
 }
 

@@ -79,6 +79,23 @@ def test_error_paths(lib):
     lib.snerf_model_destroy(m)
 
 
+def test_linear_calls_validate_the_activation_table_before_they_route(lib):
+    """snerf_linear_forward / snerf_linear_wgrad check d_act_tab / act_cols as include/season_nerf_hip.h documents them before a route is chosen: a thin-head
+    shape (precision 1, at most four outputs, >= 1024 points, bias, no statistics - the exact-fp32 stream) is held to the same conditions as the row GEMM.
+    Nothing is launched and no pointer is read: validation returns first, so any aligned non-null address will do and no GPU is needed."""
+    buf = np.zeros(64, dtype=np.float32)
+    a = (buf.ctypes.data + 63) // 64 * 64
+    for n_points in (1024, 5000):
+        for act_cols in (12, 100, 136, 0, -8):              # not a multiple of 8 / larger than n_in = 128 / empty
+            rc = lib.snerf_linear_forward(n_points, 128, 3, a, 128, a, a, 1.0, a, 4, None, 1, a, 1 << 20, a, act_cols, None)
+            assert rc == -1 and b"act_cols" in lib.snerf_last_error(), (n_points, act_cols, rc)       # SNERF_E_INVALID
+        rc = lib.snerf_linear_wgrad(n_points, 128, 3, a, 4, a, 128, 1.0, a, 1, a, 136, None)
+        assert rc == -1 and b"act_cols" in lib.snerf_last_error(), (n_points, rc)
+    # the row-GEMM shapes answer the same way (as before)
+    assert lib.snerf_linear_forward(512, 128, 64, a, 128, a, a, 1.0, a, 64, None, 1, a, 1 << 20, a, 12, None) == -1 and b"act_cols" in lib.snerf_last_error()
+    assert lib.snerf_linear_wgrad(512, 128, 64, a, 64, a, 128, 1.0, a, 1, a, 129, None) == -1 and b"act_cols" in lib.snerf_last_error()
+
+
 def test_product_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
