@@ -18,6 +18,8 @@
 //  SNERF_X2_GROUPS switch below), waves 4-7 running their epilogue slices in the odd k-steps and waves 0-3 in the even ones.
 //  So the two waves running in step is not what leaves the matrix pipe 40 % idle; the chip holds 1.8 GHz in this kernel.
 //  Weight stream, tables, digit formats, accuracy: exactly those of kernels_i8.hip (same packed model, bit-identical results).
+#include <type_traits>
+
 #include "mlp_i8_device.h"
 
 namespace snerf {
@@ -162,6 +164,86 @@ __device__ __forceinline__ TabQ load_tab_quad_h(lds_cfloat* tab_h, int b, int g)
     t.bi = tp[4 + g];
     return t;
 }
+// A layer's last block handed to the next layer (run_layer8x2): its merged sums wait in m[16], and the receiving layer runs the four
+// quads of that block inside its own block 0.  TAB = the producing layer's table start (floats from the table base), NB its block
+// count, SIN / RAWL its epilogue.  DEP: the producer's output is the receiver's first input, so block NB - 1 is the B operand of
+// k-step NB - 1 of every block of the receiver and all four quads must be complete before that k-step of block 0.
+template <int TAB_, int NB_, bool SIN_, bool RAWL_, bool DEP_>
+struct Carry {
+    static constexpr bool on = true, SIN = SIN_, RAWL = RAWL_, DEP = DEP_;
+    static constexpr int TAB = TAB_, NB = NB_;
+};
+struct NoCarry {
+    static constexpr bool on = false, SIN = false, RAWL = false, DEP = false;
+    static constexpr int TAB = 0, NB = 1;
+};
+// a carried block can be taken when the receiver has a k-step in front of the one that reads it
+__host__ __device__ constexpr bool carry_fits(int nb, bool dep) { return !dep || nb >= 2; }
+// where the carried block's results go: the producer's digit fragments (block NB - 1) or raw floats, and its raw coordinates (RAWL)
+struct CarryDst {
+    Frag8* out;
+    f32x16* raw;
+    const float* rawx;
+};
+
+// what crosses a layer boundary in registers: the merged sums of the producer's last block (HANDOFF / PEND) and the receiver's first PFX
+// weight-fragment pairs, requested by the producer in its last PFX k-steps (PRE_OUT / PRE_IN)
+struct Boundary {
+    int m[16];
+    i32x4 fT[PFX], fL[PFX];
+};
+
+// epilogue of elements 4g .. 4g+3 of one block from its merged sums m[]: digits into ob (SIN) or floats into raw
+template <bool SIN, bool RAWL>
+__device__ __forceinline__ void epi_quad(const int* m, int g, const TabQ& t, const f32x4* rqg, const float* rawx, Frag8* ob, f32x16* raw) {
+    float v[4];
+#if defined(SNERF_ABLATE) && (ABL & 16)   // timing-only: no epilogue arithmetic at all but the digit split
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = __builtin_bit_cast(float, (m[4 * g + j] & 0x007fffff) | 0x3f000000) - 0.75f;
+#else
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf((float)m[4 * g + j], t.sc[j], t.bi[j]);
+    if constexpr (RAWL) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            v[j] = __builtin_fmaf(rqg[0][j], rawx[0], __builtin_fmaf(rqg[1][j], rawx[1], __builtin_fmaf(rqg[2][j], rawx[2], v[j])));
+    }
+#endif
+    if constexpr (SIN) {
+#if defined(SNERF_ABLATE) && (ABL & 8)    // timing-only: no transcendental; 2 fract(z) - 1 keeps the data as random as sin does
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(__builtin_amdgcn_fractf(v[j]), 2.f, -1.f);
+#elif !(defined(SNERF_ABLATE) && (ABL & 16))
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = sin2pi(v[j]);
+#endif
+        int hi, lo;
+        digits4(v[0], v[1], v[2], v[3], hi, lo);
+        asm volatile("" : "+v"(hi), "+v"(lo));       // the digits exist HERE (nothing may sink the epilogue towards their first use)
+        ob->hi[g] = hi;
+        ob->lo[g] = lo;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) (*raw)[4 * g + j] = v[j];
+    }
+}
+
+// The field chain's boundaries (field_tiles2).  A layer's output is its successor's first input everywhere but behind the two one-block
+// raw heads: fc_solar_1 reads x1f, not the colour / density head, and adjust_layer_1 reads x1f, not fc_solar_4.
+__host__ __device__ constexpr bool field_feeds_next(int l) { return l != F_HEAD && l != F_S4; }
+// the last layer of a variant's chain: the tile's outputs are read right behind it
+__host__ __device__ constexpr int field_last(int variant) { return variant == 0 ? F_AC : variant == 1 ? F_S4 : F_HEAD; }
+// One flag per boundary and instantiation: does layer l hand its last block to the next layer?  Not the last layer of a variant (the tile's
+// outputs are read right behind it), and not where a one-block producer feeds k-step 0 (W = 64).  The register file is full
+// (256 registers, no scratch: tests/test_isa_guards.py): a boundary that costs an instantiation a register is switched off HERE and
+// stays exposed as before.
+__host__ __device__ constexpr bool field_carries(int W, int variant, int C, int l) {
+#ifdef SNERF_X2_NO_CARRY      // A/B: every boundary exposed (the kernel before the carry)
+    return false;
+#endif
+    return l != field_last(variant) && carry_fits(prog_layer(PROG_FIELD, W, C, l, FMT_I8).n_out / 32, field_feeds_next(l));
+}
+
 // One fused layer (see run_layer8 in kernels_i8.hip for the arithmetic).  Chunk boundaries of the read sequence are compile-time
 // positions; every layer starts on one.  The whole layer is ONE basic block for the compiler (no branch): with branches inside
 // it hipcc sinks every block's epilogue to the end of the layer and spills the accumulators meanwhile (measured, 2.4 KB scratch).
@@ -173,11 +255,33 @@ __device__ __forceinline__ TabQ load_tab_quad_h(lds_cfloat* tab_h, int b, int g)
 //   drops to 13 %, the kernel gains 2.5 %.  Tried on top without gain: the epilogue slices in the k-steps where a wave yields,
 //   biased levels ({0,2} against {1,3}: the younger wave then takes the older one's place), alternating the tie-break per
 //   k-step pair / per block (the two waves' barrier times even out, their sum and the kernel time do not change).
-template <int NB, int KS0, int KS1, bool SIN, bool RAWL = false, int PHASE = 0, bool OPQ = false>
-__device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, uint32_t stream_bytes, lds_char* lds, lds_cfloat* tab_l,
-                                             const Frag8* in0, const Frag8* in1, Frag8* out, f32x16* raw, int wave, int lane,
-                                             const float* rawx = nullptr) {
+//   PEND / HANDOFF: the layer boundary.  Inside a layer the epilogue of block b - 1 hides in block b's k-steps; the last block has no
+//   successor in its own layer, and block 0 carries nothing.  With HANDOFF the layer only merges its last block into m[] and returns;
+//   the next layer names it as PEND (a Carry) and runs its quads in block 0: before k-step NB_prev - 1 where that block is an
+//   operand (Carry::DEP: quad g at k-step g (NB_prev - 1) / 4), over the whole block otherwise.  Same arithmetic, same order per
+//   element; only its place in the instruction stream moves.  Without HANDOFF the last epilogue runs exposed behind the block loop.
+//   PRE_IN / PRE_OUT: the weight pipeline across the boundary.  A layer alone starts with a chunk rendezvous and the LDS latency of its first
+//   PFX fragment pairs in front of its first MFMA, with all eight waves in step.  With PRE_OUT the last PFX k-steps of a layer request the
+//   NEXT layer's first pairs (its chunk follows in the ring: same rendezvous, same order, PFX k-steps earlier); that layer (PRE_IN) finds
+//   them in bd.fT / bd.fL and starts on an MFMA.
+template <int NB, int KS0, int KS1, bool SIN, bool RAWL = false, int PHASE = 0, bool OPQ = false, class PEND = NoCarry, bool HANDOFF = false, bool PRE_IN = false,
+          bool PRE_OUT = false>
+__device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, uint32_t stream_bytes, lds_char* lds, lds_cfloat* tab0, lds_cfloat* tab_l,
+                                             const Frag8* in0, const Frag8* in1, Frag8* out, f32x16* raw, Boundary& bd, const CarryDst& pd,
+                                             int wave, int lane, const float* rawx = nullptr
+#ifdef SNERF_STAMP
+                                             , bool stamp_on = false, int stamp_slot = 0
+#endif
+) {
     constexpr int KS = KS0 + KS1, NP = NB * KS;
+    constexpr int NBP = PEND::NB;
+    static_assert(!PRE_OUT || (NP >= PFX && NP % PFX == 0), "the successor expects its pair j in fragment slot j");
+    static_assert(!PRE_IN || NP >= PFX, "the predecessor requested PFX pairs of this layer");
+    int (&m)[16] = bd.m;
+    i32x4 (&fT)[PFX] = bd.fT;
+    i32x4 (&fL)[PFX] = bd.fL;
+    static_assert(!PEND::on || carry_fits(NBP, PEND::DEP), "a carried block that is the operand of k-step 0 has no k-step to run in");
+    static_assert(!(PEND::on && PEND::DEP) || NBP <= KS0, "Carry::DEP: the producer's output is in0");
     typedef volatile const __attribute__((address_space(3))) f32x4 lds_vf32x4;
     f32x4 rq[4][3];        // raw-coordinate weights of the previous block's quads (RAWL), requested with the table entries
     const int h = lane >> 5;
@@ -186,12 +290,20 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
     // offset) hipcc gave every table row of THAT variant its own address register and hoisted all of them out of the persistent tile loop - ~25 registers
     // alive across the whole chain, 72-104 bytes of scratch (tests/test_isa_guards.py); the asm makes the base un-hoistable, so it lives for one layer.
     // The other variants compile without scratch as they are and keep their addressing (with the opaque bases the full program spills 116 bytes).
+    // With a carried block the one base is the PRODUCER's table (it lies below this layer's: both stay immediate offsets).
+    lds_cfloat* ptab_l = tab0 + PEND::TAB;
+    lds_cfloat* base_h = (PEND::on ? ptab_l : tab_l) + 32 * h;
+    if constexpr (OPQ) asm volatile("" : "+v"(base_h));
     lds_cfloat* raw_l = tab_l + 2 * 32 * NB;
-    lds_cfloat* tab_h = tab_l + 32 * h;
     lds_cfloat* raw_h = raw_l + 48 * h;
-    if constexpr (OPQ) asm volatile("" : "+v"(tab_h), "+v"(raw_h));
+    lds_cfloat* praw_l = ptab_l + 2 * 32 * NBP;
+    lds_cfloat* praw_h = praw_l + 48 * h;
+    if constexpr (OPQ) asm volatile("" : "+v"(raw_h));
+    if constexpr (OPQ && PEND::RAWL) asm volatile("" : "+v"(praw_h));
+    lds_cfloat* tab_h = base_h + (tab_l - (PEND::on ? ptab_l : tab_l));
+    lds_cfloat* ptab_h = base_h;
     auto tabq = [&](int b_, int g_) { return OPQ ? load_tab_quad_h(tab_h, b_, g_) : load_tab_quad(tab_l, b_, h, g_); };
-    i32x4 fT[PFX], fL[PFX];
+    auto ptabq = [&](int g_) { return OPQ ? load_tab_quad_h(ptab_h, NBP - 1, g_) : load_tab_quad(ptab_l, NBP - 1, h, g_); };
 #if defined(SNERF_ABLATE) && (ABL & 2)     // timing-only: weight fragments stay in registers, no LDS reads
     constexpr bool ABL2_ = true;
 #pragma unroll
@@ -213,17 +325,34 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
             asm volatile("" : "+v"(fT[SLOT]), "+v"(fL[SLOT]));                                         \
         }                                                                                              \
     } while (0)
+    // pair J (< PFX) of the NEXT layer, which starts on the next chunk: the weight pipeline runs on across the boundary, so the chunk rendezvous
+    // and the LDS latency of a layer's first fragments hide behind the last k-steps of the layer before (PRE_OUT there, PRE_IN here)
+#define REQUEST_NEXT(J, SLOT)                                                                          \
+    do {                                                                                               \
+        if ((J) == 0) {                                                                                \
+            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                                \
+            rg.cur = ring2_next(rg.cur);                                                               \
+        }                                                                                              \
+        lds_char* ap_ = lds + rg.cur + (J) * kPairBytes + lane * 16;                                   \
+        if (!ABL2_) {                                                                                  \
+            fT[SLOT] = *(lds_ci32x4*)ap_;                                                              \
+            fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                               \
+        } else {                                                                                       \
+            asm volatile("" : "+v"(fT[SLOT]), "+v"(fL[SLOT]));                                         \
+        }                                                                                              \
+    } while (0)
+    if constexpr (!PRE_IN) {
 #pragma unroll
-    for (int q = 0; q < PFX; ++q) {
-        if (q < NP) REQUEST(q, q);
+        for (int q = 0; q < PFX; ++q) {
+            if (q < NP) REQUEST(q, q);
+        }
     }
     // Software pipeline: when block b starts, the finished accumulators of block b-1 are merged into m[i] = (M << 8) + X
     // (16 registers instead of 32: no second accumulator set), and their epilogue - a quad of elements per slot - runs
     // inside block b's k-steps (quad g at k-step g KS / 4, its table entries requested at the top of that step).  Each
     // wave's stream is then a uniform mix of MFMA and VALU work, so it does not matter that the two waves of a SIMD run
-    // in step: whichever has an MFMA ready feeds the pipe.
+    // in step: whichever has an MFMA ready feeds the pipe.  Block 0 does the same for the block the previous layer handed over.
     Acc8 acc;
-    int m[16];
     TabQ tq[4];        // table entries of the previous block's quads: requested one k-step before their slice runs
     auto load_rq = [&](int g, int b_of) {
         if constexpr (RAWL) {
@@ -231,33 +360,29 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
             rq[g][0] = tp[0]; rq[g][1] = tp[1]; rq[g][2] = tp[2];
         }
     };
-    auto quad = [&](int g, int b_of, const TabQ& t) {       // epilogue of elements 4g .. 4g+3 of block b_of from m[]
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf((float)m[4 * g + j], t.sc[j], t.bi[j]);
-        if constexpr (RAWL) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                v[j] = __builtin_fmaf(rq[g][0][j], rawx[0], __builtin_fmaf(rq[g][1][j], rawx[1], __builtin_fmaf(rq[g][2][j], rawx[2], v[j])));
-        }
-        if (SIN) {
-            int hi, lo;
-            digits4(sin2pi(v[0]), sin2pi(v[1]), sin2pi(v[2]), sin2pi(v[3]), hi, lo);
-            asm volatile("" : "+v"(hi), "+v"(lo));       // the digits exist HERE (nothing may sink the epilogue towards their first use)
-            out[b_of].hi[g] = hi;
-            out[b_of].lo[g] = lo;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) (*raw)[4 * g + j] = v[j];
+    auto load_prq = [&](int g) {
+        if constexpr (PEND::RAWL) {
+            lds_vf32x4* tp = OPQ ? (lds_vf32x4*)(praw_h + ((NBP - 1) * 8 + g) * 12) : (lds_vf32x4*)(praw_l + (((NBP - 1) * 2 + h) * 4 + g) * 12);
+            rq[g][0] = tp[0]; rq[g][1] = tp[1]; rq[g][2] = tp[2];
         }
     };
+    auto quad = [&](int g, int b_of, const TabQ& t) { epi_quad<SIN, RAWL>(m, g, t, rq[g], rawx, out + b_of, raw); };
+    auto pquad = [&](int g, const TabQ& t) { epi_quad<PEND::SIN, PEND::RAWL>(m, g, t, rq[g], pd.rawx, pd.out + (NBP - 1), pd.raw); };
+    // k-step of a block in which quad g of the block before runs; the carried block where it is an operand: before k-step NBP - 1
+    auto slot = [](int g, bool carried) constexpr { return carried && PEND::DEP ? (g * (NBP - 1)) / 4 : (g * KS) / 4; };
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        if (b > 0) {
-            tq[0] = tabq(b - 1, 0);
-            load_rq(0, b - 1);
+        const bool carried = b == 0;
+        if (b > 0 || PEND::on) {
+            if (b > 0) {
+                tq[0] = tabq(b - 1, 0);
+                load_rq(0, b - 1);
 #pragma unroll
-            for (int i = 0; i < 16; ++i) m[i] = (int)(((uint32_t)acc.M[i] << 8) + (uint32_t)acc.X[i]);
+                for (int i = 0; i < 16; ++i) m[i] = (int)(((uint32_t)acc.M[i] << 8) + (uint32_t)acc.X[i]);
+            } else {
+                tq[0] = ptabq(0);
+                load_prq(0);
+            }
             asm volatile("" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -272,18 +397,25 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
             if (((s + PHASE) & 1) == 0) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3);
 #endif
             if (q + PFX < NP) REQUEST(q + PFX, q % PFX);
-            if (b > 0) {
+            else if constexpr (PRE_OUT) REQUEST_NEXT(q + PFX - NP, q % PFX);
+            if (b > 0 || PEND::on) {
 #pragma unroll
                 for (int g = 1; g < 4; ++g) {
-                    const int sg = (g * KS) / 4, lg = sg > 0 ? sg - 1 : 0;
-                    if (lg == s) { tq[g] = tabq(b - 1, g); load_rq(g, b - 1); }
+                    const int sg = slot(g, carried), lg = sg > 0 ? sg - 1 : 0;
+                    if (lg == s) {
+                        if (b > 0) { tq[g] = tabq(b - 1, g); load_rq(g, b - 1); }
+                        else { tq[g] = ptabq(g); load_prq(g); }
+                    }
                 }
             }
             mfma_i8x3(aT, aL, s < KS0 ? in0[s] : in1[s - KS0], acc);
-            if (b > 0) {
+            if (b > 0 || PEND::on) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    if ((g * KS) / 4 == s) quad(g, b - 1, tq[g]);
+                    if (slot(g, carried) == s) {
+                        if (b > 0) quad(g, b - 1, tq[g]);
+                        else pquad(g, tq[g]);
+                    }
             }
             asm volatile("" ::: "memory");          // table loads stay in their k-step (the optimiser would gather them up front)
 #ifdef SNERF_X2_GROUPS
@@ -300,20 +432,29 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
             __builtin_amdgcn_sched_barrier(0);      // ... and so do requests, MFMAs and epilogue slices (register pressure)
         }
     }
-    // the last block of the layer: nothing to hide its epilogue behind but the partner wave
+#ifdef SNERF_STAMP
+    stamp(wave, lane, stamp_slot, stamp_on);        // end of the block loop: what follows until the layer's own stamp is the boundary stretch
+#endif
+    // the last block of the layer: handed to the next layer, or (nothing to hide its epilogue behind but the partner wave) finished here
 #pragma unroll
     for (int i = 0; i < 16; ++i) m[i] = (int)(((uint32_t)acc.M[i] << 8) + (uint32_t)acc.X[i]);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        asm volatile("" ::: "memory");
-        const TabQ t = tabq(NB - 1, g);
-        load_rq(g, NB - 1);
-        quad(g, NB - 1, t);
+    if constexpr (HANDOFF) {
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            asm volatile("" ::: "memory");
+            const TabQ t = tabq(NB - 1, g);
+            load_rq(g, NB - 1);
+            quad(g, NB - 1, t);
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
-    rg.cur = ring2_next(rg.cur);          // the next layer starts on the next chunk
+    if constexpr (!PRE_OUT) rg.cur = ring2_next(rg.cur);          // the next layer starts on the next chunk
 #undef REQUEST
+#undef REQUEST_NEXT
 }
 
 template <int W, int VARIANT, int PHASE>
@@ -395,27 +536,50 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
         constexpr int KW = W / 32, KW2 = W2 / 32;
         Frag8 hA[KW], hB[KW];
         f32x16 raw;
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                                       \
-    run_layer8x2<NBv, K0, K1, SINv, false, PHASE, VARIANT == 3>(rg, A.stream, A.stream_bytes, lds, tab_lds + prog_table_start(PROG_FIELD, W, C_MAX, L), \
-                                                  IN0, IN1, OUT, RAW, wave, lane)
-#define LAYER_RAW(L, NBv, K0, K1, IN0, IN1, OUT, RX)                                                                          \
-    run_layer8x2<NBv, K0, K1, true, true, PHASE, VARIANT == 3>(rg, A.stream, A.stream_bytes, lds, tab_lds + prog_table_start(PROG_FIELD, W, C_MAX, L), \
-                                                 IN0, IN1, OUT, nullptr, wave, lane, RX)
+        Boundary bd;      // a layer's last block and the next layer's first weight fragments on their way across the boundary (run_layer8x2)
+        // Layer boundaries: field_carries(W, VARIANT, L) = layer L hands its last block to its successor in the chain (one flag per boundary,
+        // read by both sides: HAND(L) in the producer, PEND_T(L, ...) in the receiver).
+#define TAB(L) prog_table_start(PROG_FIELD, W, C_MAX, L)
+#define NBLK(L) (prog_layer(PROG_FIELD, W, C_MAX, L, FMT_I8).n_out / 32)
+#define HAND(L) field_carries(W, VARIANT, C_MAX, L)
+        // the weight pipeline runs across every boundary of the chain where the pair counts allow it (all of them from W = 128 on)
+#ifdef SNERF_X2_NO_XPF
+        constexpr bool XPF = false;          // A/B: every layer requests its own first fragments
+#else
+        constexpr bool XPF = KW2 >= PFX && KW2 % PFX == 0;
+#endif
+#define PRE_I(L) (XPF && L != F_FC1)
+#define PRE_O(L) (XPF && L != field_last(VARIANT))
+#define PEND_T(P, PSIN, PRAWL) std::conditional_t<HAND(P), Carry<TAB(P), NBLK(P), PSIN, PRAWL, field_feeds_next(P)>, NoCarry>
+#ifdef SNERF_STAMP
+#define STAMP_ARGS(L) , stamp_on, 24 + L
+#else
+#define STAMP_ARGS(L)
+#endif
+#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW, PEND, PDST, HANDv)                                                     \
+    run_layer8x2<NBv, K0, K1, SINv, false, PHASE, VARIANT == 3, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),  \
+                                                  IN0, IN1, OUT, RAW, bd, PDST, wave, lane, nullptr STAMP_ARGS(L))
+#define LAYER_RAW(L, NBv, K0, K1, IN0, IN1, OUT, RX, PEND, PDST, HANDv)                                                        \
+    run_layer8x2<NBv, K0, K1, true, true, PHASE, VARIANT == 3, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),   \
+                                                 IN0, IN1, OUT, nullptr, bd, PDST, wave, lane, RX STAMP_ARGS(L))
         const float rx_p[3] = {x0, x1, x2}, rx_s[3] = {s0, s1, s2};      // raw coordinates: fp32, no digit range
+        const CarryDst none{nullptr, nullptr, nullptr};
+        static_assert(NBLK(F_FC1) == KW && NBLK(F_FC9) == KW2 && NBLK(F_HEAD) == 1 && NBLK(F_S4) == 1 && NBLK(F_A1) == KW, "block counts below");
         // trunk (G_NeRF.py:80-91)
-        LAYER_RAW(F_FC1, W / 32, PEPOS_KS8, 0, pe, nullptr, hA, rx_p); STAMP(2);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr); STAMP(3);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr); STAMP(4);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr); STAMP(5);
-        LAYER_RAW(F_FC5, W / 32, KW, PEPOS_KS8, hB, pe, hA, rx_p); STAMP(6);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr); STAMP(7);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr); STAMP(8);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr); STAMP(9);
+        LAYER_RAW(F_FC1, W / 32, PEPOS_KS8, 0, pe, nullptr, hA, rx_p, NoCarry, none, HAND(F_FC1)); STAMP(2);
+        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC1, true, true), (CarryDst{hA, nullptr, rx_p}), HAND(F_FC2)); STAMP(3);
+        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC2, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC3)); STAMP(4);
+        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC3, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_FC4)); STAMP(5);
+        LAYER_RAW(F_FC5, W / 32, KW, PEPOS_KS8, hB, pe, hA, rx_p, PEND_T(F_FC4, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC5)); STAMP(6);
+        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC5, true, true), (CarryDst{hA, nullptr, rx_p}), HAND(F_FC6)); STAMP(7);
+        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC6, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC7)); STAMP(8);
+        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC7, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_FC8)); STAMP(9);
         Frag8 x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr); STAMP(10);
-        // sigma / colour head (G_NeRF.py:93-98): regs 0..2 colour, 3 density (lane-half 0)
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw); STAMP(11);
-        const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
+        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr, PEND_T(F_FC8, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC9)); STAMP(10);
+        // sigma / colour head (G_NeRF.py:93-98): regs 0..2 colour, 3 density (lane-half 0).  With the solar branch behind it the head's
+        // block finishes inside fc_solar_1 (which does not read it: spread over the whole block), so `raw` is read behind that layer.
+        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw, PEND_T(F_FC9, true, false), (CarryDst{x1f, nullptr, nullptr}), HAND(F_HEAD)); STAMP(11);
+        float col_r, col_g, col_b, rho_raw;
         float sv_raw = 0.f;
         float adj[3 * C_MAX];
 #pragma unroll
@@ -425,23 +589,35 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
             Frag8 ps[PESUN_KS8];
             make_pe_sun8(s0, s1, s2, h, ps);
             Frag8 sA[KW2], sB[KW2];
-            LAYER_RAW(F_S1, W2 / 32, KW2, PESUN_KS8, x1f, ps, sA, rx_s); STAMP(12);
-            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr); STAMP(13);
-            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr); STAMP(14);
-            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw); STAMP(15);
-            sv_raw = raw[0];
+            LAYER_RAW(F_S1, W2 / 32, KW2, PESUN_KS8, x1f, ps, sA, rx_s, PEND_T(F_HEAD, false, false), (CarryDst{nullptr, &raw, nullptr}), HAND(F_S1)); STAMP(12);
+            col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
+            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr, PEND_T(F_S1, true, true), (CarryDst{sA, nullptr, rx_s}), HAND(F_S2)); STAMP(13);
+            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr, PEND_T(F_S2, true, false), (CarryDst{sB, nullptr, nullptr}), HAND(F_S3)); STAMP(14);
+            // fc_solar_4's one block finishes inside adjust_layer_1 (variant 0), which reads x1f, not the solar branch
+            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw, PEND_T(F_S3, true, false), (CarryDst{sA, nullptr, nullptr}), HAND(F_S4)); STAMP(15);
+            if constexpr (VARIANT == 1) sv_raw = raw[0];
+        } else {
+            col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         }
         if constexpr (VARIANT == 0) {
             // seasonal colour-adjust branch (T_NeRF_net_v2.py:83-87)
-            LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr); STAMP(16);
-            LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr); STAMP(17);
-            LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr); STAMP(18);
-            LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw); STAMP(19);
+            LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr, PEND_T(F_S4, false, false), (CarryDst{nullptr, &raw, nullptr}), HAND(F_A1)); STAMP(16);
+            sv_raw = raw[0];
+            LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_A1, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_A2)); STAMP(17);
+            LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_A2, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_A3)); STAMP(18);
+            LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw, PEND_T(F_A3, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_AC)); STAMP(19);
 #pragma unroll
             for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
         }
 #undef LAYER
 #undef LAYER_RAW
+#undef PEND_T
+#undef HAND
+#undef PRE_I
+#undef PRE_O
+#undef STAMP_ARGS
+#undef TAB
+#undef NBLK
         if constexpr (VARIANT == 3) {
             RAYSUM_PASS_END(rs, A, tile, pass, passes, NW2, wave, wave, NW2, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
         } else {

@@ -82,6 +82,10 @@ def main():
             st = [buf[w * 64 + i] for i in range(21)]
             print(f"  wave {w}: tile {st[20] - st[0]} cycles; " + " ".join(f"{names[i]} {st[i] - st[i - 1]}" for i in range(1, 21)))
             print(f"          inside ring steps over the whole launch (6 tiles): vmcnt wait {buf[w * 64 + 62]}, barrier wait {buf[w * 64 + 63]}")
+            # slot 24 + L: end of layer L's block loop.  What follows until the layer's own stamp is the boundary stretch: the merge of the last block and
+            # - where the layer does not hand that block to the next one - its exposed epilogue (field layers in program order = names[2:20])
+            tail = [st[2 + l] - buf[w * 64 + 24 + l] for l in range(18)]
+            print(f"          boundary stretch (block loop end -> layer end): " + " ".join(f"{names[2 + l]} {tail[l]}" for l in range(18)) + f"; sum {sum(tail)}")
     print(f"{a.tag or os.environ.get('SNERF_LIB', 'default'):40s} {a.precision} W={Wd}: mean {tot / 3:.4f} ms  best {best:.4f} ms{chk}", flush=True)
 
 
