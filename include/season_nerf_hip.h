@@ -164,7 +164,7 @@ typedef struct snerf_composite_out {
     float* d_shadow;     /* [R] sum_s PS*Solar_Vis */
     float* d_acc;        /* [R] sum_s PS */
     float* d_surf_loc;   /* [R,3] sum PS*pts/(sum PS + 1e-8) */
-    float* d_surf_dist;  /* [R] sum cumsum(delta)*PS / sum PS */
+    float* d_surf_dist;  /* [R] sum cumsum(delta)*PS / sum PS, delta the ray's own segment length (flags bit1 does not shorten the distance) */
 } snerf_composite_out;
 
 int snerf_composite_rays(int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals,
@@ -237,7 +237,9 @@ int snerf_trainer_bind(snerf_trainer* t, float* d_params, float* d_grads, float*
                        void* d_workspace, size_t workspace_bytes, int64_t n_rays, int64_t n_solar_rays, int n_samples);
 /* the sizes the trainer is bound to (any pointer may be NULL); SNERF_E_STATE before snerf_trainer_bind */
 int snerf_trainer_bound_sizes(const snerf_trainer* t, int64_t* n_rays, int64_t* n_solar_rays, int* n_samples);
-/* image-ray pass: T_NeRF.forward + compositing.  train_bn: 1 = batch statistics + EMA update, 0 = running statistics. */
+/* image-ray pass: T_NeRF.forward + compositing.  train_bn: 1 = batch statistics + EMA update, 0 = running statistics.
+ * flags: bit0 = classic solar as in snerf_composite_rays.  bit1 (zero segment length outside the cube) is refused with SNERF_E_INVALID:
+ * the compositing backward differentiates the plain segment length, so a forward with bit1 would get the gradients of another function. */
 int snerf_trainer_forward_image(snerf_trainer* t, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot,
                                 const float* d_tvals, const float* d_sun, const float* d_time, int train_bn, int flags,
                                 const snerf_composite_out* out, float* d_sky, float* d_classes,
@@ -307,7 +309,8 @@ int snerf_linear_dgrad(int64_t n_points, int n_in, int n_out, const float* d_gra
 int snerf_linear_wgrad(int64_t n_points, int n_in, int n_out, const float* d_grad_out, int64_t ld_go, const float* d_in,
                        int64_t ld_in, float alpha, float* d_grad_weight, int precision, const float* d_act_tab, int act_cols,
                        void* stream);
-/* test introspection: synchronous copy of an internal buffer ("d_rho", "d_col", "d_head", "d_sky", ...) to the host */
+/* test introspection: synchronous copy of an internal buffer ("d_rho", "d_col", "d_head", "d_sky", "d_sv_raw", "rho", "col", "sv", "sky", ...)
+ * to the host.  "d_sv_raw": dL/dSolar_Vis of the classic solar model, as the pre-sigmoid gradient the network backward consumed. */
 int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out, int64_t n_floats);
 /* torch.optim.Adam semantics (no weight decay) over the whole parameter arena in one launch; step counts from 1. */
 int snerf_trainer_adam_step(snerf_trainer* t, float lr, float beta1, float beta2, float eps, int step, void* stream);

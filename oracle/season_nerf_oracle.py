@@ -389,9 +389,11 @@ def outside_cube(pts: Tensor) -> Tensor:
 
 
 def get_PV(rho: Tensor, delta: Tensor) -> Tensor:
-    """Eval_Tools_2.get_PV, Eval_Tools_2.py:13-16: exclusive-prefix transmittance exp(-sum_{j<s} rho_j delta_j)."""
+    """Eval_Tools_2.get_PV, Eval_Tools_2.py:13-16: exclusive-prefix transmittance exp(-sum_{j<s} rho_j delta_j), formed as the
+    reference forms it - the cumulative sum of [0, y_0, .., y_{S-1}] without its last entry - so that PV_s never contains y_s
+    (cumsum(y) - y would recover the prefix from a sum that a large y_s dominates)."""
     y = rho * delta
-    c = torch.cumsum(y, 1) - y
+    c = torch.cumsum(torch.cat([torch.zeros_like(y[:, :1]), y], 1), 1)[:, :-1]
     return torch.exp(-c)
 
 
@@ -465,6 +467,62 @@ def surface_depth(PS, pts, deltas):
     loc = (PS * pts).sum(1) / (PS.sum(1) + 1e-8)
     dist = (torch.cumsum(deltas, 1) * PS).sum(1) / PS.sum(1)
     return loc, dist
+
+
+def composite_arrays(rho, delta, col, solar_vis, sky, pts=None, ray_delta=None, classic_solar=False, rho_prior=None, trust=1.0):
+    """The compositing of `eval_rays` on plain per-ray arrays (no network), in the dtype of its arguments: the yardstick of the
+    stand-alone compositing kernels.  rho, delta, solar_vis [R,S]; col [R,S,3]; sky [R,3] (the ray's sky colour; the reference
+    carries S copies of it and takes their mean, Eval_Tools_2.py:215); pts [R,S,3] (optional: surface location);
+    ray_delta [R] (optional: the ray's own segment length for the surface distance, mg_run_NeRF.py:188-189; default `delta`);
+    rho_prior [R,S] + trust: the merged composites of Eval_Tools_2.py:232-241 (density rho*trust + rho_prior*(1-trust), the solar
+    term of the default model from the UN-merged PS).
+    -> PV, PE, PS [R,S]; Albedo_Color, Rendered_Col [R,3]; Shadow = sum PS*Solar_Vis, Acc = sum PS [R]; surf_loc [R,3],
+    surf_dist [R]; with a prior also PS_Merged, Albedo_Color_Merged, Rendered_Col_Merged."""
+    R, S = rho.shape
+    r3, d3, sv3d = rho.unsqueeze(2), delta.unsqueeze(2), solar_vis.unsqueeze(2)
+    sky3 = sky.unsqueeze(1).expand(R, S, 3)
+    o = composite(r3, d3, col, sv3d, sky3, classic_solar)
+    PS = o["PS"]
+    out = {"PV": o["PV"][..., 0], "PE": o["PE"][..., 0], "PS": PS[..., 0], "Albedo_Color": o["Albedo_Color"],
+           "Rendered_Col": o["Rendered_Col"], "Shadow": (PS * sv3d).sum(1)[:, 0], "Acc": PS.sum(1)[:, 0]}
+    dd = d3 if ray_delta is None else ray_delta.reshape(R, 1, 1).expand(R, S, 1)
+    if pts is not None:
+        loc, dist = surface_depth(PS, pts, dd)
+        out["surf_loc"], out["surf_dist"] = loc, dist[:, 0]
+    else:
+        out["surf_dist"] = ((torch.cumsum(dd, 1) * PS).sum(1) / PS.sum(1))[:, 0]
+    if rho_prior is not None:
+        rm = r3 * trust + rho_prior.unsqueeze(2) * (1 - trust)
+        PSm = get_PV(rm, d3) * (1 - torch.exp(-rm * d3))
+        alb_m = (PSm * col).sum(1)
+        if classic_solar:
+            rgb_m = (PSm * col * (sv3d + (1 - sv3d) * sky3)).sum(1)
+        else:
+            f = torch.sigmoid(((sv3d.detach() * PS).sum(1) - 0.2) * 30)
+            rgb_m = alb_m * (f + (1 - f) * sky3.mean(1))
+        out.update({"PS_Merged": PSm[..., 0], "Albedo_Color_Merged": alb_m, "Rendered_Col_Merged": rgb_m})
+    return out
+
+
+def sweep_arrays(rho, delta, col_raw, adjust, solar_vis, sky, class_vecs):
+    """The seasonal sweep (get_imgs_from_Img_Dict / _t_step, mg_Img_Eval.py:123-228) on per-ray arrays, in the dtype of its
+    arguments: rho, delta, solar_vis [R,S]; col_raw [R,S,3]; adjust [R,S,C,3]; sky [3]; class_vecs [T,C].
+    -> season [T,R,3] = sum_s PS*sigmoid(col_raw + class_t @ adjust); shaded = season * shadow_adjust; classic [T,R,3] = the same
+    sum with every sample shaded by SV + (1-SV)*sky (use_classic_shadows, :165-170); base [R,3] = sum_s PS*sigmoid(col_raw);
+    raw_shadow [R] = sum_s PS*solar_vis; shadow_adjust [R,3] = m + (1-m)*sky with m = sigmoid(30 (raw_shadow - 0.2))."""
+    r3, d3 = rho.unsqueeze(2), delta.unsqueeze(2)
+    PS = get_PV(r3, d3) * (1 - torch.exp(-r3 * d3))                               # [R,S,1]
+    sv = solar_vis.unsqueeze(2)
+    raw_shadow = (PS * sv).sum(1)[:, 0]
+    m = torch.sigmoid((raw_shadow - 0.2) * 30).unsqueeze(1)
+    shadow_adjust = m + (1 - m) * sky.reshape(1, 3)
+    base = (PS * torch.sigmoid(col_raw)).sum(1)
+    mix = torch.einsum("tc,rsck->trsk", class_vecs, adjust)
+    colt = torch.sigmoid(col_raw.unsqueeze(0) + mix)                              # [T,R,S,3]
+    season = (PS.unsqueeze(0) * colt).sum(2)
+    classic = (PS.unsqueeze(0) * colt * (sv + (1 - sv) * sky.reshape(1, 1, 3)).unsqueeze(0)).sum(2)
+    return {"season": season, "shaded": season * shadow_adjust.unsqueeze(0), "classic": classic, "base": base,
+            "raw_shadow": raw_shadow, "shadow_adjust": shadow_adjust}
 
 
 def dense_from_dsm(dsm: np.ndarray, n: int) -> Tensor:

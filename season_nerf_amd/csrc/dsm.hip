@@ -106,7 +106,8 @@ __global__ __launch_bounds__(256) void transmittance_kernel(int64_t n_rays, int 
             const float up = __shfl_up(incl, o, 64);
             if (lane >= o) incl += up;
         }
-        if (in) pv[r * S + s] = expf(-(carry + incl - y));
+        const float below = __shfl_up(incl, 1, 64);       // exclusive prefix = the inclusive value of the lane below, never incl - y (kernels.hip, wave_excl_of)
+        if (in) pv[r * S + s] = expf(-(carry + (lane == 0 ? 0.f : below)));
         carry += __shfl(incl, 63, 64);
     }
 }

@@ -260,6 +260,13 @@ __device__ __forceinline__ float wave_incl_scan(float v, int lane) {
     }
     return v;
 }
+// The exclusive prefix of the same scan: the inclusive value of the lane below, 0 in lane 0.  NOT incl - v: that recovers the prefix from a
+// sum which an opaque sample's own v = rho * delta dominates, leaving it with half an ulp of v as its absolute error - and the sample's
+// transmittance exp(-prefix), which carries the ray, with that as its relative error ("Transmittance by a shifted scan").
+__device__ __forceinline__ float wave_excl_of(float incl, int lane) {
+    const float below = __shfl_up(incl, 1, 64);
+    return lane == 0 ? 0.f : below;
+}
 
 __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
     const int lane = threadIdx.x & 63;
@@ -292,7 +299,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
         const float rho = in ? A.rho[idx] : 0.f;
         const float y = in ? rho * delta : 0.f;
         const float incl = wave_incl_scan(y, lane);
-        const float excl = carry + (incl - y);
+        const float excl = carry + wave_excl_of(incl, lane);
         carry += __shfl(incl, 63, 64);
         const float pv = expf(-excl);
         const float pe = 1.f - expf(-y);
@@ -320,7 +327,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
             const float rm = in ? (rho * tr + A.rho_prior[idx] * (1.f - tr)) : 0.f;
             const float ym = rm * delta;
             const float incl_m = wave_incl_scan(ym, lane);
-            const float excl_m = carry_m + (incl_m - ym);
+            const float excl_m = carry_m + wave_excl_of(incl_m, lane);
             carry_m += __shfl(incl_m, 63, 64);
             const float psm = in ? expf(-excl_m) * (1.f - expf(-ym)) : 0.f;
             if (classic) {
@@ -457,7 +464,8 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs A) {
                 const float t = __shfl_up(incl, o, 32);
                 if (sl >= o) incl += t;
             }
-            const float excl = carry + (incl - y);
+            const float below = __shfl_up(incl, 1, 32);   // exclusive prefix = the inclusive value of the lane below (see wave_excl_of)
+            const float excl = carry + (sl == 0 ? 0.f : below);
             carry += __shfl(incl, 31, 32);
             const float ps = in ? expf(-excl) * (1.f - expf(-y)) : 0.f;
             const float sv = in ? cur.sv : 0.f;

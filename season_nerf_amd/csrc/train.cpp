@@ -592,6 +592,8 @@ int snerf_trainer_forward_image(snerf_trainer* t, int64_t n_rays, int n_samples,
                                 void* stream) {
     RC(check_bound(t, n_rays, n_samples, false));
     if (!d_top || !d_bot || !d_tvals || !d_sun || !d_time || !out) return snerf_set_error(SNERF_E_INVALID, "snerf_trainer_forward_image: bad argument");
+    // the compositing backward differentiates the plain segment length: with bit 1 the gradients would be those of another function
+    if (flags & 2) return snerf_set_error(SNERF_E_INVALID, "snerf_trainer_forward_image: flags bit 1 (zero segment length outside the cube) has no backward");
     CtxGuard ctx(t);
     t->img_flags = flags;
     hipStream_t st = (hipStream_t)stream;
@@ -805,7 +807,7 @@ int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out
     const std::string k = name;
     const float* src = k == "d_rho" ? t->d_rho : k == "d_col" ? t->d_col : k == "d_head" ? t->d_head : k == "d_adj" ? t->d_adj
                      : k == "d_sky" ? t->d_sky : k == "d_cls" ? t->d_cls : k == "rho" ? t->img.rho : k == "col" ? t->img.col
-                     : k == "sv" ? t->img.sv : k == "sky" ? t->img.sky : k == "head" ? t->img.head.p : nullptr;
+                     : k == "sv" ? t->img.sv : k == "sky" ? t->img.sky : k == "head" ? t->img.head.p : k == "d_sv_raw" ? t->d_sv_raw : nullptr;
     if (!src) return snerf_set_error(SNERF_E_INVALID, "snerf_trainer_debug_read: unknown buffer " + k);
     HIPCK(hipDeviceSynchronize());
     HIPCK(hipMemcpy(host_out, src, n_floats * sizeof(float), hipMemcpyDeviceToHost));

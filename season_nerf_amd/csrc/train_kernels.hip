@@ -866,6 +866,25 @@ __device__ __forceinline__ float wscan_incl(float v, int lane) {
     }
     return v;
 }
+// exclusive prefix of wscan_incl: the inclusive value of the lane below, 0 in lane 0 - never incl - v (csrc/kernels.hip, wave_excl_of)
+__device__ __forceinline__ float wscan_excl_of(float incl, int lane) {
+    const float below = __shfl_up(incl, 1, 64);
+    return lane == 0 ? 0.f : below;
+}
+// inclusive SUFFIX scan v_lane + .. + v_63, and from it what lies strictly behind a lane (0 in lane 63).  The backward needs sum_{k>s} dPV_k PV_k, which
+// behind an opaque sample is tiny against the chunk's total: tot - inclusive_prefix would leave it with half an ulp of the TOTAL as its absolute error.
+__device__ __forceinline__ float wscan_incl_suffix(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_down(v, o, 64);
+        if (lane + o < 64) v += t;
+    }
+    return v;
+}
+__device__ __forceinline__ float wscan_behind_of(float incl_suffix, int lane) {
+    const float above = __shfl_down(incl_suffix, 1, 64);
+    return lane == 63 ? 0.f : above;
+}
 __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -885,7 +904,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         const float rho = A.rho[idx];
         const float y = in ? rho * delta : 0.f;
         const float incl = wscan_incl(y, lane);
-        const float pv = expf(-(carry + incl - y));
+        const float pv = expf(-(carry + wscan_excl_of(incl, lane)));
         carry += __shfl(incl, 63, 64);
         const float ps = in ? pv * (1.f - expf(-y)) : 0.f;
 #pragma unroll
@@ -894,7 +913,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         if (prior) {
             const float ym = in ? (rho * tr + A.rho_prior[idx] * (1.f - tr)) * delta : 0.f;
             const float inclm = wscan_incl(ym, lane);
-            const float pvm = expf(-(carry_m + inclm - ym));
+            const float pvm = expf(-(carry_m + wscan_excl_of(inclm, lane)));
             carry_m += __shfl(inclm, 63, 64);
             const float psm = in ? pvm * (1.f - expf(-ym)) : 0.f;
 #pragma unroll
@@ -943,7 +962,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         const float rho = A.rho[idx];
         const float y = in ? rho * delta : 0.f;
         const float incl = wscan_incl(y, lane);
-        const float pv = expf(-(pre + incl - y));
+        const float pv = expf(-(pre + wscan_excl_of(incl, lane)));
         const float ey = expf(-y);
         const float pe = 1.f - ey;
         float dps = 0.f;
@@ -960,9 +979,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         const float dpv_pv = in ? dps * pe * pv : 0.f;          // dPV_s * PV_s
         float dpe = in ? dps * pv : 0.f;
         if (in && A.g_pe) dpe += A.g_pe[idx];
-        const float incl2 = wscan_incl(dpv_pv, lane);
-        const float tot = __shfl(incl2, 63, 64);
-        const float later = suffix + (tot - incl2);
+        const float sfx = wscan_incl_suffix(dpv_pv, lane);
+        const float tot = __shfl(sfx, 0, 64);
+        const float later = suffix + wscan_behind_of(sfx, lane);
         float d_rho = (dpe * ey - later) * delta;
         float dc[3];
         const float ps = pv * pe;
@@ -981,7 +1000,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         if (prior) {
             const float ym = in ? (rho * tr + A.rho_prior[idx] * (1.f - tr)) * delta : 0.f;
             const float inclm = wscan_incl(ym, lane);
-            const float pvm = expf(-(pre_m + inclm - ym));
+            const float pvm = expf(-(pre_m + wscan_excl_of(inclm, lane)));
             const float eym = expf(-ym);
             const float pem = 1.f - eym;
             float dpsm = 0.f;
@@ -990,9 +1009,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
                 for (int k = 0; k < 3; ++k) dpsm += (dalbm[k] + grgbm[k] * shade[k]) * A.col[idx * 3 + k];
             }
             const float dpvm_pvm = in ? dpsm * pem * pvm : 0.f;
-            const float incl3 = wscan_incl(dpvm_pvm, lane);
-            const float totm = __shfl(incl3, 63, 64);
-            const float later_m = suffix_m + (totm - incl3);
+            const float sfx_m = wscan_incl_suffix(dpvm_pvm, lane);
+            const float totm = __shfl(sfx_m, 0, 64);
+            const float later_m = suffix_m + wscan_behind_of(sfx_m, lane);
             d_rho += tr * (dpsm * pvm * eym - later_m) * delta;
             const float psm = pvm * pem;
 #pragma unroll

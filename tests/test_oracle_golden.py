@@ -374,3 +374,81 @@ def test_eval_at_the_benchmark_size(golden_dir):
     sel = slice(0, 4096, 4096 // int(g["keep"]))
     for k in ("Rho", "Solar_Vis", "Col", "PS"):
         close(r[k][sel], g["sub_" + k], rtol=5e-5)
+
+
+def D(a):
+    return torch.tensor(np.asarray(a), dtype=torch.float64)
+
+
+def _max_dev(got, ref):
+    return float((got.reshape(-1) - D(ref).reshape(-1)).abs().max())
+
+
+@pytest.mark.parametrize("name", ["eval_W64_R48_S64.npz", "eval_W256_R64_S96.npz"])
+def test_compositing_yardstick_is_the_reference(golden_dir, name):
+    """oracle.composite_arrays - the float64 yardstick of tests/test_gpu_compositing.py - fed the reference's own recorded per-sample fields (fp32 values
+    cast to float64) reproduces the reference's recorded composites.  The recorded values are the reference's fp32, so this is an fp32-accuracy
+    comparison: absolute bounds of twice the largest deviation observed (eval_*: 2.4e-7, on eval_surf_dist of the W = 256 file; classic_: 1.4e-7;
+    prior_ / cprior_ colours 1.3e-7, PS 6.6e-8), rtol = 0.  The supervised outputs are the merged ones at trust 0."""
+    g = load(golden_dir, name)
+    assert (g["eval_Sky_Col"] == g["eval_Sky_Col"][:, :1]).all()            # [R,S,3]: S copies of the ray's sky colour
+    rho, dl, sv = D(g["eval_Rho"])[..., 0], D(g["eval_deltas"])[..., 0], D(g["eval_Solar_Vis"])[..., 0]
+    col, sky, pts = D(g["eval_Col"]), D(g["eval_Sky_Col"])[:, 0], D(g["eval_sample_pts"])
+    o = orc.composite_arrays(rho, dl, col, sv, sky, pts)
+    for k in ("PV", "PS", "PE", "Rendered_Col", "Albedo_Color", "surf_loc", "surf_dist"):
+        dev = _max_dev(o[k], g["eval_" + k])
+        print(f"  {name} eval_{k}: {dev:.2e}")
+        assert dev <= 5e-7, (k, dev)
+    oc = orc.composite_arrays(rho, dl, col, sv, sky, pts, classic_solar=True)
+    dev = _max_dev(oc["Rendered_Col"], g["classic_Rendered_Col"])
+    print(f"  {name} classic_Rendered_Col: {dev:.2e}")
+    assert dev <= 2.8e-7, dev
+    torch.testing.assert_close(oc["PS"], o["PS"], rtol=0, atol=0)
+    if "hm" not in g:
+        return
+    trust = int(g["prior_step"]) / int(g["prior_n_steps"])
+    rp = orc.supervised_sample(g["hm"], T(g["eval_sample_pts"]).reshape(-1, 3), T(g["eval_deltas"]).reshape(-1, 1)).reshape(rho.shape).double()
+    assert 0 < trust < 1 and float(rp.max()) > 100
+    for tag, classic in (("prior_", False), ("cprior_", True)):
+        m = orc.composite_arrays(rho, dl, col, sv, sky, pts, classic_solar=classic, rho_prior=rp, trust=trust)
+        s = orc.composite_arrays(rho, dl, col, sv, sky, pts, classic_solar=classic, rho_prior=rp, trust=0.0)
+        pairs = [("Rendered_Col", m["Rendered_Col"], 2.6e-7), ("Rendered_Col_Merged", m["Rendered_Col_Merged"], 2.6e-7),
+                 ("Albedo_Color", m["Albedo_Color_Merged"], 2.6e-7), ("Rendered_Col_Supervised", s["Rendered_Col_Merged"], 2.6e-7)]
+        if not classic:
+            pairs += [("PS_Merged", m["PS_Merged"], 1.4e-7), ("PS_Supervised", s["PS_Merged"], 1.4e-7)]
+        for k, v, atol in pairs:
+            dev = _max_dev(v, g[tag + k])
+            print(f"  {name} {tag}{k}: {dev:.2e}")
+            assert dev <= atol, (tag + k, dev)
+
+
+def test_transmittance_is_the_shifted_cumulative_sum():
+    """get_PV never lets a sample's own optical depth into its transmittance: behind haze, PV of an opaque sample (y = 1e6) is the haze's alone.  In fp32
+    `cumsum(y) - y` would leave the prefix with half an ulp of 1e6 (0.03) as its absolute error."""
+    y = torch.tensor([[0.25, 0.5, 1.0e6, 0.125]], dtype=torch.float32)
+    pv = orc.get_PV(y, torch.ones_like(y))
+    np.testing.assert_allclose(pv.numpy()[0, :3], np.exp(-np.array([0.0, 0.25, 0.75])), rtol=2e-7)
+    assert float(pv[0, 3]) == 0.0
+    pv3 = orc.get_PV(y.unsqueeze(2), torch.ones(1, 4, 1))
+    assert torch.equal(pv3[..., 0], pv)
+
+
+def test_sweep_yardstick_is_the_reference(golden_dir):
+    """oracle.sweep_arrays on the recorded per-sample dict of a render_by_dir reproduces the reference's recorded float64 images of
+    get_imgs_from_Img_Dict / _t_step (mg_Img_Eval.py:123-228) to float64 rounding (48 samples per ray: 1e-14), and the classic output is its own formula
+    evaluated sample by sample."""
+    g = load(golden_dir, "render_W64_s2.npz")
+    rho, dl, sv = D(g["dir_Rho"])[..., 0], D(g["dir_Deltas"])[..., 0], D(g["dir_Est_Solar_Vis"])[..., 0]
+    cvs = torch.cat([D(g["dir_Output_class0"]).reshape(1, -1), D(g["sweep_classes"])])
+    sky = D(g["dir_Sky_Col0"])
+    o = orc.sweep_arrays(rho, dl, D(g["dir_Base_Col"]), D(g["dir_Adjust_col"]), sv, sky, cvs)
+    for got, ref in ((o["base"], g["img_Base_Img"]), (o["season"][0], g["img_Season_Adj_Img"]), (o["shadow_adjust"], g["img_Shadow_Adjust"]),
+                     (o["raw_shadow"], g["img_Raw_Shadow_Mask"]), (o["shaded"][1:], g["sweep_imgs"])):
+        assert _max_dev(got, ref) <= 1e-14
+    PS = (orc.get_PV(rho, dl) * (1 - torch.exp(-rho * dl))).numpy()
+    r, t = 17, 5
+    want = np.zeros(3)
+    for s in range(rho.shape[1]):
+        c = 1 / (1 + np.exp(-(g["dir_Base_Col"][r, s].astype(np.float64) + cvs[t].numpy() @ g["dir_Adjust_col"][r, s].astype(np.float64))))
+        want += PS[r, s] * c * (float(sv[r, s]) + (1 - float(sv[r, s])) * sky.numpy())
+    np.testing.assert_allclose(o["classic"][t, r].numpy(), want, rtol=1e-13)
