@@ -20,7 +20,7 @@
 
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "gemm_rows.h"
 #include "train.h"
 
 namespace snerf {
@@ -177,7 +177,7 @@ hipError_t launch_gemm(const GemmArgs& g, hipStream_t st) {
 //     C[m,n] (+)= alpha * (sum_k A[m,k] * Bt[n,k] + bias[n])          [+ per-column shifted sums for train-mode BatchNorm]
 //   A  : fp32 activations / gradients [M, lda], k contiguous - read straight from HBM into MFMA operand registers
 //        (lane (r,h) of a 32x32x16 MFMA holds 8 consecutive k of row r: two 16-byte loads), split into bf16 hi/lo in registers
-//   Bt : weights, pre-split by split_weights_kernel into MFMA fragment order, resident in LDS for the whole kernel
+//   Bt : weights, pre-split by split_weights_kernel (gemm_rows.h) into MFMA fragment order, resident in LDS for the whole kernel
 // Every wave owns its 32 rows: no barrier in the main loop, activations never touch LDS, four k-steps of loads are kept
 // in flight.  Persistent: 1 workgroup (8 waves) per CU loops over 256-row tiles; the n-groups of
 // one row tile sit on the same XCD so the second reader of a tile hits that XCD's L2.
@@ -187,26 +187,6 @@ namespace snerf {
 
 
 constexpr int RO_PF = 4;                                     // k-steps of A loads in flight ahead of the MFMAs
-
-// Fragment-order split: tile T (32 output columns), k-step ks (16 k): 1 KiB hi then 1 KiB lo; inside, lane (r,h) owns 16 bytes =
-// bf16 of Bt[T*32 + r][ks*16 + h*8 + 0..7].  Bt[n][k] = W[n][k] (transpose = 0, W is [rows x cols]) or W[k][n] (transpose = 1).
-__global__ void split_weights_kernel(const float* W, int rows, int cols, int transpose, uint16_t* frag, int n_tiles, int ksteps) {
-    const int64_t total = (int64_t)n_tiles * ksteps * 512;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
-        const int64_t tk = i >> 9;
-        const int ks = (int)(tk % ksteps), T = (int)(tk / ksteps);
-        const int n = T * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8 + e;
-        float v = 0.f;
-        if (!transpose) { if (n < rows && k < cols) v = W[(int64_t)n * cols + k]; }
-        else { if (k < rows && n < cols) v = W[(int64_t)k * cols + n]; }
-        const __bf16 h = (__bf16)v;
-        const __bf16 l = (__bf16)(v - (float)h);
-        uint16_t* dst = frag + tk * 1024 + lane * 8 + e;
-        dst[0] = __builtin_bit_cast(uint16_t, h);
-        dst[512] = __builtin_bit_cast(uint16_t, l);
-    }
-}
 
 // AOL ("activation on load"): the A operand is the stored PRE-activation Z of the layer below; its first act_cols columns
 // become sin(2 pi (a z + b)) = one fma + one v_sin_f32 (which takes revolutions) while they sit in registers.  The table
@@ -223,11 +203,7 @@ __global__ __launch_bounds__(512) void gemm_rows_kernel(const GemmX g) {
     const int r = lane & 31, h = lane >> 5;
     const int KS = g.ksteps;
     const int n_groups = (g.n_tiles + NT - 1) / NT;
-    // block -> (XCD, slot on the XCD) -> (n-group, worker): all n-groups of a worker share an XCD (and its L2)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int workers_per_xcd = slots / n_groups;
-    if (slot >= workers_per_xcd * n_groups) return;
-    const int grp = slot % n_groups, worker = (slot / n_groups) * 8 + xcd, n_workers = workers_per_xcd * 8;
+    SNERF_ROWS_BLOCK_MAP(n_groups);
     const int tiles_here = (g.n_tiles - grp * NT) < NT ? (g.n_tiles - grp * NT) : NT;
 
     {   // weights of this n-group -> LDS (fragment order, straight copy)
@@ -394,27 +370,7 @@ __global__ __launch_bounds__(512) void gemm_rows_kernel(const GemmX g) {
                 }
         }
     }
-    if (g.stats) {      // per-column sums (forward: sum(v - shift), sum((v - shift)^2); ACT: sum v, sum v*xhat) -> double atomics
-        __syncthreads();                                   // weights no longer needed: reuse LDS for the cross-wave reduction
-        float* red = (float*)lds_w;                        // [8 waves][NT][2][32]
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            float a = st1[j] + __shfl_xor(st1[j], 32, 64), b = st2[j] + __shfl_xor(st2[j], 32, 64);
-            if (h == 0) {
-                red[((wave * NT + j) * 2 + 0) * 32 + r] = a;
-                red[((wave * NT + j) * 2 + 1) * 32 + r] = b;
-            }
-        }
-        __syncthreads();
-        if (tid < NT * 64) {
-            const int j = tid >> 6, which = (tid >> 5) & 1, c = tid & 31;
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < RO_WAVES; ++w) s += (double)red[((w * NT + j) * 2 + which) * 32 + c];
-            const int64_t n = (int64_t)(grp * NT + j) * 32 + c;
-            if (j < tiles_here && n < g.N) atomicAdd(g.stats + which * g.N + n, s);
-        }
-    }
+    SNERF_ROWS_COLUMN_SUMS(32, NT, RO_WAVES, st1[j], st2[j], h == 0, r, j < tiles_here)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -448,25 +404,9 @@ __global__ __launch_bounds__(512) void gemm_rows_full_kernel(const GemmX g) {
     const int r = lane & 31, h = lane >> 5;
     const int KS = g.ksteps;                                        // multiple of PF
     const int n_groups = g.n_tiles / NT;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int workers_per_xcd = slots / n_groups;
-    if (slot >= workers_per_xcd * n_groups) return;
-    const int grp = slot % n_groups, worker = (slot / n_groups) * 8 + xcd, n_workers = workers_per_xcd * 8;
+    SNERF_ROWS_BLOCK_MAP(n_groups);
 
-    {
-        const u32x4* src = (const u32x4*)(g.frag + (int64_t)grp * NT * KS * 1024);
-        u32x4* dst = (u32x4*)lds_w;
-        const int n16 = NT * KS * 128;
-        int i0 = tid;
-        for (; i0 + 7 * 512 < n16; i0 += 512 * 8) {                  // n16 is a multiple of 512
-            u32x4 v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = src[i0 + q * 512];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) dst[i0 + q * 512] = v[q];
-        }
-        for (; i0 < n16; i0 += 512) dst[i0] = src[i0];
-    }
+    SNERF_ROWS_WEIGHTS_TO_LDS(NT, 512)      // (a multiple of 512 pieces)
     const uint8_t* lds_tab = lds_w + (size_t)NT * KS * 2048;
     if (AOL == 1) {
         float* dst = (float*)lds_tab;
@@ -580,17 +520,7 @@ __global__ __launch_bounds__(512) void gemm_rows_full_kernel(const GemmX g) {
             float zt[2][16], ec[2][4];
             auto fetch = [&](int j, float (&z_)[16], float (&c_)[4]) {    // ACT: pre-activations and [a, b, mu, istd] of column j
                 const int64_t n = (int64_t)(grp * NT + j) * 32 + r;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int64_t ro = (e & 3) + 8 * (e >> 2);
-                    if (INTERIOR) {
-                        z_[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_z, lz + j * 128, (int)((rowu + ro) * g.eld * 4), 0));
-                    } else {
-                        int64_t m = row0 + ro;
-                        m = m < g.M ? m : g.M - 1;
-                        z_[e] = g.ez[m * g.eld + n];
-                    }
-                }
+                SNERF_ROWS_ACT_FETCH_Z(z_, 16, (e & 3) + 8 * (e >> 2), row0 + ro, j * 128, n)
                 c_[0] = g.etab[n]; c_[1] = g.etab[g.N + n];
                 c_[2] = g.emu[n]; c_[3] = g.eistd[n];                     // the launcher substitutes zeros for a layer without BatchNorm
             };
@@ -606,7 +536,7 @@ __global__ __launch_bounds__(512) void gemm_rows_full_kernel(const GemmX g) {
                 for (int e = 0; e < 16; ++e) {
                     const int64_t ro = (e & 3) + 8 * (e >> 2);
                     float v = g.alpha * (acc[j][e] + biasv[j]);
-                    if (ACT) v *= __builtin_amdgcn_cosf(__builtin_fmaf(ec[j & 1][0], zt[j & 1][e], ec[j & 1][1]));
+                    if (ACT) v = rows_act_bwd(v, zt[j & 1][e], ec[j & 1]);
                     const bool ok = INTERIOR || row0 + ro < g.M;
                     if (INTERIOR) {
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs_c, lc + j * 128, (int)((rowu + ro) * g.ldc * 4), 0);
@@ -614,9 +544,7 @@ __global__ __launch_bounds__(512) void gemm_rows_full_kernel(const GemmX g) {
                         g.C[(row0 + ro) * g.ldc + n] = v;
                     }
                     if (ACT) {
-                        const float s1 = v, s2 = v * ((zt[j & 1][e] - ec[j & 1][2]) * ec[j & 1][3]);
-                        st1[j] += ok ? s1 : 0.f;
-                        st2[j] += ok ? s2 : 0.f;
+                        rows_act_bwd_sums(v, zt[j & 1][e], ec[j & 1], ok, st1[j], st2[j]);
                     } else {
                         const float d = v - shiftv[j];
                         st1[j] += ok ? d : 0.f;
@@ -639,27 +567,7 @@ __global__ __launch_bounds__(512) void gemm_rows_full_kernel(const GemmX g) {
     // (an address, for instance).  The wait also keeps the registers allocated up to this point.
 #pragma unroll
     for (int d = 0; d < PF; ++d) a8_wait<0>(px[d], py[d]);
-    if (g.stats) {
-        __syncthreads();
-        float* red = (float*)lds_w;                        // [8 waves][NT][2][32]
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            float a = st1[j] + __shfl_xor(st1[j], 32, 64), b = st2[j] + __shfl_xor(st2[j], 32, 64);
-            if (h == 0) {
-                red[((wave * NT + j) * 2 + 0) * 32 + r] = a;
-                red[((wave * NT + j) * 2 + 1) * 32 + r] = b;
-            }
-        }
-        __syncthreads();
-        if (tid < NT * 64) {
-            const int j = tid >> 6, which = (tid >> 5) & 1, c = tid & 31;
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < RO_WAVES; ++w) s += (double)red[((w * NT + j) * 2 + which) * 32 + c];
-            const int64_t n = (int64_t)(grp * NT + j) * 32 + c;
-            if (n < g.N) atomicAdd(g.stats + which * g.N + n, s);
-        }
-    }
+    SNERF_ROWS_COLUMN_SUMS(32, NT, RO_WAVES, st1[j], st2[j], h == 0, r, true)
 }
 
 // =====================================================================================================
@@ -671,35 +579,38 @@ __global__ __launch_bounds__(512) void gemm_rows_full_kernel(const GemmX g) {
 // Stage = 32 points; double-buffered LDS (2 x 64 KiB), one barrier per stage; the loads of stage s+1 fly during the MFMAs of s.
 // Direction of the next streaming kernel (row GEMMs on the 16x16x32 form, weight gradients): they alternate, so that a kernel starts with the
 // rows its producer touched last - some of which are still in the Infinity Cache (forward 256 -> 256: 182 -> 177 us; SNERF_SNAKE=0: always forwards)
-static int ro_grid_blocks_public();
 // Launch context of the calling thread (set by a training pass, train.cpp CtxGuard): the launch parity of ITS trainer - reset at the start of
 // every pass, so the direction of each launch (and with it the order in which wgrad_bf16x3_kernel accumulates its fp32 stages) is a function of the
 // launch's position in the pass, not of the process's launch history - and that trainer's pre-allocated partial-sum scratch.
 struct LaunchCtx { float* wgrad_partial = nullptr; size_t wgrad_floats = 0; unsigned* parity = nullptr; };
 static thread_local LaunchCtx tl_ctx;
 void gemm_launch_context(float* wgrad_partial, size_t wgrad_floats, unsigned* parity) { tl_ctx = LaunchCtx{wgrad_partial, wgrad_floats, parity}; }
-size_t gemm_wgrad_partial_floats() { return (size_t)(ro_grid_blocks_public() < 256 ? 256 : ro_grid_blocks_public()) * 8 * 2 * 4 * 1024; }
+size_t gemm_wgrad_partial_floats() { return (size_t)(gemm_device_cus(true) < 256 ? 256 : gemm_device_cus(true)) * 8 * 2 * 4 * 1024; }
 
 int stream_direction(int64_t rows) {
     static std::atomic<unsigned> launches{0};        // stand-alone launches (snerf_linear_*): one process-wide parity
-    static const int snake = [] { const char* e = getenv("SNERF_SNAKE"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (!snake || rows < 32768) return 0;                  // (a small launch neither gains from a direction nor takes a turn)
+    if (!rows_switches().snake || rows < 32768) return 0;                  // (a small launch neither gains from a direction nor takes a turn)
     if (tl_ctx.parity) return (int)((*tl_ctx.parity)++ & 1u);
     return (int)(launches.fetch_add(1, std::memory_order_relaxed) & 1u);
 }
 
-static int ro_grid_blocks();
-static int ro_grid_blocks_public() { return ro_grid_blocks(); }
-static int ro_grid_blocks() {
-    static int n = 0;
-    if (!n) {
+int gemm_device_cus(bool whole_xcds) {
+    static int cus = 0;
+    if (!cus) {
         hipDeviceProp_t p;
         int dev = 0;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-        n = n / 8 * 8;
-        if (n < 8) n = 8;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
     }
-    return n;
+    if (!whole_xcds) return cus;
+    return cus / 8 * 8 < 8 ? 8 : cus / 8 * 8;
+}
+
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int env_not0(const char* name) { const char* e = getenv(name); return (e && e[0] == '0') ? 0 : 1; }      // on unless the value starts with '0'
+const RowsSwitches& rows_switches() {
+    static const RowsSwitches sw = {env_int("SNERF_GEMM_AREG", 1), env_int("SNERF_GEMM_AREG_ACT", 1), env_int("SNERF_AREG_HV", 2), env_not0("SNERF_GEMM_FULL"),
+                                    env_int("SNERF_GEMM_PF", 0),   env_not0("SNERF_GEMM16"),          env_not0("SNERF_GEMM16_K320"), env_not0("SNERF_SNAKE")};
+    return sw;
 }
 
 struct WgradX {
@@ -963,15 +874,7 @@ float* gemm_partial_scratch(hipStream_t st, size_t floats) { return wgrad_scratc
 
 template <bool FULL, bool BNZ, int TA, int TB>
 static hipError_t launch_wgrad_as(const WgradX& g, dim3 grid, hipStream_t st) {
-    static bool done = false;
-    auto k = wgrad_bf16x3_kernel<FULL, BNZ, TA, TB>;
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
-    hipLaunchKernelGGL(k, grid, dim3(512), 131072, st, g);
-    return hipGetLastError();
+    return launch_big_lds<wgrad_bf16x3_kernel<FULL, BNZ, TA, TB>, 131072>(grid, dim3(512), 131072, st, g);
 }
 
 hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t ldi, int64_t M, int n_out, int n_in, float alpha,
@@ -986,7 +889,7 @@ hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t 
     const int ta = (small_blocks && n_out <= 128) ? 1 : 2, tb = (small_blocks && n_in <= 128) ? 2 : 4;
     const int bo = 128 * ta, bi = 64 * tb;
     const int by = (n_out + bo - 1) / bo, bz = (n_in + bi - 1) / bi;
-    int64_t bx = ro_grid_blocks() / (by * bz);
+    int64_t bx = gemm_device_cus(true) / (by * bz);
     if (bx < 1) bx = 1;
     int64_t rows = (M + bx - 1) / bx;
     rows = (rows + WG_STAGE - 1) / WG_STAGE * WG_STAGE;
@@ -1025,12 +928,17 @@ hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t 
     return hipGetLastError();
 }
 
-hipError_t launch_split_weights(const float* W, int rows, int cols, bool transpose, uint16_t* frag, int n_tiles, int ksteps, hipStream_t st) {
+hipError_t launch_split_weights(SplitLayout layout, const float* W, int rows, int cols, bool transpose, uint16_t* frag, int n_tiles, int ksteps,
+                                int max_blocks, hipStream_t st) {
     const int64_t total = (int64_t)n_tiles * ksteps * 512;
     if (total <= 0) return hipSuccess;
     int64_t b = (total + 255) / 256;
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL(split_weights_kernel, dim3((unsigned)b), dim3(256), 0, st, W, rows, cols, transpose ? 1 : 0, frag, n_tiles, ksteps);
+    if (b > max_blocks) b = max_blocks;
+    const dim3 grid((unsigned)b), block(256);
+    const int tr = transpose ? 1 : 0;
+    if (layout == SplitLayout::Tile16) hipLaunchKernelGGL(split_weights_kernel<SplitLayout::Tile16>, grid, block, 0, st, W, rows, cols, tr, frag, n_tiles, ksteps);
+    else if (layout == SplitLayout::KMajor32) hipLaunchKernelGGL(split_weights_kernel<SplitLayout::KMajor32>, grid, block, 0, st, W, rows, cols, tr, frag, n_tiles, ksteps);
+    else hipLaunchKernelGGL(split_weights_kernel<SplitLayout::Tile32>, grid, block, 0, st, W, rows, cols, tr, frag, n_tiles, ksteps);
     return hipGetLastError();
 }
 
@@ -1048,144 +956,154 @@ static const float* zeros_dev(int64_t n) {
     return p;
 }
 
-template <int NT, int PF>
-static hipError_t launch_full(const GemmX& gx, int aol_mode, int act_mode, dim3 grid, size_t lds, hipStream_t st) {
-#define SNERF_GO(A_, C_)                                                                                              \
-    do {                                                                                                              \
-        static bool done = false;                                                                                     \
-        auto k = gemm_rows_full_kernel<NT, PF, A_, C_>;                                                               \
-        if (!done) {                                                                                                  \
-            hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess) return e;                                                                            \
-            done = true;                                                                                              \
-        }                                                                                                             \
-        hipLaunchKernelGGL(k, grid, dim3(512), lds, st, gx);                                                          \
-    } while (0)
-    if (act_mode == 1) {
-        if constexpr (NT > 1) SNERF_GO(0, 1);
-        else return hipErrorInvalidValue;
-    }
-    else if (aol_mode == 1) SNERF_GO(1, 0);
-    else SNERF_GO(0, 0);
-#undef SNERF_GO
-    return hipGetLastError();
-}
-
 // n-tiles whose weights (2 KiB per tile and 16-k step) fit the 160 KiB LDS beside an activation-on-load table (8 bytes per input column):
 // four up to K = 320, two up to K = 608 (W = 512's [fc4 | PE] layer has 36 k-steps)
 int gemm_rows_group_tiles(int ksteps) { return ksteps <= 20 ? 4 : (ksteps <= 38 ? 2 : 0); }
 
-hipError_t launch_gemm_bf16x3(const GemmX& g, hipStream_t st) {
-    if (g.M <= 0 || g.N <= 0) return hipSuccess;
-    const int nt = gemm_rows_group_tiles(g.ksteps);
+// The routing of launch_gemm_bf16x3: every choice among the four kernels and their instances is made here, and nothing is launched.
+hipError_t plan_gemm_rows(const GemmX& g, const RowsSwitches& sw, RowsPlan& p) {
+    constexpr size_t LDS_MAX = 160 * 1024;
+    const int KS = g.ksteps;
+    const int nt = gemm_rows_group_tiles(KS);
     if (!nt) return hipErrorInvalidValue;
-    const size_t lds = (size_t)nt * g.ksteps * 2048;
-    const int groups = (g.n_tiles + nt - 1) / nt;
-    int blocks = ro_grid_blocks();
-    if (blocks / 8 < groups) blocks = groups * 8;            // at least one worker per XCD
-    static bool attr_done = false;
-    if (!attr_done) {
-        const void* fns[6] = {(const void*)gemm_rows_kernel<4, false, false>, (const void*)gemm_rows_kernel<4, true, false>,
-                              (const void*)gemm_rows_kernel<4, false, true>, (const void*)gemm_rows_kernel<2, false, false>,
-                              (const void*)gemm_rows_kernel<2, true, false>, (const void*)gemm_rows_kernel<2, false, true>};
-        for (const void* f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        attr_done = true;
-    }
     const bool aol = g.act_tab != nullptr && g.act_cols > 0;
     const bool act = g.ez != nullptr;
     if (aol && (g.act_cols % 8 != 0 || g.act_cols > g.K || (uintptr_t)g.act_tab % 16 != 0)) return hipErrorInvalidValue;
     if (act && (aol || !g.stats || !g.etab)) return hipErrorInvalidValue;
+    p = RowsPlan{};
+    p.aol = aol ? 1 : 0;
+    p.act = act ? 1 : 0;
+    p.hv = 1;
+    // The reference's default width (512-wide layers): accumulators in AGPRs, A and weights streamed (gemm_areg.hip).  SNERF_GEMM_AREG=2: every shape the
+    // kernel takes (also the 256-wide layers of a W = 256 network, where the column-group kernels are HBM-bound already)
+    if (sw.areg && (!act || sw.areg_act) && g.W && (g.N == 512 || g.K > 256 || sw.areg == 2) && gemm_areg_ok(g)) {
+        int tile_rows;
+        size_t ring_bytes;
+        gemm_areg_geometry(&tile_rows, &ring_bytes);
+        // two waves per SIMD, a column half each: not for the activation-backward form - with its pre-activation staging the 128 architectural registers
+        // of a wave overflow by four (hipcc would park them in the accumulators' AGPRs), and the forward's gain (-4 % with activation on load, 0 without)
+        // would not pay for a third staging scheme
+        const bool two = g.N == 512 && sw.areg_hv >= 2 && !act;
+        p.kernel = RowsKernel::AREG;
+        p.hv = two ? 2 : 1;
+        p.nt = two ? 8 : (int)(g.N / 32);                         // HV = 2: eight n-tiles per column half
+        p.pf = two ? 4 : (KS % 8 == 0 ? 8 : 4);
+        p.lds = ring_bytes + (size_t)(2 * 16 * KS + (act ? 7 : 3) * g.N) * 4 + (two ? 4 * 4096 : 0);
+        if (p.lds > LDS_MAX) return hipErrorInvalidValue;
+        const int64_t row_tiles = (g.M + tile_rows - 1) / tile_rows;
+        const int cus = gemm_device_cus(false);
+        p.grid = (unsigned)(row_tiles < cus ? (row_tiles < 1 ? 1 : row_tiles) : cus);
+        p.split = SplitLayout::KMajor32;
+        return hipSuccess;
+    }
+    const auto grid_for = [](int groups) { const int b = gemm_device_cus(true); return (unsigned)(b / 8 < groups ? groups * 8 : b); };      // at least one worker per XCD
+    p.split = SplitLayout::Tile32;
+    // the pipelined full-tile kernels wherever the shape allows it (every per-point layer of the training step)
+    const bool k_ok = g.K % 16 == 0 || (g.a_padded && g.lda >= (int64_t)KS * 16);
+    const bool a_vec = ((uintptr_t)g.A % 16 == 0) && (g.lda % 4 == 0);
+    int pf = KS % 8 == 0 ? 8 : (KS % 4 == 0 ? 4 : (KS % 2 == 0 ? 2 : 0));
+    if (act && pf > 4) pf = 4;                               // the activation-backward epilogue needs the registers
+    if (sw.pf && sw.pf <= pf && KS % sw.pf == 0 && (sw.pf == 8 || sw.pf == 4 || sw.pf == 2)) pf = sw.pf;
+    // activation on load wants its table in LDS: with 20 k-steps four n-tiles fill the 160 KiB, so that layer runs two per group
+    int ntf = nt;
+    if (aol && ntf == 4 && (size_t)4 * KS * 2048 + (size_t)g.act_cols * 8 > LDS_MAX) ntf = 2;
+    if (g.n_tiles == 1 && !act) ntf = 1;                      // thin heads (1..32 outputs)
+    const size_t lds_f = (size_t)ntf * KS * 2048 + (aol ? (size_t)g.act_cols * 8 : 0);
+    if (sw.full && k_ok && a_vec && pf && g.n_tiles % ntf == 0 && (g.N == (int64_t)g.n_tiles * 32 || ntf == 1) && (!aol || g.act_cols % 16 == 0) &&
+        !g.accumulate && lds_f <= LDS_MAX && g.M * g.ldc < (1ll << 29) && (!act || g.M * g.eld < (1ll << 29))) {      // 32-bit byte offsets
+        p.grid = grid_for(g.n_tiles / ntf);
+        p.tab_lds = p.aol;
+        p.zero_bn = act && !g.emu;                             // a layer without BatchNorm: xhat sums are defined as 0
+        // the 16x16x32 form (quad-coalesced A loads): raw weights at hand, K in whole 32-k steps, and
+        //   wide: 128-column groups (8 tiles of 16) of the wide layers - the thin heads keep the 32x32x16 form;
+        //   k320: the forward of the K = 320 layer ([fc4 | PE]: 64-column groups, four of them read every A row, and its 128-column slice of hi / lo
+        //         weights does not fit the LDS beside its table) - its quad-coalesced A loads cost the vector-memory path half of what the lane-per-row
+        //         operand layout of the 32x32x16 form does.
+        // Behind the weights and the table: the per-column constants of the group (bias; ACT: four more)
+        const bool k32 = KS % 2 == 0 && (g.K % 32 == 0 || (g.a_padded && g.lda >= (int64_t)KS * 16));
+        const bool wide = ntf == 4 && lds_f + 128 * 4 * 5 <= LDS_MAX;
+        const bool k320 = sw.gemm16_k320 && ntf == 2 && !act && g.n_tiles % 2 == 0 && lds_f + 128 * 4 <= LDS_MAX;
+        if (sw.gemm16 && g.W && k32 && (!aol || g.act_cols % 32 == 0) && (wide || k320)) {
+            const int KS32 = KS / 2;
+            p.kernel = RowsKernel::ROWS16;
+            p.nt = wide ? 8 : 4;
+            // 32-k steps of A in flight: 4 with activation on load (244 registers, no scratch), 2 otherwise (the plain form spills at 4,
+            // the activation-backward epilogue needs the registers); must divide the k-step count
+            p.pf = (aol && !act && KS32 % 4 == 0) ? 4 : (KS32 % 2 == 0 ? 2 : 1);
+            if (gemm_rows16_waves() != RO_WAVES) {             // experimental geometry (16 waves x 16 rows, 128 registers): only the scratch-free forms
+                if (act) return hipErrorInvalidValue;
+                p.pf = 1;
+            }
+            p.lds = lds_f + 128 * 4 * (wide && act ? 5 : 1);
+            p.split = SplitLayout::Tile16;
+            return hipSuccess;
+        }
+        p.kernel = RowsKernel::FULL;
+        p.nt = ntf;
+        p.pf = pf;
+        p.lds = lds_f;
+        return hipSuccess;
+    }
+    // the general kernel.  AOL: the [a | b] table goes behind the weights when the 160 KiB allow it
+    p.kernel = RowsKernel::GENERAL;
+    p.nt = nt;
+    p.grid = grid_for((g.n_tiles + nt - 1) / nt);
+    p.lds = (size_t)nt * KS * 2048;
+    if (aol && p.lds + (size_t)g.act_cols * 8 <= LDS_MAX) { p.tab_lds = 1; p.lds += (size_t)g.act_cols * 8; }
+    return hipSuccess;
+}
+
+template <int NT, int PF>
+static hipError_t launch_full(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
+    const dim3 grid(p.grid), block(512);
+    if (p.act) {
+        if constexpr (NT > 1) return launch_big_lds<gemm_rows_full_kernel<NT, PF, 0, 1>>(grid, block, p.lds, st, gx);
+        else return hipErrorInvalidValue;
+    }
+    if (p.aol) return launch_big_lds<gemm_rows_full_kernel<NT, PF, 1, 0>>(grid, block, p.lds, st, gx);
+    return launch_big_lds<gemm_rows_full_kernel<NT, PF, 0, 0>>(grid, block, p.lds, st, gx);
+}
+template <int NT>
+static hipError_t launch_full_nt(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
+    return p.pf == 8 ? launch_full<NT, 8>(gx, p, st) : p.pf == 4 ? launch_full<NT, 4>(gx, p, st) : launch_full<NT, 2>(gx, p, st);
+}
+template <int NT>
+static hipError_t launch_general(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
+    const dim3 grid(p.grid), block(512);
+    if (p.act) return launch_big_lds<gemm_rows_kernel<NT, false, true>>(grid, block, p.lds, st, gx);
+    if (p.aol) return launch_big_lds<gemm_rows_kernel<NT, true, false>>(grid, block, p.lds, st, gx);
+    return launch_big_lds<gemm_rows_kernel<NT, false, false>>(grid, block, p.lds, st, gx);
+}
+
+// Executes a plan: raw weights are split here, in the fragment order of the kernel that runs.
+static hipError_t run_gemm_rows(const GemmX& g, const RowsPlan& p, hipStream_t st) {
     GemmX gx = g;
-    gx.tab_lds = 0;
-    size_t lds_total = lds;
-    if (aol && lds + (size_t)g.act_cols * 8 <= 160 * 1024) { gx.tab_lds = 1; lds_total = lds + (size_t)g.act_cols * 8; }
-    const dim3 grid(blocks), block(512);
-    // raw weights: split them here, in the fragment order of the kernel that runs
-    auto split32 = [&]() -> hipError_t {
-        return g.W ? launch_split_weights(g.W, g.w_rows, g.w_cols, g.w_transpose != 0, const_cast<uint16_t*>(g.frag), g.n_tiles, g.ksteps, st) : hipSuccess;
-    };
-    {   // the reference's default width (512-wide layers): accumulators in AGPRs, A and weights streamed (gemm_areg.hip).  SNERF_GEMM_AREG=0 off, =2 every
-        // shape the kernel takes (also the 256-wide layers of a W = 256 network, where the column-group kernels are HBM-bound already)
-        static const int areg_mode = [] { const char* e = getenv("SNERF_GEMM_AREG"); return e ? atoi(e) : 1; }();
-        static const int areg_act = [] { const char* e = getenv("SNERF_GEMM_AREG_ACT"); return e ? atoi(e) : 1; }();      // the activation-backward form on it: SNERF_GEMM_AREG_ACT=0 keeps the column-group kernel for those
-        if (areg_mode && (!act || areg_act) && g.W && (g.N == 512 || g.K > 256 || areg_mode == 2) && gemm_areg_ok(g)) {
-            hipError_t e = launch_areg_split_weights(g.W, g.w_rows, g.w_cols, g.w_transpose != 0, const_cast<uint16_t*>(g.frag), g.n_tiles, g.ksteps, st);
-            if (e != hipSuccess) return e;
-            return launch_gemm_areg(gx, st);
-        }
+    gx.tab_lds = p.tab_lds;
+    if (p.zero_bn) {
+        gx.emu = zeros_dev(g.N);
+        gx.eistd = gx.emu;
+        if (!gx.emu) return hipErrorOutOfMemory;
     }
-    {   // the pipelined full-tile kernel wherever the shape allows it (every per-point layer of the training step)
-        static const int full_mode = [] { const char* e = getenv("SNERF_GEMM_FULL"); return (e && e[0] == '0') ? 0 : 1; }();
-        static const int pf_force = [] { const char* e = getenv("SNERF_GEMM_PF"); return e ? atoi(e) : 0; }();
-        static const int mode16 = [] { const char* e = getenv("SNERF_GEMM16"); return (e && e[0] == '0') ? 0 : 1; }();
-        const int KS = g.ksteps;
-        const bool k_ok = g.K % 16 == 0 || (g.a_padded && g.lda >= (int64_t)KS * 16);
-        const bool a_vec = ((uintptr_t)g.A % 16 == 0) && (g.lda % 4 == 0);
-        int pf = KS % 8 == 0 ? 8 : (KS % 4 == 0 ? 4 : (KS % 2 == 0 ? 2 : 0));
-        if (act && pf > 4) pf = 4;                               // the activation-backward epilogue needs the registers
-        if (pf_force && pf_force <= pf && KS % pf_force == 0 && (pf_force == 8 || pf_force == 4 || pf_force == 2)) pf = pf_force;
-        // activation on load wants its table in LDS: with 20 k-steps four n-tiles fill the 160 KiB, so that layer runs two per group
-        int ntf = nt;
-        if (aol && ntf == 4 && (size_t)4 * KS * 2048 + (size_t)g.act_cols * 8 > 160 * 1024) ntf = 2;
-        if (g.n_tiles == 1 && !act) ntf = 1;                      // thin heads (1..32 outputs)
-        const size_t lds_f = (size_t)ntf * KS * 2048 + (aol ? (size_t)g.act_cols * 8 : 0);
-        if (full_mode && k_ok && a_vec && pf && g.n_tiles % ntf == 0 && (g.N == (int64_t)g.n_tiles * 32 || ntf == 1) && (!aol || g.act_cols % 16 == 0) &&
-            !g.accumulate && lds_f <= 160 * 1024 && g.M * g.ldc < (1ll << 29) && (!act || g.M * g.eld < (1ll << 29))) {      // 32-bit byte offsets
-            const int groups_f = g.n_tiles / ntf;
-            int blocks_f = ro_grid_blocks();
-            if (blocks_f / 8 < groups_f) blocks_f = groups_f * 8;
-            const dim3 grid_f(blocks_f);
-            gx.tab_lds = aol ? 1 : 0;
-            const int aol_mode = aol ? 1 : 0, act_mode = act ? 1 : 0;
-            if (act && !gx.emu) {                                  // a layer without BatchNorm: xhat sums are defined as 0
-                gx.emu = zeros_dev(g.N);
-                gx.eistd = gx.emu;
-                if (!gx.emu) return hipErrorOutOfMemory;
-            }
-            // the 16x16x32 form (quad-coalesced A loads): raw weights at hand, K in whole 32-k steps, wide layers only (the thin
-            // heads and the 64-column groups of the K = 320 layer keep the 32x32x16 form)
-            const bool k32 = KS % 2 == 0 && (g.K % 32 == 0 || (g.a_padded && g.lda >= (int64_t)KS * 16));
-            if (mode16 && g.W && k32 && ntf == 4 && (!aol || g.act_cols % 32 == 0) && lds_f + 128 * 4 * 5 <= 160 * 1024) {
-                return launch_gemm_rows16(gx, aol_mode, act_mode, grid_f, lds_f + 128 * 4 * (act_mode ? 5 : 1), st);      // + per-column constants
-            }
-            // the K = 320 layer ([fc4 | PE]: 64-column groups, four of them read every A row): its forward on the same kernel, whose quad-coalesced
-            // A loads cost the vector-memory path half of what the lane-per-row operand layout of the 32x32x16 form does
-            static const int mode16_k320 = [] { const char* e = getenv("SNERF_GEMM16_K320"); return (e && e[0] == '0') ? 0 : 1; }();
-            if (mode16 && mode16_k320 && g.W && k32 && ntf == 2 && !act && g.n_tiles % 2 == 0 && (!aol || g.act_cols % 32 == 0) && lds_f + 128 * 4 <= 160 * 1024) {
-                return launch_gemm_rows16(gx, aol_mode, 0, grid_f, lds_f + 128 * 4, st, 4);
-            }
-            {
-                hipError_t e = split32();
-                if (e != hipSuccess) return e;
-            }
-            if (ntf == 1)
-                return pf == 8 ? launch_full<1, 8>(gx, aol_mode, 0, grid_f, lds_f, st)
-                               : pf == 4 ? launch_full<1, 4>(gx, aol_mode, 0, grid_f, lds_f, st) : launch_full<1, 2>(gx, aol_mode, 0, grid_f, lds_f, st);
-            return ntf == 4 ? (pf == 8 ? launch_full<4, 8>(gx, aol_mode, act_mode, grid_f, lds_f, st)
-                                       : pf == 4 ? launch_full<4, 4>(gx, aol_mode, act_mode, grid_f, lds_f, st)
-                                                 : launch_full<4, 2>(gx, aol_mode, act_mode, grid_f, lds_f, st))
-                            : (pf == 8 ? launch_full<2, 8>(gx, aol_mode, act_mode, grid_f, lds_f, st)
-                                       : pf == 4 ? launch_full<2, 4>(gx, aol_mode, act_mode, grid_f, lds_f, st)
-                                                 : launch_full<2, 2>(gx, aol_mode, act_mode, grid_f, lds_f, st));
-        }
-    }
-    {
-        hipError_t e = split32();
+    if (p.kernel == RowsKernel::ROWS16) gx.reverse = stream_direction(gx.M);      // every other streaming launch walks its row tiles backwards
+    if (g.W) {
+        const bool t16 = p.split == SplitLayout::Tile16;                          // 16-column tiles, 32-k steps
+        hipError_t e = launch_split_weights(p.split, g.W, g.w_rows, g.w_cols, g.w_transpose != 0, const_cast<uint16_t*>(g.frag), t16 ? 2 * g.n_tiles : g.n_tiles,
+                                            t16 ? g.ksteps / 2 : g.ksteps, p.split == SplitLayout::KMajor32 ? 2048 : 4096, st);
         if (e != hipSuccess) return e;
     }
-    if (nt == 4) {
-        if (act) hipLaunchKernelGGL((gemm_rows_kernel<4, false, true>), grid, block, lds_total, st, gx);
-        else if (aol) hipLaunchKernelGGL((gemm_rows_kernel<4, true, false>), grid, block, lds_total, st, gx);
-        else hipLaunchKernelGGL((gemm_rows_kernel<4, false, false>), grid, block, lds_total, st, gx);
-    } else {
-        if (act) hipLaunchKernelGGL((gemm_rows_kernel<2, false, true>), grid, block, lds_total, st, gx);
-        else if (aol) hipLaunchKernelGGL((gemm_rows_kernel<2, true, false>), grid, block, lds_total, st, gx);
-        else hipLaunchKernelGGL((gemm_rows_kernel<2, false, false>), grid, block, lds_total, st, gx);
+    switch (p.kernel) {
+        case RowsKernel::AREG: return launch_gemm_areg(gx, p, st);
+        case RowsKernel::ROWS16: return launch_gemm_rows16(gx, p, st);
+        case RowsKernel::FULL: return p.nt == 1 ? launch_full_nt<1>(gx, p, st) : p.nt == 4 ? launch_full_nt<4>(gx, p, st) : launch_full_nt<2>(gx, p, st);
+        default: return p.nt == 4 ? launch_general<4>(gx, p, st) : launch_general<2>(gx, p, st);
     }
-    return hipGetLastError();
+}
+
+hipError_t launch_gemm_bf16x3(const GemmX& g, hipStream_t st) {
+    if (g.M <= 0 || g.N <= 0) return hipSuccess;
+    RowsPlan p;
+    const hipError_t e = plan_gemm_rows(g, rows_switches(), p);
+    return e != hipSuccess ? e : run_gemm_rows(g, p, st);
 }
 
 }  // namespace snerf

@@ -13,7 +13,7 @@
 //     in the AGPRs and walked the n-tiles: it had to fetch and convert the next tile's A inside its last n-tile - a 14 TB/s burst chip-wide, 110 us of a
 //     785 us layer by ablation - and its dependent three-MFMA chains left no room to hide anything: profiles/r5/areg_ablation.txt.)
 //   * weights: L2 -> LDS through the 16 KiB ring of the fused kernels (LDS-DMA, one counted vmcnt wait + one barrier per chunk), k-major
-//     ([k-step][n-tile] pairs: areg_split_weights_kernel), every fragment shared by the four waves of the workgroup;
+//     ([k-step][n-tile] pairs: SplitLayout::KMajor32 of split_weights_kernel, gemm_rows.h), every fragment shared by the four waves of the workgroup;
 //   * n-tiles in pairs: six MFMAs (lo*hi, hi*lo, hi*hi of two accumulators, interleaved: no MFMA waits for the one before it), the next pair's
 //     fragments requested one pair ahead, and between the pairs the slices of the NEXT k-step's conversion;
 //   * epilogue (bias, BatchNorm column sums, stores through a buffer descriptor: no address arithmetic, rows past M dropped by the bounds check) of row
@@ -30,7 +30,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "gemm_common.h"
+#include "gemm_rows.h"
 #include "mlp_device.h"
 #include "train.h"
 
@@ -46,26 +46,6 @@ namespace snerf {
 constexpr int AR_WAVES = 4, AR_ROWS = 32 * AR_WAVES;
 constexpr int AR_D = SNERF_AR_D;              // ring slots (16 KiB chunks of 8 weight pairs)
 static_assert(kChunkPairs == 8 && DMA_PER_WAVE == 4, "ring arithmetic below assumes 8-pair chunks moved by four waves");
-
-// k-major fragment stream: pair (ks, T) = 1 KiB hi then 1 KiB lo; inside, lane (r, h) owns 16 bytes = bf16 of Bt[32 T + r][16 ks + 8 h + 0..7]
-// (the lane layout of split_weights_kernel, gemm.hip; only the order of the pairs differs: there n-tile-major).  Bt[n][k] = W[n][k] or W[k][n] (transpose).
-__global__ void areg_split_weights_kernel(const float* W, int rows, int cols, int transpose, uint16_t* frag, int n_tiles, int ksteps) {
-    const int64_t total = (int64_t)n_tiles * ksteps * 512;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
-        const int64_t tk = i >> 9;
-        const int T = (int)(tk % n_tiles), ks = (int)(tk / n_tiles);
-        const int n = T * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8 + e;
-        float v = 0.f;
-        if (!transpose) { if (n < rows && k < cols) v = W[(int64_t)n * cols + k]; }
-        else { if (k < rows && n < cols) v = W[(int64_t)k * cols + n]; }
-        const __bf16 h = (__bf16)v;
-        const __bf16 l = (__bf16)(v - (float)h);
-        uint16_t* dst = frag + tk * 1024 + lane * 8 + e;
-        dst[0] = __builtin_bit_cast(uint16_t, h);
-        dst[512] = __builtin_bit_cast(uint16_t, l);
-    }
-}
 
 #define AR8(n) "a" #n
 #define AR8x8(n) AR8(n##0), AR8(n##1), AR8(n##2), AR8(n##3), AR8(n##4), AR8(n##5), AR8(n##6), AR8(n##7), AR8(n##8), AR8(n##9)
@@ -582,17 +562,6 @@ __global__ __launch_bounds__(64 * AR_WAVES * HV, 1) void gemm_areg_kernel(const 
     }
 }
 
-static int areg_blocks() {
-    static int n = 0;
-    if (!n) {
-        hipDeviceProp_t p;
-        int dev = 0;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-        if (n < 1) n = 256;
-    }
-    return n;
-}
-
 // shapes this kernel takes: N = 256 or 512 exactly (8 / 16 n-tiles in 128 / 256 AGPRs); K in whole 16-k steps (or zero-padded to one: a_padded), their
 // number a multiple of 4 between 8 and 64; whole 16-byte aligned rows; no accumulate, no activation-backward epilogue; an activation table covers K
 bool gemm_areg_ok(const GemmX& g) {
@@ -605,55 +574,30 @@ bool gemm_areg_ok(const GemmX& g) {
            g.M * g.ldc < (1ll << 29);      // 32-bit byte offsets of the buffer stores
 }
 
-hipError_t launch_areg_split_weights(const float* W, int rows, int cols, bool transpose, uint16_t* frag, int n_tiles, int ksteps, hipStream_t st) {
-    const int64_t total = (int64_t)n_tiles * ksteps * 512;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(areg_split_weights_kernel, dim3(blocks), dim3(256), 0, st, W, rows, cols, transpose ? 1 : 0, frag, n_tiles, ksteps);
-    return hipGetLastError();
+void gemm_areg_geometry(int* tile_rows, size_t* ring_bytes) {
+    *tile_rows = AR_ROWS;
+    *ring_bytes = (size_t)AR_D * kChunkBytes;
 }
 
-// g.frag must hold the k-major stream (launch_areg_split_weights)
-hipError_t launch_gemm_areg(const GemmX& g, hipStream_t st) {
-    if (!gemm_areg_ok(g)) return hipErrorInvalidValue;
-    const bool aol = g.act_tab != nullptr && g.act_cols > 0;
-    const int KS = g.ksteps;
-    const bool act = g.ez != nullptr;
-    static const int hv = [] { const char* e = getenv("SNERF_AREG_HV"); return e ? atoi(e) : 2; }();      // SNERF_AREG_HV=1: the one-wave-per-SIMD form at N = 512 too (A/B)
-    // (not for the activation-backward form: with its pre-activation staging the 128 architectural registers of a wave overflow by four - hipcc would park
-    // them in the accumulators' AGPRs - and the forward's gain, -4 % with activation on load, 0 without, would not pay for a third staging scheme)
-    const bool two = g.N == 512 && hv >= 2 && !act;
-    const size_t lds = (size_t)AR_D * kChunkBytes + (size_t)(2 * 16 * KS + (act ? 7 : 3) * g.N) * 4 + (two ? 4 * 4096 : 0);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const int64_t n_tiles = (g.M + AR_ROWS - 1) / AR_ROWS;
-    int grid = (int)(n_tiles < areg_blocks() ? n_tiles : areg_blocks());
-    if (grid < 1) grid = 1;
-#define AR_LAUNCH_HV(HV_, NT_, AOL_, PFA_, ACT_)                                                                                  \
-    do {                                                                                                                         \
-        auto k = gemm_areg_kernel<NT_, AOL_, PFA_, ACT_, HV_>;                                                                   \
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-        if (e != hipSuccess) return e;                                                                                           \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * AR_WAVES * HV_), lds, st, g);                                                \
-        return hipGetLastError();                                                                                                \
-    } while (0)
-#define AR_LAUNCH(NT_, AOL_, PFA_, ...) AR_LAUNCH_HV(1, NT_, AOL_, PFA_, (0 __VA_OPT__(+) __VA_ARGS__))
-    const bool p8 = KS % 8 == 0;
-    if (two) {      // two waves per SIMD, a column half each
-        if (aol) AR_LAUNCH_HV(2, 8, 1, 4, 0);
-        AR_LAUNCH_HV(2, 8, 0, 4, 0);
+template <int NT, int AOL, int PFA, int ACT = 0, int HV = 1>
+static hipError_t launch_areg(const GemmX& g, const RowsPlan& p, hipStream_t st) {
+    return launch_big_lds<gemm_areg_kernel<NT, AOL, PFA, ACT, HV>>(dim3(p.grid), dim3(64 * AR_WAVES * HV), p.lds, st, g);
+}
+
+// g.frag must hold the k-major stream (SplitLayout::KMajor32); p: the instance plan_gemm_rows chose for a shape gemm_areg_ok takes
+hipError_t launch_gemm_areg(const GemmX& g, const RowsPlan& p, hipStream_t st) {
+    const bool p8 = p.pf == 8, wide = p.nt == 16;      // wide: N = 512 in one wave's 256 AGPRs
+    if (p.hv == 2) return p.aol ? launch_areg<8, 1, 4, 0, 2>(g, p, st) : launch_areg<8, 0, 4, 0, 2>(g, p, st);      // two waves per SIMD, a column half each
+    if (p.act) {      // input gradient with the activation-backward epilogue
+        if (wide) return p8 ? launch_areg<16, 0, 8, 1>(g, p, st) : launch_areg<16, 0, 4, 1>(g, p, st);
+        return p8 ? launch_areg<8, 0, 8, 1>(g, p, st) : launch_areg<8, 0, 4, 1>(g, p, st);
     }
-    if (act) {      // input gradient with the activation-backward epilogue
-        if (g.N == 512) { if (p8) AR_LAUNCH(16, 0, 8, 1); else AR_LAUNCH(16, 0, 4, 1); }
-        if (p8) AR_LAUNCH(8, 0, 8, 1); else AR_LAUNCH(8, 0, 4, 1);
+    if (wide) {
+        if (p.aol) return p8 ? launch_areg<16, 1, 8>(g, p, st) : launch_areg<16, 1, 4>(g, p, st);
+        return p8 ? launch_areg<16, 0, 8>(g, p, st) : launch_areg<16, 0, 4>(g, p, st);
     }
-    if (g.N == 512) {
-        if (aol) { if (p8) AR_LAUNCH(16, 1, 8); else AR_LAUNCH(16, 1, 4); }
-        if (p8) AR_LAUNCH(16, 0, 8); else AR_LAUNCH(16, 0, 4);
-    }
-    if (aol) { if (p8) AR_LAUNCH(8, 1, 8); else AR_LAUNCH(8, 1, 4); }
-    if (p8) AR_LAUNCH(8, 0, 8); else AR_LAUNCH(8, 0, 4);
-#undef AR_LAUNCH
-#undef AR_LAUNCH_HV
+    if (p.aol) return p8 ? launch_areg<8, 1, 8>(g, p, st) : launch_areg<8, 1, 4>(g, p, st);
+    return p8 ? launch_areg<8, 0, 8>(g, p, st) : launch_areg<8, 0, 4>(g, p, st);
 }
 
 }  // namespace snerf

@@ -1,4 +1,5 @@
-// Shared device helpers of the bf16x3 row GEMMs (gemm.hip, gemm16.hip): vector types, the bf16 hi/lo split, tile constants.
+// Shared device helpers of the bf16x3 GEMMs (gemm.hip, gemm16.hip, gemm_areg.hip): vector types, the bf16 hi/lo split, tile constants.
+// What the row GEMMs share beyond these - device pieces, split kernel, routing plan, launch helper - is in gemm_rows.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

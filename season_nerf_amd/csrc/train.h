@@ -22,7 +22,7 @@ struct GemmArgs {
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t st);
 
 // bf16x3 row-owner GEMM (forward and dgrad of the training engine): C (+)= alpha*(A Bt^T + bias); Bt pre-split into MFMA
-// fragment order by launch_split_weights (n_tiles x ksteps fragments of 2 KiB: bf16 hi, bf16 lo)
+// fragment order by split_weights_kernel (gemm_rows.h; n_tiles x ksteps fragments of 2 KiB: bf16 hi, bf16 lo)
 struct GemmX {
     const float* A;            // [M, lda] fp32, k contiguous
     // weights: either already split (frag, 32x32x16 fragment order: [n_tiles][ksteps][2][512] bf16) or raw fp32 (W != NULL): the
@@ -37,7 +37,7 @@ struct GemmX {
     const float* bias;
     double* stats;             // optional [2][N]: += sum_m (v - alpha*bias), += sum_m (v - alpha*bias)^2   (train-mode BatchNorm)
     int accumulate;
-    int reverse;               // row tiles from the last to the first (set by the launcher, see launch_gemm_rows16)
+    int reverse;               // row tiles from the last to the first (set by the launcher for gemm_rows16_kernel, see run_gemm_rows)
     const float* act_tab;      // optional activation-on-load table [a | b] x act_cols for the leading columns of A: sin(2 pi (a z + b))
     int act_cols;              // multiple of 8, <= K
     int tab_lds;               // set by the launcher: the table fits in LDS behind the weights
@@ -49,14 +49,10 @@ struct GemmX {
     const float *etab, *emu, *eistd;
     int a_padded;              // caller's promise: columns K .. 16*ksteps-1 of A exist (lda covers them) and hold zeros
 };
-hipError_t launch_split_weights(const float* W, int rows, int cols, bool transpose, uint16_t* frag, int n_tiles, int ksteps, hipStream_t st);
 int gemm_rows_group_tiles(int ksteps);      // 0 = K too large for the LDS-resident weight layout (caller falls back to fp32 MFMA)
-hipError_t launch_gemm_bf16x3(const GemmX& g, hipStream_t st);
-hipError_t launch_gemm_rows16(const GemmX& gx, int aol_mode, int act_mode, dim3 grid, size_t lds, hipStream_t st, int nt16 = 8);      // gemm16.hip
-// gemm_areg.hip: K = 256 / 512 with the activations resident in AGPRs and the weights streamed through the LDS ring (the reference's default width)
+hipError_t launch_gemm_bf16x3(const GemmX& g, hipStream_t st);      // routing, split and the launchers of the three translation units: gemm_rows.h
+// gemm_areg.hip: N = 256 / 512 with the accumulators in AGPRs, A and the weights streamed (the reference's default width): the shapes it takes
 bool gemm_areg_ok(const GemmX& g);
-hipError_t launch_areg_split_weights(const float* W, int rows, int cols, bool transpose, uint16_t* frag, int n_tiles, int ksteps, hipStream_t st);      // k-major stream
-hipError_t launch_gemm_areg(const GemmX& g, hipStream_t st);
 // bf16x3 weight gradient: dW[n_out, n_in] (ld ldw) += alpha * dZ[M, n_out]^T In[M, n_in]   (fp32 atomics over M-chunks)
 // optional BatchNorm backward folded into the weight-gradient kernel (dZ holds dL/dY on entry, dL/dZ on exit; needs n_in <= 256)
 struct WgradBN {

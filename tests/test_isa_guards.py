@@ -39,7 +39,7 @@ def test_full_tile_kernels_do_not_spill_pending_loads(tmp_path):
         if not m:
             i += 1
             continue
-        kname = "gemm_rows16_kernel" if "rows16" in lines[i] else "gemm_rows_full_kernel"      # (gemm_wreg_kernel loads by LDS-DMA: no register holds a load in flight)
+        kname = "gemm_rows16_kernel" if "rows16" in lines[i] else "gemm_rows_full_kernel"
         wait = "a8_wait" if kname == "gemm_rows_full_kernel" else "a16_wait"
         j = i
         while "s_endpgm" not in lines[j]:

@@ -4,7 +4,7 @@
 //   0: 16 B per lane, 1 KiB contiguous per wave instruction           (a plain copy)
 //   1: dword per lane in the 16x16 accumulator layout: 4 x 64 B row segments per instruction, only columns [128 c, 128 c + 128) of a
 //      row by one workgroup (the other half by another workgroup, later)   (gemm_rows16_kernel)
-//   2: as 1 but a workgroup writes whole rows (both column halves)     (gemm_wreg_kernel)
+//   2: as 1 but a workgroup writes whole rows (both column halves)     (one workgroup per whole row)
 // build: hipcc -O3 --offload-arch=gfx950 copy_patterns.hip -o copy_patterns
 #include <hip/hip_runtime.h>
 #include <stdio.h>
