@@ -105,6 +105,11 @@ int snerf_model_pack_host(snerf_model* m, int program, uint8_t* stream_out, size
  * Outputs: classes [G,C] softmax, sky_raw [G,3] pre-sigmoid, sky [G,3] sigmoid. */
 int snerf_group_forward(const snerf_model* m, int64_t n_groups, const float* d_time, const float* d_sun,
                         float* d_classes, float* d_sky_raw, float* d_sky, void* stream);
+/* Which kernel snerf_group_forward launches at widths 64 and 256, process-wide: 0 = one 32-ray tile per workgroup with every layer's
+ * output blocks split over the four waves (csrc/kernels_group.hip; the default), 1 = one wave per 32 rays (csrc/kernels.hip).  The two
+ * give bit-identical outputs; 1 exists for A/B timing and as the reference of the bit-identity test.  SNERF_GROUP_ONE_WAVE in the
+ * environment (read once) makes 1 the initial value.  Width 512 has one kernel and ignores the mode. */
+int snerf_set_group_kernel(int mode);
 
 /* ---- per-point field network on explicit points: device part of T_NeRF.forward / forward_seperate /
  * forward_full_eval / forward_Solar / forward_Classic_Sigma_Only (T_NeRF_net_v2.py:75-204).

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -353,6 +354,17 @@ static int group_forward_f32(const snerf_model* m, int64_t R, const float* d_tim
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "hipFreeAsync");
 }
 
+// 0: kernels_group.hip (output blocks split over the waves), 1: kernels.hip (one wave per 32 rays); SNERF_GROUP_ONE_WAVE=1: start at 1 (A/B)
+static std::atomic<int>& group_kernel_mode() {
+    static std::atomic<int> mode{getenv("SNERF_GROUP_ONE_WAVE") != nullptr ? 1 : 0};
+    return mode;
+}
+int snerf_set_group_kernel(int mode) {
+    if (mode != 0 && mode != 1) return fail(SNERF_E_INVALID, "snerf_set_group_kernel: mode must be 0 (split) or 1 (one wave)");
+    group_kernel_mode().store(mode);
+    return SNERF_OK;
+}
+
 int snerf_group_forward(const snerf_model* m, int64_t n_groups, const float* d_time, const float* d_sun,
                         float* d_classes, float* d_sky_raw, float* d_sky, void* stream) {
     int rc = check_ready(m);
@@ -377,6 +389,7 @@ int snerf_group_forward(const snerf_model* m, int64_t n_groups, const float* d_t
     a.g_sky_raw = d_sky_raw;
     a.g_sky = d_sky;
     hipError_t e = ks ? launch_mlp_ks_group(m->W, a, m->n_cu, (hipStream_t)stream)
+                : group_kernel_mode().load() == 0 ? launch_mlp_group_split(m->W, a, m->n_cu, (hipStream_t)stream)
                       : launch_mlp(PROG_GROUP, m->W, 0, false, a, m->n_cu, (hipStream_t)stream);      // bf16x3: its cost is 1/S of the field network's
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "group kernel launch");
 }
