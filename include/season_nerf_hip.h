@@ -216,6 +216,44 @@ int snerf_composite_sweep(int64_t n_rays, int n_samples, int n_classes, int n_ti
                           const float* d_adjust, const float* d_solar_vis, const float* d_sky, const float* d_class_vecs,
                           int flags, const snerf_sweep_out* out, void* stream);
 
+/* ---- sun walk: many sun directions (and, with the grid compositing below, many seasons) of one view from ONE field pass.
+ * The reference renders its season and shadow studies as a grid over view, sun direction and time and calls component_render_by_dir once
+ * per (view, sun, time) triple (T_NeRF_Eval_Utils/mg_Season_Eval.py:74-98, Full_Eval_Seasons).  Of the field network only fc_solar_1..4
+ * depend on the sun (G_NeRF.py:100-108): the walk runs the trunk, the density / colour head and the colour-adjust branch once per sample and
+ * the solar branch once per sun direction.  Exact solar visibility is not part of the walk (every sun direction needs its own secondary
+ * rays: snerf_field_ray_visibility), and the int8-digit and one-term bf16 kernel families do not have it.
+ *
+ * The walk stream of n_suns directions, on the host (no GPU): the field program's stream (program 0 of snerf_model_pack_host; program 3,
+ * the K-split order, at width 512) rearranged by whole 16 KiB chunks into [fc1 .. head] [fc_solar_1..4] x n_suns [adjust branch] - the
+ * order the walk kernels' weight ring consumes.  stream_out may be NULL to query the size.  SNERF_E_INVALID unless 1 <= n_suns <= 32. */
+int snerf_model_pack_sun_walk_host(snerf_model* m, int n_suns, uint8_t* stream_out, size_t* stream_bytes);
+/* The walk on rays (the device side of `_internal_render`, mg_Img_Eval.py:17-56, for n_suns sun directions of one view): points as in
+ * snerf_field_forward_rays, ONE class vector d_classes [C] (may be NULL) for the whole launch, d_suns [n_suns,3].  Outputs as
+ * snerf_field_out (all optional), stored once per point - except out->d_solar_vis, which is [n_suns, R*S]: row j is what
+ * snerf_field_forward_rays gives for sun j, bit for bit.  SNERF_E_INVALID unless the model's resolved precision is SNERF_PREC_BF16X3
+ * (width 64, 256 or 512) and 1 <= n_suns <= 32.  The device copy of the walk stream is built at the first call per n_suns and kept
+ * (the most recent one) until the model is destroyed. */
+int snerf_field_sun_walk_rays(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot,
+                              const float* d_tvals, int n_suns, const float* d_suns, const float* d_classes,
+                              const snerf_field_out* out, void* stream);
+/* Grid compositing of a walk: `Season_Adj_Img * Shadow_Adjust` of Full_Eval_Seasons (mg_Season_Eval.py:74-98; mg_Img_Eval.py:192-228 per
+ * (sun, time)) for M sun directions x T class vectors from the per-sample tensors of one walk.  As snerf_composite_sweep (same PS, same
+ * flags, top / bot / tvals or explicit d_deltas), with d_solar_vis [M,R,S] and d_sky [M,3]:
+ *   season[k,r] = sum_s PS sigmoid(col_raw + class_k @ adjust),  raw_shadow[j,r] = sum_s PS solar_vis[j,r,s],
+ *   shadow_adjust[j,r] = m + (1 - m) sky_j with m = sigmoid(30 (raw_shadow[j,r] - 0.2)),  shaded[j,k,r] = season[k,r] * shadow_adjust[j,r].
+ * All outputs optional.  SNERF_E_INVALID when a ray's PS and shadow factors (4 (S + 3 M) floats per workgroup) exceed 64 KiB of LDS. */
+typedef struct snerf_sun_walk_out {
+    float* d_shaded;         /* [M,T,R,3] */
+    float* d_season;         /* [T,R,3] */
+    float* d_base;           /* [R,3] sum_s PS sigmoid(col_raw) */
+    float* d_raw_shadow;     /* [M,R] */
+    float* d_shadow_adjust;  /* [M,R,3] */
+} snerf_sun_walk_out;
+int snerf_composite_sun_walk(int64_t n_rays, int n_samples, int n_classes, int n_times, int n_suns, const float* d_top,
+                             const float* d_bot, const float* d_tvals, const float* d_deltas, const float* d_rho, const float* d_col_raw,
+                             const float* d_adjust, const float* d_solar_vis, const float* d_sky, const float* d_class_vecs,
+                             int flags, const snerf_sun_walk_out* out, void* stream);
+
 /* ---- training engine: the device side of Net_tool.train_step (mg_run_NeRF.py:288-326) = All_in_One_Eval.get_loss
  * (Eval_Tools_2.py:340-459) forward passes in .train() mode, backward, Adam.  Layer-wise, fp32 storage, 3-term split bf16 MFMA
  * GEMMs (exact-fp32 MFMA under SNERF_TRAIN_GEMM=fp32), batch-statistics BatchNorm1d (momentum 0.01, misc.py:170) with running-stat EMA, activations stashed in HBM.

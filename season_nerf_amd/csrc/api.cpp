@@ -56,6 +56,9 @@ struct snerf_model {
     float* d_bias_ks = nullptr;
     uint8_t* d_stream_ksg = nullptr;
     float* d_bias_ksg = nullptr;
+    // sun walk: device copy of the walk stream (program.h sun_walk_*) of the most recent n_suns, built at the first snerf_field_sun_walk_rays that asks for it
+    mutable uint8_t* d_walk = nullptr;
+    mutable int walk_suns = 0;
     int n_cu = 0;
 };
 
@@ -299,6 +302,7 @@ void snerf_model_destroy(snerf_model* m) {
     if (m->d_stream_ksg) (void)hipFree(m->d_stream_ksg);
     if (m->d_bias_ksg) (void)hipFree(m->d_bias_ksg);
     if (m->d_group_f32) (void)hipFree(m->d_group_f32);
+    if (m->d_walk) (void)hipFree(m->d_walk);
     delete m;
 }
 
@@ -472,6 +476,86 @@ int snerf_field_forward_rays(const snerf_model* m, int variant, int64_t n_rays, 
     return field_launch(m, variant, a, out, stream);
 }
 
+int snerf_model_pack_sun_walk_host(snerf_model* m, int n_suns, uint8_t* stream_out, size_t* stream_bytes) {
+    if (!m) return fail(SNERF_E_INVALID, "NULL model");
+    if (n_suns < 1 || n_suns > kMaxWalkSuns) return fail(SNERF_E_INVALID, "snerf_model_pack_sun_walk_host: n_suns must be in [1," + std::to_string(kMaxWalkSuns) + "]");
+    int rc = pack_both(m, true);
+    if (rc) return rc;
+    const bool ks = ks_width(m->W);
+    const Packed& P = ks ? m->host_ks : m->host[PROG_FIELD];
+    const int chunks = sun_walk_chunks(m->W, m->C, n_suns, ks);
+    if (P.stream.size() != (size_t)field_chunk_start(m->W, m->C, F_NUM, ks) * kChunkBytes) return fail(SNERF_E_STATE, "snerf_model_pack_sun_walk_host: packed stream has an unexpected size");
+    if (stream_bytes) *stream_bytes = (size_t)chunks * kChunkBytes;
+    if (stream_out)
+        for (int c = 0; c < chunks; ++c)
+            std::memcpy(stream_out + (size_t)c * kChunkBytes, P.stream.data() + (size_t)sun_walk_source_chunk(m->W, m->C, n_suns, ks, c) * kChunkBytes, kChunkBytes);
+    return SNERF_OK;
+}
+
+// device copy of the walk stream: whole layers' chunks out of the packed host stream, uploaded as snerf_model_finalize uploads the stream itself
+// (synchronous copies: nothing here is stream-ordered, so nothing of it can end up in a captured graph)
+static int walk_stream(const snerf_model* m, int n_suns) {
+    if (m->d_walk && m->walk_suns == n_suns) return SNERF_OK;
+    const bool ks = ks_width(m->W);
+    const uint8_t* src = (ks ? m->host_ks : m->host[PROG_FIELD]).stream.data();
+    hipError_t e;
+    if (m->d_walk) {                        // another n_suns: hipFree waits for the launches that still read the old copy
+        if ((e = hipFree(m->d_walk)) != hipSuccess) return fail_hip(e, "hipFree");
+        m->d_walk = nullptr;
+        m->walk_suns = 0;
+    }
+    const size_t a = (size_t)field_chunk_start(m->W, m->C, F_S1, ks) * kChunkBytes, b = (size_t)field_chunk_start(m->W, m->C, F_A1, ks) * kChunkBytes,
+                 end = (size_t)field_chunk_start(m->W, m->C, F_NUM, ks) * kChunkBytes;
+    if ((ks ? m->host_ks : m->host[PROG_FIELD]).stream.size() != end) return fail(SNERF_E_STATE, "sun walk: the packed field stream has an unexpected size");
+    if ((e = hipMalloc((void**)&m->d_walk, (size_t)sun_walk_chunks(m->W, m->C, n_suns, ks) * kChunkBytes)) != hipSuccess) return fail_hip(e, "hipMalloc (walk stream)");
+    e = hipMemcpy(m->d_walk, src, a, hipMemcpyHostToDevice);
+    for (int j = 0; j < n_suns && e == hipSuccess; ++j) e = hipMemcpy(m->d_walk + a + (size_t)j * (b - a), src + a, b - a, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->d_walk + a + (size_t)n_suns * (b - a), src + b, end - b, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(m->d_walk);
+        m->d_walk = nullptr;
+        return fail_hip(e, "hipMemcpy (walk stream)");
+    }
+    m->walk_suns = n_suns;
+    return SNERF_OK;
+}
+
+int snerf_field_sun_walk_rays(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals,
+                              int n_suns, const float* d_suns, const float* d_classes, const snerf_field_out* out, void* stream) {
+    int rc = check_ready(m);
+    if (rc) return rc;
+    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
+        return fail(SNERF_E_INVALID, "snerf_field_sun_walk_rays: the sun walk exists for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
+    if (n_suns < 1 || n_suns > kMaxWalkSuns) return fail(SNERF_E_INVALID, "snerf_field_sun_walk_rays: n_suns must be in [1," + std::to_string(kMaxWalkSuns) + "]");
+    if (n_rays < 0 || n_samples < 1 || !d_top || !d_bot || !d_tvals || !d_suns) return fail(SNERF_E_INVALID, "snerf_field_sun_walk_rays: bad argument");
+    if (n_rays == 0) return SNERF_OK;
+    rc = walk_stream(m, n_suns);
+    if (rc) return rc;
+    const bool ks = ks_width(m->W);
+    SunWalkArgs a{};
+    a.n_suns = n_suns;
+    a.m.stream = m->d_walk;
+    a.m.stream_bytes = (uint32_t)sun_walk_chunks(m->W, m->C, n_suns, ks) * kChunkBytes;
+    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
+    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
+    a.m.n = n_rays * n_samples;
+    a.m.n_classes = m->C;
+    a.m.top = d_top;
+    a.m.bot = d_bot;
+    a.m.tvals = d_tvals;
+    a.m.n_samples = n_samples;
+    a.m.group_size = a.m.n;
+    a.m.sun = d_suns;
+    a.m.classes = d_classes;
+    if (out) {
+        a.m.out.rho = out->d_rho; a.m.out.solar_vis = out->d_solar_vis; a.m.out.col_raw = out->d_col_raw;
+        a.m.out.adjust = out->d_adjust; a.m.out.col = out->d_col; a.m.out.adjust_col = out->d_adjust_col;
+        a.m.out.points = out->d_points;
+    }
+    hipError_t e = launch_sun_walk(m->W, a, m->n_cu, (hipStream_t)stream);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "sun walk kernel launch");
+}
+
 int snerf_field_ray_visibility(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot,
                                const float* d_tvals, int flags, float* d_vis, void* stream) {
     int rc = check_ready(m);
@@ -584,6 +668,25 @@ int snerf_composite_sweep(int64_t n_rays, int n_samples, int n_classes, int n_ti
     a.raw_shadow = out->d_raw_shadow;
     hipError_t e = launch_sweep(a, (hipStream_t)stream);
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "sweep kernel launch");
+}
+
+int snerf_composite_sun_walk(int64_t n_rays, int n_samples, int n_classes, int n_times, int n_suns, const float* d_top, const float* d_bot,
+                             const float* d_tvals, const float* d_deltas, const float* d_rho, const float* d_col_raw, const float* d_adjust,
+                             const float* d_solar_vis, const float* d_sky, const float* d_class_vecs, int flags, const snerf_sun_walk_out* out, void* stream) {
+    if (n_rays < 0 || n_samples < 1 || n_times < 0 || n_suns < 0 || n_classes < 1 || n_classes > kMaxClasses || !out)
+        return fail(SNERF_E_INVALID, "snerf_composite_sun_walk: bad argument");
+    if (n_rays == 0 || (n_times == 0 && n_suns == 0)) return SNERF_OK;
+    if ((!d_deltas && (!d_top || !d_bot || !d_tvals)) || !d_rho || !d_col_raw || !d_adjust || (n_suns && (!d_solar_vis || !d_sky)) || (n_times && !d_class_vecs))
+        return fail(SNERF_E_INVALID, "snerf_composite_sun_walk: bad argument");
+    if (sun_walk_composite_lds_bytes(n_samples, n_suns) > 64 * 1024)
+        return fail(SNERF_E_INVALID, "snerf_composite_sun_walk: n_samples + 3 n_suns must not exceed 4096 (a ray's weights and shadow factors wait in LDS)");
+    SunWalkCompArgs a{};
+    a.n_rays = n_rays; a.n_samples = n_samples; a.n_classes = n_classes; a.n_times = n_times; a.n_suns = n_suns; a.flags = flags;
+    a.top = d_top; a.bot = d_bot; a.tvals = d_tvals; a.deltas = d_deltas;
+    a.rho = d_rho; a.col_raw = d_col_raw; a.adjust = d_adjust; a.solar_vis = d_solar_vis; a.sky = d_sky; a.class_vecs = d_class_vecs;
+    a.shaded = out->d_shaded; a.season = out->d_season; a.base = out->d_base; a.raw_shadow = out->d_raw_shadow; a.shadow_adjust = out->d_shadow_adjust;
+    hipError_t e = launch_sun_walk_composite(a, (hipStream_t)stream);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "sun walk compositing kernel launch");
 }
 
 int snerf_rays_from_camera(const double* P_3x4, int rows, int cols, int downscale, float* d_rows, uint8_t* d_valid, void* stream) {

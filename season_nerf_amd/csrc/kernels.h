@@ -46,6 +46,15 @@ struct MlpArgs {
     int ray_flags;             // bit 1: a sample outside [-1,1]^3 contributes nothing (mg_Img_Eval.py:42,65-66); bit 2: no early-out (A/B); bit 3: passes from the sun side inwards (the order before round 6's reversal, A/B)
 };
 
+// Sun walk (sun_walk_kernel / sun_walk_ks_kernel): the variant-0 layer walk with fc_solar_1..4 repeated for n_suns sun directions.  Wraps MlpArgs
+// so that the argument layout of the existing kernels stays as it is.  m.sun is [n_suns,3], m.out.solar_vis [n_suns, m.n]; m.stream is the walk
+// stream (program.h sun_walk_*) and m.stream_bytes its whole length.
+constexpr int kMaxWalkSuns = 32;
+struct SunWalkArgs {
+    MlpArgs m;
+    int n_suns;
+};
+
 struct CompOutDev {
     float *rgb, *albedo, *pv, *pe, *ps, *delta, *shadow, *acc, *surf_loc, *surf_dist;
 };
@@ -100,11 +109,32 @@ struct SweepArgs {
     float *base, *shadow_adjust, *raw_shadow;   // [R,3], [R,3], [R]
 };
 hipError_t launch_sweep(const SweepArgs& a, hipStream_t st);
+// grid compositing of a sun walk (sun_walk_composite_kernel): the sweep's season images times the shadow factors of n_suns sun directions
+struct SunWalkCompArgs {
+    int64_t n_rays;
+    int n_samples, n_classes, n_times, n_suns, flags;
+    const float *top, *bot, *tvals;
+    const float* deltas;       // optional [R,S], as SweepArgs
+    const float *rho, *col_raw, *adjust;
+    const float* solar_vis;    // [M,R,S]
+    const float* sky;          // [M,3]
+    const float* class_vecs;   // [T,C]
+    float* shaded;             // [M,T,R,3]
+    float* season;             // [T,R,3]
+    float* base;               // [R,3]
+    float* raw_shadow;         // [M,R]
+    float* shadow_adjust;      // [M,R,3]
+};
+int sun_walk_composite_lds_bytes(int n_samples, int n_suns);
+hipError_t launch_sun_walk_composite(const SunWalkCompArgs& a, hipStream_t st);
 // workgroup tiles of a fused field launch: `rays` rays per tile in VARIANT 3 (ray visibility), `pts` points per tile otherwise
 __host__ __device__ inline int64_t field_tiles(int64_t n, int variant, int pts, int rays) { return variant == 3 ? (n + rays - 1) / rays : (n + pts - 1) / pts; }
 // persistent launch of a fused kernel: min(n_tiles, n_cu) workgroups (at least one) of `block` threads with `lds_bytes` of dynamic LDS (kernels.hip)
 hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);                          // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
+hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)
 int field_variant_chunks_i8(int W, int C, int variant);
 hipError_t launch_mlp_i8x2(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8x2.hip (W <= 256)

@@ -246,6 +246,102 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
 }
 
 // =====================================================================================================
+// Sun walk: the VARIANT 0 layer walk of mlp_kernel with fc_solar_1..4 (G_NeRF.py:100-108) run for n_suns sun directions.  The trunk, the density /
+// colour head and the colour-adjust branch do not depend on the sun: one pass feeds every sun direction of a season / shadow study of one view
+// (mg_Season_Eval.py:74-98).  The weights come from the walk stream (program.h sun_walk_*): the ring cannot branch, so the solar layers' chunks
+// are repeated in the stream.  x1f stays live as long as in VARIANT 0 (through the solar layers, last read by F_A1).  The sun directions are staged
+// in LDS behind the vote words: a global load inside the chain would make hipcc drain the LDS-DMA pipeline with vmcnt(0) (field_tile_inputs).
+// Everything but solar_vis is stored once per point; solar_vis of sun j goes to out.solar_vis[j * n + point].
+__host__ __device__ constexpr int sun_walk_lds_extra() { return kMaxWalkSuns * 3 * 4; }
+
+// The density store of the walk's output block, as a call.  Inlined, the log1pf of softplus_f leaves a packed-multiply operand pair with one constant half,
+// which is hoisted out of the persistent tile loop; the trunk of W = 256 uses all 256 VGPRs, so a VGPR-only value that lives across the loop is spilled
+// (to AGPRs: .vgpr_spill_count 4, as mlp_kernel<PROG_FIELD, 256, 0> has).  Behind a call the constant lives in the callee: no spill, no scratch, and the
+// same arithmetic (the callee is softplus_f).  Once per tile and lane, behind the last layer.
+__device__ __attribute__((noinline)) void store_softplus(float* p, float x) { *p = softplus_f(x); }
+
+template <int W>
+__global__ __launch_bounds__(256, 1) void sun_walk_kernel(const SunWalkArgs SA) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MlpArgs& A = SA.m;
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    lds_char* lds = (lds_char*)smem;
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
+    __attribute__((address_space(3))) float* sun_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + A.bias_floats * 4 + kVoteBytes);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5;
+    const int C = A.n_classes;
+    const int n_suns = SA.n_suns;
+
+    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
+    for (int i = threadIdx.x; i < 3 * n_suns; i += 256) sun_lds[i] = A.sun[i];
+
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
+    __syncthreads();
+
+    const int64_t n_tiles = field_tiles(A.n, 0, TILE_PTS, 4);
+    snerf_field_out_dev once = A.out;      // what is stored once per point (the density through store_softplus)
+    once.solar_vis = nullptr;
+    once.rho = nullptr;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t n = tile * TILE_PTS + wave * 32 + (lane & 31);
+        const bool valid = n < A.n;
+        const int64_t nc = valid ? n : A.n - 1;
+        float x0, x1, x2;
+        field_point(A, nc, x0, x1, x2);
+        float u0, u1, u2, pcls[C_MAX];
+        field_tile_inputs<0>(A, 0, u0, u1, u2, pcls);      // one class vector for the whole launch; the sun directions come from LDS
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KW = W / 16, KW2 = W2 / 16;
+        Frag hA[KW], hB[KW];
+        f32x16 raw;
+#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
+    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
+        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
+        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
+        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        Frag x1f[KW2];
+        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
+        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+        const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
+        for (int j = 0; j < n_suns; ++j) {
+            const float s0 = sun_lds[3 * j], s1 = sun_lds[3 * j + 1], s2 = sun_lds[3 * j + 2];      // wave-uniform
+            Frag ps[PESUN_KS];
+            make_pe_sun(s0, s1, s2, h, ps);
+            Frag sA[KW2], sB[KW2];
+            LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
+            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
+            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
+            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
+            if (h == 0 && valid && A.out.solar_vis) A.out.solar_vis[(int64_t)j * A.n + n] = sigmoid_f(raw[0]);
+        }
+        LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr);
+        LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw);
+        float adj[3 * C_MAX];
+#pragma unroll
+        for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
+#undef LAYER
+        if (h == 0 && valid) {
+            if (A.out.rho) store_softplus(A.out.rho + n, rho_raw);
+            store_field_outputs<0>(once, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, 0.f, adj, pcls);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+// =====================================================================================================
 // compositing: one wavefront per ray (Eval_Tools_2.py:13-16,187-215; mg_run_NeRF.py:188-189)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -518,6 +614,142 @@ hipError_t launch_sweep(const SweepArgs& a, hipStream_t st) {
 }
 
 // =====================================================================================================
+// Grid compositing of a sun walk (mg_Season_Eval.py:74-98 over mg_Img_Eval.py:192-228): the per-sample tensors of ONE field pass and the solar
+// visibility of M sun directions -> every (sun j, class vector k) image of a view,
+//   shaded[j,k,r] = season[k,r] * (m_j + (1 - m_j) sky_j),  season[k,r] = sum_s PS sigmoid(col_raw + class_k @ adjust),
+//   m_j = sigmoid(30 (raw_shadow[j,r] - 0.2)),  raw_shadow[j,r] = sum_s PS solar_vis[j,r,s].
+// One wavefront per ray.  PS is formed once per ray (the scan of composite_kernel) and kept in LDS, S floats per wave; then passes of SW_M_CHUNK sun
+// directions and of SW_T_CHUNK class vectors over the per-sample arrays (accumulators in registers, as sweep_kernel's T_CHUNK); the M shadow factors
+// of the ray wait in LDS (3 M floats per wave) for the season passes, whose lanes then write the M x T products.
+constexpr int SW_M_CHUNK = 8, SW_T_CHUNK = 6;
+__global__ __launch_bounds__(256) void sun_walk_composite_kernel(const SunWalkCompArgs A) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+    if (r >= A.n_rays) return;       // (no workgroup barrier below: a wave's LDS is its own)
+    const int S = A.n_samples, C = A.n_classes, M = A.n_suns, T = A.n_times;
+    float* ps_l = (float*)smem + (size_t)wv * (S + 3 * M);
+    float* fac_l = ps_l + S;
+    const bool explicit_delta = A.deltas != nullptr;
+    float tx = 0.f, ty = 0.f, tz = 0.f, bx = 0.f, by = 0.f, bz = 0.f, delta_ray = 0.f;
+    if (!explicit_delta) {
+        tx = A.top[r * 3]; ty = A.top[r * 3 + 1]; tz = A.top[r * 3 + 2];
+        bx = A.bot[r * 3]; by = A.bot[r * 3 + 1]; bz = A.bot[r * 3 + 2];
+        const float dx = tx - bx, dy = ty - by, dz = tz - bz;
+        delta_ray = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)S);
+    }
+    const bool zero_oob = (A.flags & 2) && !explicit_delta;
+    // ---- PS of the ray
+    float carry = 0.f;
+    for (int base = 0; base < S; base += 64) {
+        const int s = base + lane;
+        const bool in = s < S;
+        const int64_t idx = r * S + (in ? s : S - 1);
+        float delta = delta_ray;
+        if (explicit_delta) {
+            delta = A.deltas[idx];
+        } else if (zero_oob) {
+            const float t = A.tvals[in ? s : S - 1], omt = __fsub_rn(1.f, t);
+            const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
+            const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
+            const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
+            if (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f) delta = 0.f;
+        }
+        const float y = in ? A.rho[idx] * delta : 0.f;
+        const float incl = wave_incl_scan(y, lane);
+        const float excl = carry + wave_excl_of(incl, lane);
+        carry += __shfl(incl, 63, 64);
+        if (in) ps_l[s] = expf(-excl) * (1.f - expf(-y));
+    }
+    // ---- shadow factors of the M sun directions
+    for (int j0 = 0; j0 < M; j0 += SW_M_CHUNK) {
+        float acc[SW_M_CHUNK];
+#pragma unroll
+        for (int q = 0; q < SW_M_CHUNK; ++q) acc[q] = 0.f;
+        for (int s = lane; s < S; s += 64) {
+            const float ps = ps_l[s];
+#pragma unroll
+            for (int q = 0; q < SW_M_CHUNK; ++q)
+                if (j0 + q < M) acc[q] += ps * A.solar_vis[((int64_t)(j0 + q) * A.n_rays + r) * S + s];
+        }
+#pragma unroll
+        for (int q = 0; q < SW_M_CHUNK; ++q) {
+            const float raw = wave_sum(acc[q]);
+            const int j = j0 + q;
+            if (lane == 0 && j < M) {
+                const float mask = sigmoid_f((raw - 0.2f) * 30.f);
+                const int64_t o = (int64_t)j * A.n_rays + r;
+                if (A.raw_shadow) A.raw_shadow[o] = raw;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float f = mask + (1.f - mask) * A.sky[j * 3 + k];
+                    fac_l[j * 3 + k] = f;
+                    if (A.shadow_adjust) A.shadow_adjust[o * 3 + k] = f;
+                }
+            }
+        }
+    }
+    // ---- season images of the T class vectors, and their products with the shadow factors
+    for (int t0 = 0; t0 < T; t0 += SW_T_CHUNK) {
+        float cw[SW_T_CHUNK][kMaxClasses];
+#pragma unroll
+        for (int t = 0; t < SW_T_CHUNK; ++t)
+#pragma unroll
+            for (int c = 0; c < kMaxClasses; ++c) cw[t][c] = (t0 + t < T && c < C) ? A.class_vecs[(t0 + t) * C + c] : 0.f;
+        float acc[SW_T_CHUNK][3], b0 = 0.f, b1 = 0.f, b2 = 0.f;
+#pragma unroll
+        for (int t = 0; t < SW_T_CHUNK; ++t) acc[t][0] = acc[t][1] = acc[t][2] = 0.f;
+        for (int s = lane; s < S; s += 64) {
+            const int64_t idx = r * S + s;
+            const float ps = ps_l[s];
+            const float k0 = A.col_raw[idx * 3], k1 = A.col_raw[idx * 3 + 1], k2 = A.col_raw[idx * 3 + 2];
+            float ad[kMaxClasses][3];
+#pragma unroll
+            for (int c = 0; c < kMaxClasses; ++c)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) ad[c][k] = c < C ? A.adjust[(idx * C + c) * 3 + k] : 0.f;
+            if (t0 == 0) { b0 += ps * sigmoid_fast(k0); b1 += ps * sigmoid_fast(k1); b2 += ps * sigmoid_fast(k2); }
+#pragma unroll
+            for (int t = 0; t < SW_T_CHUNK; ++t) {
+                float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+#pragma unroll
+                for (int c = 0; c < kMaxClasses; ++c) { m0 += cw[t][c] * ad[c][0]; m1 += cw[t][c] * ad[c][1]; m2 += cw[t][c] * ad[c][2]; }
+                acc[t][0] += ps * sigmoid_fast(k0 + m0); acc[t][1] += ps * sigmoid_fast(k1 + m1); acc[t][2] += ps * sigmoid_fast(k2 + m2);
+            }
+        }
+        if (t0 == 0 && A.base) {
+            b0 = wave_sum(b0); b1 = wave_sum(b1); b2 = wave_sum(b2);
+            if (lane == 0) { A.base[r * 3] = b0; A.base[r * 3 + 1] = b1; A.base[r * 3 + 2] = b2; }
+        }
+#pragma unroll
+        for (int t = 0; t < SW_T_CHUNK; ++t) {
+            const float v0 = wave_sum(acc[t][0]), v1 = wave_sum(acc[t][1]), v2 = wave_sum(acc[t][2]);      // in every lane
+            const int k = t0 + t;
+            if (k >= T) continue;
+            if (lane == 0 && A.season) {
+                const int64_t o = ((int64_t)k * A.n_rays + r) * 3;
+                A.season[o] = v0; A.season[o + 1] = v1; A.season[o + 2] = v2;
+            }
+            if (A.shaded) {
+                for (int j = lane; j < M; j += 64) {
+                    const int64_t o = (((int64_t)j * T + k) * A.n_rays + r) * 3;
+                    A.shaded[o] = v0 * fac_l[j * 3]; A.shaded[o + 1] = v1 * fac_l[j * 3 + 1]; A.shaded[o + 2] = v2 * fac_l[j * 3 + 2];
+                }
+            }
+        }
+    }
+}
+
+int sun_walk_composite_lds_bytes(int n_samples, int n_suns) { return 4 * (n_samples + 3 * n_suns) * 4; }
+hipError_t launch_sun_walk_composite(const SunWalkCompArgs& a, hipStream_t st) {
+    const int lds_bytes = sun_walk_composite_lds_bytes(a.n_samples, a.n_suns);
+    if (lds_bytes > 64 * 1024) return hipErrorInvalidValue;
+    const int grid = (int)((a.n_rays + 3) / 4);
+    hipLaunchKernelGGL(sun_walk_composite_kernel, dim3(grid), dim3(256), lds_bytes, st, a);
+    return hipGetLastError();
+}
+
+// =====================================================================================================
 // ray table from a 3x4 projective camera (pre_NeRF/P_Img.py:133-147 `invert_P`, mg_Pt_holder.py:178-194): for every
 // pixel (i*DS, j*DS) of the down-scaled grid, the cube xy where its ray crosses z = +1 (Top) and z = -1 (Bot): a 2x2
 // solve in fp64 (as the reference), results rounded to fp32 rows [Img_Pt 2 | Top 3 | Bot 3 | View 3] + validity.
@@ -631,13 +863,30 @@ hipError_t launch_ray_grid(const RayGridArgs& a, hipStream_t st) {
 
 // =====================================================================================================
 // launchers
-hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st) {
+template <class Args>
+static hipError_t launch_fused_t(void (*kernel)(Args), int64_t n_tiles, int block, int lds_bytes, const Args& a, int n_cu, hipStream_t st) {
     int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
     if (grid < 1) grid = 1;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, st, a);
     return hipGetLastError();
+}
+hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st) {
+    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
+}
+hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st) {
+    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
+}
+
+hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st) {
+    if (a.n_suns < 1 || a.n_suns > kMaxWalkSuns) return hipErrorInvalidValue;      // the kernels stage 3 * kMaxWalkSuns floats in LDS
+    if (W == 512) return launch_sun_walk_ks(W, a, n_cu, st);
+    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats) + sun_walk_lds_extra();
+    const int64_t tiles = field_tiles(a.m.n, 0, TILE_PTS, 4);
+    if (W == 64) return launch_fused(sun_walk_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
+    if (W == 256) return launch_fused(sun_walk_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
+    return hipErrorInvalidValue;
 }
 
 int mlp_lds_bytes(int bias_floats) { return RING_BYTES + bias_floats * 4 + kVoteBytes; }

@@ -14,6 +14,14 @@
 // first layer needs no exchange at all.  The raw heads (one block) are symmetric: both waves add the partner's half and both hold the result.
 // Epilogue work (sin + split) exists in every second phase only: per MFMA half the vector work of the W = 256 kernel.
 //
+// The sun walk (sun_walk_ks_kernel: the solar layers repeated for n_suns sun directions) adds one layer adjacency, F_S4 -> F_S1: a raw head
+// followed by a hidden layer, as F_HEAD -> F_S1 and F_S4 -> F_A1 already are, and ordered the same way.  A head ends with its own exchange:
+// xbuf_write, s_waitcnt lgkmcnt(0) + s_barrier, xbuf_read.  The hidden layer that follows writes the exchange buffer first in k-step 1 of its
+// first O phase, i.e. behind a whole F phase of KSH >= 8 k-steps = two ring steps, each with a workgroup barrier the partner passes only after
+// it has issued the head's xbuf_read (LDS operations of a wave complete in order, and the ring's fragment reads issued behind it are waited
+// for before the first MFMA of that F phase); the first read of that buffer is in F phase 1, after the write, as inside any layer.  Nothing in
+// this argument depends on which hidden layer follows, so it holds for F_S1 after F_S4 as it does for F_A1 after F_S4.
+//
 // Weight stream (pack.cpp pack_program_ks): the pairs of the canonical bf16 stream in the order each wave consumes them, a 16 KiB chunk =
 // 4 pairs for parity 0 | 4 pairs for parity 1; every chunk is read by two waves (one per pair), i.e. the L2 -> LDS stream per point is twice
 // the W = 256 kernel's (64 points share a chunk, not 128) - the price of the width; the ring (7 slots, 5 in flight) is the same, its refill spread
@@ -397,6 +405,108 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+// Sun walk at this width: the VARIANT 0 walk of mlp_ks_kernel with fc_solar_1..4 run for n_suns sun directions from the walk stream (kernels.hip
+// sun_walk_kernel; the new layer adjacency is argued in the head comment).  The sun directions wait in LDS behind the vote words.
+template <int W>
+__global__ __launch_bounds__(256, 1) void sun_walk_ks_kernel(const SunWalkArgs SA) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MlpArgs& A = SA.m;
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    lds_char* lds = (lds_char*)smem;
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
+    __attribute__((address_space(3))) float* sun_lds = (__attribute__((address_space(3))) float*)(lds + ks_lds_bytes(A.bias_floats));
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pair = wave >> 1, par = wave & 1;
+    const int h = lane >> 5;
+    const int C = A.n_classes;
+    const int n_suns = SA.n_suns;
+
+    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
+    for (int i = threadIdx.x; i < 3 * n_suns; i += 256) sun_lds[i] = A.sun[i];
+    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
+    KsCtx cx;
+    cx.lds = lds;
+    cx.par_off = par * KS_PAR_BYTES;
+    {
+        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
+        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
+        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
+    }
+
+    Pend pd;
+    pd.goff = 0;
+    pd.wr = 0;
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
+    __syncthreads();
+
+    const int64_t n_tiles = field_tiles(A.n, 0, KS_TILE_PTS, 2);
+    snerf_field_out_dev once = A.out;      // what is stored once per point
+    once.solar_vis = nullptr;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t n = tile * KS_TILE_PTS + pair * 32 + (lane & 31);
+        const bool valid = n < A.n;
+        const int64_t nc = valid ? n : A.n - 1;
+        float x0, x1, x2;
+        field_point(A, nc, x0, x1, x2);
+        float u0, u1, u2, pcls[C_MAX];
+        field_tile_inputs<0>(A, 0, u0, u1, u2, pcls);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KH = W / 32, KH2 = W2 / 32;
+        constexpr int NBW = W / 64, NBW2 = W2 / 64;
+        Frag hA[KH], hB[KH];
+#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
+#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
+#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
+        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
+        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
+        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
+        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
+        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
+        Frag x1f[KH2];
+        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
+        f32x16 raw = HEADL(F_HEAD, KH2, x1f);
+        const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
+        for (int j = 0; j < n_suns; ++j) {
+            const float s0 = sun_lds[3 * j], s1 = sun_lds[3 * j + 1], s2 = sun_lds[3 * j + 2];      // wave-uniform
+            Frag ps[PESUN_KS];
+            make_pe_sun(s0, s1, s2, h, ps);
+            Frag sA[KH2], sB[KH2];
+            LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);
+            LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);
+            LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);
+            raw = HEADL(F_S4, KH2, sA);
+            if (par == 0 && h == 0 && valid && A.out.solar_vis) A.out.solar_vis[(int64_t)j * A.n + n] = sigmoid_f(raw[0]);
+        }
+        LAYER(F_A1, NBW, KH2, 0, x1f, nullptr, hA);
+        LAYER(F_A2, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_A3, NBW, KH, 0, hB, nullptr, hA);
+        raw = HEADL(F_AC, KH, hA);
+        float adj[3 * C_MAX];
+#pragma unroll
+        for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
+#undef LAYER
+#undef HEADL
+#undef OWNB
+        if (par == 0 && h == 0 && valid) store_field_outputs<0>(once, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, 0.f, adj, pcls);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t st) {
+    if (W != 512 || a.n_suns < 1 || a.n_suns > kMaxWalkSuns) return hipErrorInvalidValue;
+    const int lds_bytes = ks_lds_bytes(a.m.bias_floats) + kMaxWalkSuns * 3 * 4;
+    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    return launch_fused(sun_walk_ks_kernel<512>, field_tiles(a.m.n, 0, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
 }
 
 // The per-ray networks at this width (time -> class softmax, T_NeRF_net_v2.py:77-78,160-163; sun -> sky colour, G_NeRF.py:110-111) on the same wave-pair

@@ -16,6 +16,10 @@
 //        -> (rgb[R,3], depth[R,2] = (surface distance, accumulated weight), albedo[R,3], per_sample[])  All_in_One_Eval.eval
 //   season_nerf::composite(top, bot, tvals, rho, col, solar_vis, sky, flags, rho_prior?, trust) -> Tensor[10]    get_PV + shading
 //   season_nerf::composite_sweep(...) -> Tensor[6]                                                    mg_Img_Eval t-step sweep
+//   season_nerf::sun_walk_fwd(model, top[R,3], bot[R,3], tvals[S], suns[M,3], classes[C]?)             one field pass, M sun directions
+//        -> [rho[R,S,1], solar_vis[M,R,S,1], col_raw[R,S,3], adjust[R,S,C,3], points[R,S,3]]             (mg_Season_Eval.py:74-98; `model` = Model.handle())
+//   season_nerf::composite_sun_walk(top, bot, tvals, rho, col_raw, adjust, solar_vis[M,R,S], sky[M,3], class_vecs[T,C], flags, deltas?)
+//        -> [shaded[M,T,R,3], season[T,R,3], base[R,3], raw_shadow[M,R], shadow_adjust[M,R,3]]           the M x T grid of a view
 //   season_nerf::fused_adam_(param!, grad, m!, v!, lr, b1, b2, eps, step) -> ()                         mg_run_NeRF.py:312-320
 // Training engine (csrc/train.cpp; `trainer` = the snerf_trainer handle a season_nerf_amd.training.TrainEngine owns and has bound to its
 // parameter / gradient / workspace tensors).  The forward ops are functional in their tensor arguments (torch.library.register_autograd
@@ -249,6 +253,56 @@ std::vector<Tensor> composite_sweep(const Tensor& top, const Tensor& bot, const 
     ck(snerf_composite_sweep(R, (int)S, (int)C, (int)T, fptr(top), fptr(bot), fptr(tvals), nullptr, fptr(rho), fptr(col_raw), fptr(adjust), fptr(solar_vis),
                              fptr(sky), fptr(class_vecs), (int)flags, &so, cur_stream(top)), "composite_sweep");
     return r;      // season, shaded, base, shadow_adjust, raw_shadow, classic
+}
+
+// Sun walk (include/season_nerf_hip.h snerf_field_sun_walk_rays).  The model travels as an integer, as the trainer does below: the handle of a
+// finalized model (Model.handle()), which the caller keeps alive.
+std::vector<Tensor> sun_walk_fwd(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, const Tensor& suns, const c10::optional<Tensor>& classes) {
+    TORCH_CHECK(model != 0, "season_nerf::sun_walk_fwd: NULL model handle");
+    const snerf_model* m = (const snerf_model*)model;
+    check_shape(top, "top", -1, 3);
+    const int64_t R = top.size(0);
+    check_shape(bot, "bot", R, 3);
+    check_dev_f32(tvals, "tvals");
+    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    check_shape(suns, "suns", -1, 3);
+    const int64_t S = tvals.numel(), M = suns.size(0), C = snerf_model_classes(m);
+    TORCH_CHECK(M >= 1 && M <= 32, "suns must hold 1 to 32 directions per launch, got ", M);
+    if (classes.has_value()) { check_dev_f32(*classes, "classes"); TORCH_CHECK(classes->numel() == C, "classes must hold ", C, " values, got ", classes->sizes()); }
+    c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
+    auto o = top.options();
+    std::vector<Tensor> r = {at::empty({R, S, 1}, o), at::empty({M, R, S, 1}, o), at::empty({R, S, 3}, o), at::empty({R, S, C, 3}, o), at::empty({R, S, 3}, o)};
+    snerf_field_out fo{};
+    fo.d_rho = mptr(r[0]); fo.d_solar_vis = mptr(r[1]); fo.d_col_raw = mptr(r[2]); fo.d_adjust = mptr(r[3]); fo.d_points = mptr(r[4]);
+    ck(snerf_field_sun_walk_rays(m, R, (int)S, fptr(top), fptr(bot), fptr(tvals), (int)M, fptr(suns), classes.has_value() ? fptr(*classes) : nullptr, &fo,
+                                 cur_stream(top)), "sun_walk_fwd");
+    return r;      // rho, solar_vis, col_raw, adjust, points
+}
+
+std::vector<Tensor> composite_sun_walk(const Tensor& top, const Tensor& bot, const Tensor& tvals, const Tensor& rho, const Tensor& col_raw, const Tensor& adjust,
+                                       const Tensor& solar_vis, const Tensor& sky, const Tensor& class_vecs, int64_t flags, const c10::optional<Tensor>& deltas) {
+    check_shape(top, "top", -1, 3);
+    const int64_t R = top.size(0);
+    check_shape(bot, "bot", R, 3);
+    check_dev_f32(tvals, "tvals");
+    const int64_t S = tvals.numel();
+    TORCH_CHECK(S >= 1, "tvals must be [S]");
+    check_dev_f32(class_vecs, "class_vecs");
+    TORCH_CHECK(class_vecs.dim() == 2, "class_vecs must be [T,C]");
+    const int64_t T = class_vecs.size(0), C = class_vecs.size(1);
+    check_shape(sky, "sky", -1, 3);
+    const int64_t M = sky.size(0);
+    check_dev_f32(rho, "rho"); check_dev_f32(col_raw, "col_raw"); check_dev_f32(adjust, "adjust"); check_dev_f32(solar_vis, "solar_vis");
+    TORCH_CHECK(rho.numel() == R * S && solar_vis.numel() == M * R * S && col_raw.numel() == R * S * 3 && adjust.numel() == R * S * C * 3,
+                "per-sample tensors must hold R*S elements (col_raw x3, adjust xC x3, solar_vis xM = the rows of sky)");
+    if (deltas.has_value()) { check_dev_f32(*deltas, "deltas"); TORCH_CHECK(deltas->numel() == R * S, "deltas must hold R*S elements"); }
+    c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
+    auto o = top.options();
+    std::vector<Tensor> r = {at::empty({M, T, R, 3}, o), at::empty({T, R, 3}, o), at::empty({R, 3}, o), at::empty({M, R}, o), at::empty({M, R, 3}, o)};
+    snerf_sun_walk_out so{mptr(r[0]), mptr(r[1]), mptr(r[2]), mptr(r[3]), mptr(r[4])};
+    ck(snerf_composite_sun_walk(R, (int)S, (int)C, (int)T, (int)M, fptr(top), fptr(bot), fptr(tvals), deltas.has_value() ? fptr(*deltas) : nullptr, fptr(rho),
+                                fptr(col_raw), fptr(adjust), fptr(solar_vis), fptr(sky), fptr(class_vecs), (int)flags, &so, cur_stream(top)), "composite_sun_walk");
+    return r;      // shaded, season, base, raw_shadow, shadow_adjust
 }
 
 void fused_adam_(Tensor param, const Tensor& grad, Tensor m, Tensor v, double lr, double beta1, double beta2, double eps, int64_t step) {
@@ -530,6 +584,9 @@ TORCH_LIBRARY(season_nerf, m) {
           "-> Tensor[]");
     m.def("composite_sweep(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
           "int flags, bool classic) -> Tensor[]");
+    m.def("sun_walk_fwd(int model, Tensor top, Tensor bot, Tensor tvals, Tensor suns, Tensor? classes) -> Tensor[]");
+    m.def("composite_sun_walk(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
+          "int flags, Tensor? deltas=None) -> Tensor[]");
     m.def("fused_adam_(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, int step) -> ()");
     m.def("prior_density(Tensor pts, Tensor delta, Tensor height_map, Tensor? outside) -> Tensor");
     m.def("trainer_adam_step_(int trainer, Tensor(a!) params, Tensor grads, float lr, float beta1, float beta2, float eps, int step) -> ()");
@@ -558,6 +615,8 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("ray_visibility", ray_visibility);
     m.impl("composite", composite);
     m.impl("composite_sweep", composite_sweep);
+    m.impl("sun_walk_fwd", sun_walk_fwd);
+    m.impl("composite_sun_walk", composite_sun_walk);
     m.impl("trainer_adam_step_", trainer_adam_step_);
     m.impl("trainer_adam_step_dev_", trainer_adam_step_dev_);
     m.impl("trainer_zero_grad_", trainer_zero_grad_);

@@ -172,6 +172,19 @@ __host__ __device__ constexpr int ks_pair_source(const LayerShape& s, int a, int
     return (a * nbh + i) * 4096 + (t < ksh ? a * ksh + t : s.ks0 + (t - ksh));
 }
 
+// ---- sun-walk stream (sun_walk_kernel, sun_walk_ks_kernel): the field program's stream (canonical order, or K-split order with ks) rearranged by
+// whole chunks - every layer starts on a chunk boundary - into [F_FC1 .. F_HEAD] [F_S1 .. F_S4] x n_suns [F_A1 .. F_AC].  The ring consumes a stream
+// strictly in order, so a walk over n_suns sun directions is a longer stream, not a branch.  The bias table is indexed by layer and does not change.
+__host__ __device__ constexpr int field_chunk_start(int W, int C, int l, bool ks) { return ks ? ks_chunk_start(W, C, l) : prog_chunk_start(PROG_FIELD, W, C, l); }
+__host__ __device__ constexpr int sun_walk_chunks(int W, int C, int n_suns, bool ks) {
+    return field_chunk_start(W, C, F_NUM, ks) + (n_suns - 1) * (field_chunk_start(W, C, F_A1, ks) - field_chunk_start(W, C, F_S1, ks));
+}
+// chunk of the field program's stream behind chunk c of the walk stream
+__host__ __device__ constexpr int sun_walk_source_chunk(int W, int C, int n_suns, bool ks, int c) {
+    const int a = field_chunk_start(W, C, F_S1, ks), b = field_chunk_start(W, C, F_A1, ks);
+    return c < a ? c : c < a + n_suns * (b - a) ? a + (c - a) % (b - a) : c - (n_suns - 1) * (b - a);
+}
+
 // accumulator register i of lane-half h  <->  row of the 32-row output block
 __host__ __device__ constexpr int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 

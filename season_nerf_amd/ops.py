@@ -43,6 +43,17 @@ def _register_fakes():
         e = top.new_empty
         return [e(T, R, 3), e(T, R, 3), e(R, 3), e(R, 3), e(R), e(T if classic else 0, R, 3)]
 
+    @reg("season_nerf::sun_walk_fwd")
+    def _(model, top, bot, tvals, suns, classes):
+        R, S, M, e = top.shape[0], tvals.numel(), suns.shape[0], top.new_empty
+        C = _lib.lib().snerf_model_classes(model)
+        return [e(R, S, 1), e(M, R, S, 1), e(R, S, 3), e(R, S, C, 3), e(R, S, 3)]
+
+    @reg("season_nerf::composite_sun_walk")
+    def _(top, bot, tvals, rho, col_raw, adjust, solar_vis, sky, class_vecs, flags, deltas=None):
+        R, T, M, e = top.shape[0], class_vecs.shape[0], sky.shape[0], top.new_empty
+        return [e(M, T, R, 3), e(T, R, 3), e(R, 3), e(M, R), e(M, R, 3)]
+
     @reg("season_nerf::fused_adam_")
     def _(param, grad, m, v, lr, beta1, beta2, eps, step):
         return None

@@ -5,7 +5,9 @@
     `All_in_One_Eval.eval_exact_solar` (Eval_Tools_2.py:255-295) - O(R*S^2) density-only evaluations;
   * path B  `component_render_by_dir` (T_NeRF_Eval_Utils/mg_Img_Eval.py:96-115 + `_internal_render` :17-72),
     `get_imgs_from_Img_Dict` (:123-190) and the seasonal sweep `get_imgs_from_Img_Dict_t_step` (:192-228),
-    plus `render_season_sweep`, the same pipeline without the float64 host round trip (BASELINE config 5).
+    plus `render_season_sweep`, the same pipeline without the float64 host round trip (BASELINE config 5), and the sun walk
+    (`component_render_sun_walk`, `render_sun_season_walk`): the sun x time grid of one view of `Full_Eval_Seasons`
+    (T_NeRF_Eval_Utils/mg_Season_Eval.py:74-98) from one pass of the field network.
 
 Ray-grid geometry is float64 numpy on the host exactly as in the reference (a few kFLOP per image); everything
 per-sample runs on the GPU.
@@ -564,3 +566,164 @@ def render_season_sweep(the_network, view_el_az, sun_el_az, time_fracs, out_img_
             from .parallel import gather_rows
             shaded = gather_rows(shaded.permute(1, 0, 2).contiguous(), n_total, group).permute(1, 0, 2).contiguous()
         return shaded.reshape(len(time_fracs), out_img_size[0], out_img_size[1], 3)
+
+
+# ------------------------------------------------------------------------------------------------ sun walk
+WALK_MAX_SUNS = 32                 # sun directions per walk launch (include/season_nerf_hip.h snerf_field_sun_walk_rays)
+WALK_SOLAR_VIS_BYTES = 1 << 30     # a walk launch's solar_vis [M, rays, S] stays below this: the ray blocks are sized by it
+
+
+def _walks(net):
+    """True where the fused sun-walk kernels serve the network: a fused model whose precision resolves to bf16x3 (widths 64 / 256 / 512)."""
+    return net.fused and net.resolved_precision == "bf16x3"
+
+
+def _sun_walk_device(net, view_el_az, sun_el_azs, time_frac, out_img_size, W2C, W2L_H, device, ray_range=None):
+    """The device dict of `_render_by_dir_device` for M sun directions of one view: the sun-independent tensors once, plus `Solar_Vis_All`
+    [M,R,S,1] and `Sky_All` [M,3]; `Est_Solar_Vis` / `Sky` are sun 0's rows."""
+    Hh, Ww, S = out_img_size
+    dev = torch.device(device)
+    suns64 = [world_angle_2_local_vec(s[0], s[1], W2C, W2L_H) for s in sun_el_azs]
+    M = len(suns64)
+    if M < 1:
+        raise ValueError("season_nerf_amd: the sun walk needs at least one sun direction")
+    if not _walks(net):
+        # fallback (int8-resolved models, widths without a fused kernel, the one-term fast mode): everything for sun 0, density + solar visibility for the rest
+        d = dict(_render_by_dir_device(net, view_el_az, sun_el_azs[0], time_frac, out_img_size, W2C, W2L_H, device, False, ray_range=ray_range))
+        R = d["Rho"].shape[0]
+        sv_all, sky_all = torch.empty(M, R, S, 1, device=dev), torch.empty(M, 3, device=dev)
+        sv_all[0], sky_all[0] = d["Est_Solar_Vis"], d["Sky"]
+        tim1 = _f32(encode_time(time_frac).reshape(1, 4), dev)
+        pts = d["World_Points"].reshape(-1, 3)
+        per = (1 << 20) if net.fused else (1 << 16)      # the layer-wise engine keeps every layer's array of a chunk
+        for j in range(1, M):
+            sun1 = _f32(np.asarray(suns64[j], dtype=np.float64).reshape(1, 3), dev)
+            flat = sv_all[j].reshape(-1)
+            sky_raw = None
+            for i in range(0, max(pts.shape[0], 1), per):
+                p = pts[i:i + per] if R > 0 else torch.zeros(1, 3, device=dev)
+                o = net.forward_Solar(p, sun1.expand(p.shape[0], 3), tim1.expand(p.shape[0], 4))
+                if R > 0:
+                    flat[i:i + per] = o[1].reshape(-1)
+                sky_raw = o[2][:1] if sky_raw is None else sky_raw
+            sky_all[j] = torch.sigmoid(sky_raw[0])
+        d["Solar_Vis_All"], d["Sky_All"] = sv_all, sky_all
+        return d
+    v = world_angle_2_local_vec(view_el_az[0], view_el_az[1], W2C, W2L_H)
+    lo, hi = (0, Hh * Ww) if ray_range is None else ray_range
+    top, bot, _ = _ray_grid(0, Hh, Ww, v / v[2], device, lo, hi)
+    (top, bot) = net._prep(top, bot)
+    R, Cn = top.shape[0], net.n_classes
+    L, st = _lib.lib(), net._stream()
+    tv = sample_parameters_on(dev, S, eval_mode=True, include_end_pt=True)
+    suns = _f32(np.stack([np.asarray(s, dtype=np.float64) for s in suns64]), dev)
+    tim = _f32(encode_time(time_frac).reshape(1, 4), dev).expand(M, 4).contiguous()
+    cls, _, sky_all = net._groups(tim, suns)                   # one group-network call: M sky colours, one class vector (the rows agree: one time)
+    cls0 = cls[0].contiguous()
+    e = lambda *s: torch.empty(*s, device=dev)
+    rho, col_raw, adj, pts, dl = e(R, S, 1), e(R, S, 3), e(R, S, Cn, 3), e(R, S, 3), e(R, S, 1)
+    sv_all = e(M, R, S, 1)
+    model = net.device_model()
+    for b0 in range(0, M, WALK_MAX_SUNS):
+        b1 = min(M, b0 + WALK_MAX_SUNS)
+        block = max(1, WALK_SOLAR_VIS_BYTES // (4 * S * (b1 - b0)))
+        for r0 in range(0, R, block):
+            r1 = min(R, r0 + block)
+            whole = r0 == 0 and r1 == R
+            sv = sv_all[b0:b1] if whole else e(b1 - b0, r1 - r0, S, 1)
+            # the sun-independent outputs are stored by the first batch of sun directions only
+            fo = _lib.FieldOut(d_solar_vis=sv.data_ptr()) if b0 else _lib.FieldOut(
+                d_rho=rho[r0:r1].data_ptr(), d_solar_vis=sv.data_ptr(), d_col_raw=col_raw[r0:r1].data_ptr(), d_adjust=adj[r0:r1].data_ptr(),
+                d_points=pts[r0:r1].data_ptr())
+            _lib.check(L.snerf_field_sun_walk_rays(model, r1 - r0, S, top[r0:r1].data_ptr(), bot[r0:r1].data_ptr(), tv.data_ptr(), b1 - b0,
+                                                   suns[b0:b1].data_ptr(), cls0.data_ptr(), C.byref(fo), st), "field_sun_walk_rays")
+            if not whole:
+                sv_all[b0:b1, r0:r1] = sv
+    if R > 0:
+        z3 = torch.zeros(R, S, 3, device=dev)
+        co = _lib.CompositeOut(d_delta=dl.data_ptr())
+        _lib.check(L.snerf_composite_rays(R, S, top.data_ptr(), bot.data_ptr(), tv.data_ptr(), rho.data_ptr(), z3.data_ptr(), sv_all[0].data_ptr(),
+                                          sky_all[:1].expand(R, 3).contiguous().data_ptr(), 2, None, 1.0, C.byref(co), st), "composite_rays")
+    return {"top": top, "bot": bot, "tv": tv, "World_Points": pts, "Deltas": dl, "Rho": rho, "Base_Col": col_raw, "Est_Solar_Vis": sv_all[0],
+            "Sky": sky_all[0].contiguous(), "Class": cls0, "Adjust_col": adj, "Solar_Vis_All": sv_all, "Sky_All": sky_all}
+
+
+class SunWalkRender:
+    """What `component_render_sun_walk` returns: `walk[j]` is the `ImgDict` of sun direction j, as `component_render_by_dir` would give it without exact
+    solar visibility.  The sun-independent device tensors are shared between the M dicts; `Est_Solar_Vis` and `Sky` of dict j are views of
+    `walk.dev["Solar_Vis_All"][j]` / `walk.dev["Sky_All"][j]`."""
+
+    def __init__(self, dev, net, S, image_points):
+        self.dev, self._net, self._S, self._ij, self._dicts = dev, net, S, image_points, {}
+
+    def __len__(self):
+        return self.dev["Solar_Vis_All"].shape[0]
+
+    def __getitem__(self, j):
+        j = range(len(self))[j]
+        if j not in self._dicts:
+            d = {k: v for k, v in self.dev.items() if k not in ("Solar_Vis_All", "Sky_All")}
+            d["Est_Solar_Vis"], d["Sky"] = self.dev["Solar_Vis_All"][j], self.dev["Sky_All"][j]
+            res = _to_img_dict(d, self._net, self._S, False)
+            res["Image_Points"] = self._ij
+            self._dicts[j] = res
+        return self._dicts[j]
+
+    def __iter__(self):
+        return (self[j] for j in range(len(self)))
+
+
+def component_render_sun_walk(the_network, view_el_az, sun_el_azs, time_frac, out_img_size: tuple, W2C, W2L_H, device, ray_range=None):
+    """`component_render_by_dir(..., include_exact_solar=False)` for M sun directions of one view (the sun axis of `Full_Eval_Seasons`,
+    T_NeRF_Eval_Utils/mg_Season_Eval.py:74-98) from ONE pass of the field network: only fc_solar_1..4 and the sky colour depend on the sun
+    (G_NeRF.py:100-111).  One ray grid, one group-network call (M sky colours, one class vector), one walk launch per batch of <= 32 sun
+    directions and block of rays.  Returns a `SunWalkRender`: `[j]` is the ImgDict of `sun_el_azs[j]`, bit for bit what the single-sun render
+    gives.  Exact solar visibility is not part of the walk: every sun direction needs its own secondary rays.
+
+    Fallback: a network the walk kernels do not serve (a model resolved to int8 digits, a width without a fused kernel, the one-term "bf16"
+    mode) gets the same result from one full pass for sun 0 and density + solar-visibility passes for the others - slower, and correct."""
+    with torch.no_grad():
+        Hh, Ww, S = out_img_size
+        d = _sun_walk_device(the_network, view_el_az, sun_el_azs, time_frac, out_img_size, W2C, W2L_H, device, ray_range)
+        lo, hi = (0, Hh * Ww) if ray_range is None else ray_range
+        idx = np.arange(lo, hi)
+        return SunWalkRender(d, the_network, S, np.stack([idx // Ww, idx % Ww], 1))
+
+
+def _composite_sun_walk(d, class_vecs):
+    """The grid compositing kernel on a walk's device dict; class_vecs [T,C] numpy or tensor -> dict of device tensors."""
+    dev = d["Rho"].device
+    R, S = d["Rho"].shape[0], d["Rho"].shape[1]
+    Cn = d["Adjust_col"].shape[2]
+    cv = class_vecs.to(device=dev, dtype=torch.float32).contiguous() if isinstance(class_vecs, torch.Tensor) else _f32(class_vecs, dev)
+    T, M = cv.shape[0], d["Solar_Vis_All"].shape[0]
+    e = lambda *s: torch.empty(*s, device=dev)
+    shaded, season, base, raw, sadj = e(M, T, R, 3), e(T, R, 3), e(R, 3), e(M, R), e(M, R, 3)
+    so = _lib.SunWalkOut(d_shaded=shaded.data_ptr(), d_season=season.data_ptr(), d_base=base.data_ptr(), d_raw_shadow=raw.data_ptr(),
+                         d_shadow_adjust=sadj.data_ptr())
+    sv, sky = d["Solar_Vis_All"].contiguous(), d["Sky_All"].contiguous()
+    p = lambda k: d[k].data_ptr() if d.get(k) is not None else None
+    _lib.check(_lib.lib().snerf_composite_sun_walk(R, S, Cn, T, M, p("top"), p("bot"), p("tv"), p("Deltas_explicit"), d["Rho"].data_ptr(),
+                                                   d["Base_Col"].data_ptr(), d["Adjust_col"].data_ptr(), sv.data_ptr(), sky.data_ptr(), cv.data_ptr(), 2,
+                                                   C.byref(so), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "composite_sun_walk")
+    return {"shaded": shaded, "season": season, "base": base, "raw_shadow": raw, "shadow_adjust": sadj}
+
+
+def render_sun_season_walk(the_network, view_el_az, sun_el_azs, time_fracs, out_img_size: tuple, W2C, W2L_H, device, render_time_frac=None,
+                           ray_range=None):
+    """The M x T grid of one view of `Full_Eval_Seasons` (mg_Season_Eval.py:74-98) in one GPU pipeline: the sun walk, the class vectors of all
+    `time_fracs` (`get_class_only`, as `season_sweep_tile`) and the grid compositing kernel.  Returns (images, shadow_mask), float32 on the GPU:
+    images [M,T,H,W,3] = `Season_Adj_Img * Shadow_Adjust` per (sun, time), what `get_imgs_from_Img_Dict_t_step` gives for the dict of sun j;
+    shadow_mask [M,H,W] = `Shadow_Mask` of `get_imgs_from_Img_Dict`.  With ray_range = (lo, hi) the two are [M,T,hi-lo,3] and [M,hi-lo]: the
+    blocks of `parallel.shard_bounds(H * W, n)` concatenated along the ray axis are the whole grid.  The fallback of
+    `component_render_sun_walk` applies: same results on a network the walk kernels do not serve, slower."""
+    with torch.no_grad():
+        tf0 = time_fracs[0] if render_time_frac is None else render_time_frac
+        d = _sun_walk_device(the_network, view_el_az, sun_el_azs, tf0, out_img_size, W2C, W2L_H, device, ray_range)
+        times = _f32(np.stack([encode_time(t) for t in time_fracs]), d["Rho"].device)
+        o = _composite_sun_walk(d, the_network.get_class_only(times))
+        mask = torch.sigmoid((o["raw_shadow"] - 0.2) * 30.0)
+        if ray_range is not None:
+            return o["shaded"], mask
+        M, T = o["shaded"].shape[0], o["shaded"].shape[1]
+        return o["shaded"].reshape(M, T, out_img_size[0], out_img_size[1], 3), mask.reshape(M, out_img_size[0], out_img_size[1])
