@@ -355,6 +355,22 @@ int snerf_linear_wgrad(int64_t n_points, int n_in, int n_out, const float* d_gra
 /* test introspection: synchronous copy of an internal buffer ("d_rho", "d_col", "d_head", "d_sky", "d_sv_raw", "rho", "col", "sv", "sky", ...)
  * to the host.  "d_sv_raw": dL/dSolar_Vis of the classic solar model, as the pre-sigmoid gradient the network backward consumed. */
 int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out, int64_t n_floats);
+/* test introspection of the bf16x3 row GEMMs' routing (csrc/gemm.hip plan_gemm_rows: which of the separately compiled kernel instances a product runs on).
+ * snerf_rows_debug_set - state of the CALLING THREAD, (NULL, 0, 0) restores the default:
+ *   switches8: NULL = the process's own environment switches, else eight ints that replace them for every reader - SNERF_GEMM_AREG, SNERF_GEMM_AREG_ACT,
+ *              SNERF_AREG_HV, SNERF_GEMM_FULL, SNERF_GEMM_PF, SNERF_GEMM16, SNERF_GEMM16_K320, SNERF_SNAKE, in this order;
+ *   dry_run:   snerf_linear_forward / snerf_linear_dgrad check their arguments and route as always; the route - and on the row-GEMM route the plan - is
+ *              recorded, nothing is launched and no pointer is dereferenced (any aligned non-null addresses will do: no GPU is needed);
+ *   x_padded:  the public calls promise that the input's columns n_in .. the next multiple of 16 exist (ld_in covers them) and hold zeros, as the engine
+ *              does for its K = 63 / 319 / 575 inputs.
+ * snerf_rows_record_reset / _read - one record per PROCESS (the engine's backward may run on another thread): the distinct plans executed or dry-run
+ * since the last reset.  reset(on) empties it and switches recording of executed plans on or off (dry runs are always recorded).  read copies at most
+ * max_entries entries of 12 ints and returns how many the record holds: route (0 thin-head stream, 1 row GEMM, 2 exact-fp32 GEMM), then for a row GEMM
+ * (otherwise kernel = -1, rest 0) kernel (0 gemm_areg_kernel, 1 gemm_rows16_kernel, 2 gemm_rows_full_kernel, 3 gemm_rows_kernel), the template arguments
+ * nt, pf, aol, act, hv, then tab_lds, zero_bn, the weights' split layout (0 Tile32, 1 Tile16, 2 KMajor32), grid, dynamic LDS bytes. */
+int snerf_rows_debug_set(const int* switches8, int dry_run, int x_padded);
+int snerf_rows_record_reset(int on);
+int snerf_rows_record_read(int32_t* host_out, int max_entries);
 /* torch.optim.Adam semantics (no weight decay) over the whole parameter arena in one launch; step counts from 1. */
 int snerf_trainer_adam_step(snerf_trainer* t, float lr, float beta1, float beta2, float eps, int step, void* stream);
 /* the same update with its per-step scalars in DEVICE memory: d_hyper6 = [lr, beta1, beta2, eps, 1 - beta1^step, 1 - beta2^step].  For a training

@@ -15,12 +15,15 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <set>
+#include <array>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "gemm_rows.h"
+#include "rows_debug.h"
 #include "train.h"
 
 namespace snerf {
@@ -607,10 +610,44 @@ int gemm_device_cus(bool whole_xcds) {
 
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static int env_not0(const char* name) { const char* e = getenv(name); return (e && e[0] == '0') ? 0 : 1; }      // on unless the value starts with '0'
+static thread_local RowsSwitches tl_rows_sw;      // the calling thread's override (rows_debug.h)
 const RowsSwitches& rows_switches() {
+    if (tl_rows_debug.active && tl_rows_debug.override_sw) return tl_rows_sw;
     static const RowsSwitches sw = {env_int("SNERF_GEMM_AREG", 1), env_int("SNERF_GEMM_AREG_ACT", 1), env_int("SNERF_AREG_HV", 2), env_not0("SNERF_GEMM_FULL"),
                                     env_int("SNERF_GEMM_PF", 0),   env_not0("SNERF_GEMM16"),          env_not0("SNERF_GEMM16_K320"), env_not0("SNERF_SNAKE")};
     return sw;
+}
+
+// ---- test introspection (rows_debug.h)
+void rows_debug_set(const int* v, bool dry_run, bool x_padded) {
+    if (v) tl_rows_sw = RowsSwitches{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    tl_rows_debug = RowsDebug{v != nullptr || dry_run || x_padded, v != nullptr, dry_run, x_padded};
+}
+using RowsRecord = std::array<int32_t, ROWS_RECORD_INTS>;
+static std::mutex rows_record_mu;
+static std::set<RowsRecord>& rows_record() { static std::set<RowsRecord> r; return r; }
+void rows_record_reset(bool on) {
+    std::lock_guard<std::mutex> lock(rows_record_mu);
+    rows_record().clear();
+    rows_record_on.store(on, std::memory_order_relaxed);
+}
+int rows_record_read(int32_t* out, int max_entries) {
+    std::lock_guard<std::mutex> lock(rows_record_mu);
+    int i = 0;
+    for (const RowsRecord& r : rows_record()) {
+        if (i >= max_entries || !out) break;
+        for (int q = 0; q < ROWS_RECORD_INTS; ++q) out[(size_t)i * ROWS_RECORD_INTS + q] = r[q];
+        ++i;
+    }
+    return (int)rows_record().size();
+}
+static void rows_note(const RowsRecord& r) {
+    std::lock_guard<std::mutex> lock(rows_record_mu);
+    rows_record().insert(r);
+}
+void rows_note_route(int route) { rows_note(RowsRecord{route, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}); }
+static void rows_note_plan(const RowsPlan& p) {
+    rows_note(RowsRecord{1, (int)p.kernel, p.nt, p.pf, p.aol, p.act, p.hv, p.tab_lds, p.zero_bn ? 1 : 0, (int)p.split, (int32_t)p.grid, (int32_t)p.lds});
 }
 
 struct WgradX {
@@ -1065,7 +1102,7 @@ static hipError_t launch_full(const GemmX& gx, const RowsPlan& p, hipStream_t st
 }
 template <int NT>
 static hipError_t launch_full_nt(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
-    return p.pf == 8 ? launch_full<NT, 8>(gx, p, st) : p.pf == 4 ? launch_full<NT, 4>(gx, p, st) : launch_full<NT, 2>(gx, p, st);
+    return p.pf == 8 ? launch_full<NT, 8>(gx, p, st) : p.pf == 4 ? launch_full<NT, 4>(gx, p, st) : p.pf == 2 ? launch_full<NT, 2>(gx, p, st) : hipErrorInvalidValue;
 }
 template <int NT>
 static hipError_t launch_general(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
@@ -1094,16 +1131,20 @@ static hipError_t run_gemm_rows(const GemmX& g, const RowsPlan& p, hipStream_t s
     switch (p.kernel) {
         case RowsKernel::AREG: return launch_gemm_areg(gx, p, st);
         case RowsKernel::ROWS16: return launch_gemm_rows16(gx, p, st);
-        case RowsKernel::FULL: return p.nt == 1 ? launch_full_nt<1>(gx, p, st) : p.nt == 4 ? launch_full_nt<4>(gx, p, st) : launch_full_nt<2>(gx, p, st);
-        default: return p.nt == 4 ? launch_general<4>(gx, p, st) : launch_general<2>(gx, p, st);
+        case RowsKernel::FULL: return p.nt == 1 ? launch_full_nt<1>(gx, p, st) : p.nt == 4 ? launch_full_nt<4>(gx, p, st) : p.nt == 2 ? launch_full_nt<2>(gx, p, st) : hipErrorInvalidValue;
+        case RowsKernel::GENERAL: return p.nt == 4 ? launch_general<4>(gx, p, st) : p.nt == 2 ? launch_general<2>(gx, p, st) : hipErrorInvalidValue;
     }
+    return hipErrorInvalidValue;      // a plan that names an instance that does not exist is an error, never another instance
 }
 
 hipError_t launch_gemm_bf16x3(const GemmX& g, hipStream_t st) {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     RowsPlan p;
     const hipError_t e = plan_gemm_rows(g, rows_switches(), p);
-    return e != hipSuccess ? e : run_gemm_rows(g, p, st);
+    if (e != hipSuccess) return e;
+    if (rows_noting()) rows_note_plan(p);
+    if (rows_dry_run()) return hipSuccess;      // planned and recorded: nothing is launched (rows_debug.h)
+    return run_gemm_rows(g, p, st);
 }
 
 }  // namespace snerf

@@ -338,7 +338,7 @@ static hipError_t launch_rows16(const GemmX& gx, const RowsPlan& p, hipStream_t 
 }
 template <int NT>
 static hipError_t launch_rows16_nt(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
-    return p.pf == 4 ? launch_rows16<NT, 4>(gx, p, st) : p.pf == 2 ? launch_rows16<NT, 2>(gx, p, st) : launch_rows16<NT, 1>(gx, p, st);
+    return p.pf == 4 ? launch_rows16<NT, 4>(gx, p, st) : p.pf == 2 ? launch_rows16<NT, 2>(gx, p, st) : p.pf == 1 ? launch_rows16<NT, 1>(gx, p, st) : hipErrorInvalidValue;
 }
 
 int gemm_rows16_waves() { return R16_WAVES; }
@@ -347,7 +347,7 @@ int gemm_rows16_waves() { return R16_WAVES; }
 // group - 8 (128 columns; K <= 256) or 4 (64 columns: the K = 320 layer, forwards only)
 hipError_t launch_gemm_rows16(const GemmX& gx, const RowsPlan& p, hipStream_t st) {
     if (p.nt == 4 && p.act) return hipErrorInvalidValue;
-    return p.nt == 4 ? launch_rows16_nt<4>(gx, p, st) : launch_rows16_nt<8>(gx, p, st);
+    return p.nt == 4 ? launch_rows16_nt<4>(gx, p, st) : p.nt == 8 ? launch_rows16_nt<8>(gx, p, st) : hipErrorInvalidValue;
 }
 
 }  // namespace snerf

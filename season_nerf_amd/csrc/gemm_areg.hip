@@ -587,6 +587,9 @@ static hipError_t launch_areg(const GemmX& g, const RowsPlan& p, hipStream_t st)
 // g.frag must hold the k-major stream (SplitLayout::KMajor32); p: the instance plan_gemm_rows chose for a shape gemm_areg_ok takes
 hipError_t launch_gemm_areg(const GemmX& g, const RowsPlan& p, hipStream_t st) {
     const bool p8 = p.pf == 8, wide = p.nt == 16;      // wide: N = 512 in one wave's 256 AGPRs
+    // a plan that names an instance that does not exist is an error, never another instance
+    if ((p.pf != 8 && p.pf != 4) || (p.nt != 16 && p.nt != 8) || (p.hv != 1 && p.hv != 2) || (p.act && p.aol) || (p.hv == 2 && (p.nt != 8 || p.pf != 4 || p.act)))
+        return hipErrorInvalidValue;
     if (p.hv == 2) return p.aol ? launch_areg<8, 1, 4, 0, 2>(g, p, st) : launch_areg<8, 0, 4, 0, 2>(g, p, st);      // two waves per SIMD, a column half each
     if (p.act) {      // input gradient with the activation-backward epilogue
         if (wide) return p8 ? launch_areg<16, 0, 8, 1>(g, p, st) : launch_areg<16, 0, 4, 1>(g, p, st);

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "rows_debug.h"
 #include "train.h"
 
 namespace snerf {
@@ -126,16 +127,23 @@ inline Route route_wgrad(const Product& p, const Policy& pol) {
     return wgrad_rows_ok(pol, p.M) ? Route::Rows : Route::Fp32;
 }
 // ---- launching a routed product (the two-head form: Route::Thin only).  What a route cannot do is an error, never another route.
+// Test introspection (rows_debug.h): a Thin / Fp32 route is recorded here, a Rows plan by launch_gemm_bf16x3; true = dry run, launch nothing.
+inline bool route_noted_dry(Route r) {
+    if (r != Route::Rows && rows_noting()) rows_note_route((int)r);
+    return r != Route::Rows && rows_dry_run();
+}
 inline hipError_t run_fwd(const Product& p, Route r, hipStream_t st) {
-    if (r == Route::Thin) return launch_thin_fwd(thin_fwd_args(p), st);
     if (r == Route::Rows) return launch_gemm_bf16x3(gemm_fwd_x(p), st);
-    if (p.tab || p.stats) return hipErrorInvalidValue;      // activation on load / epilogue statistics need the row kernel
+    if (r == Route::Fp32 && (p.tab || p.stats)) return hipErrorInvalidValue;      // activation on load / epilogue statistics need the row kernel
+    if (route_noted_dry(r)) return hipSuccess;
+    if (r == Route::Thin) return launch_thin_fwd(thin_fwd_args(p), st);
     return launch_gemm(gemm_fwd_args(p), st);
 }
 // the epilogue (p.below) is applied on the thin and row routes, ignored by the fp32 GEMM: the caller asks `r != Route::Fp32`
 inline hipError_t run_dgrad(const Product& p, Route r, hipStream_t st) {
-    if (r == Route::Thin) return launch_thin_dgrad(thin_dgrad_args(p), st);
     if (r == Route::Rows) return launch_gemm_bf16x3(gemm_dgrad_x(p), st);
+    if (route_noted_dry(r)) return hipSuccess;
+    if (r == Route::Thin) return launch_thin_dgrad(thin_dgrad_args(p), st);
     return launch_gemm(gemm_dgrad_args(p), st);
 }
 inline hipError_t run_wgrad(const Product& p, Route r, hipStream_t st) {

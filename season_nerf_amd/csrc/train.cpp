@@ -814,6 +814,21 @@ int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out
     return SNERF_OK;
 }
 
+// Introspection for tests: the row GEMMs' routing (rows_debug.h).
+int snerf_rows_debug_set(const int* switches8, int dry_run, int x_padded) {
+    if (switches8 && switches8[4] != 0 && switches8[4] != 2 && switches8[4] != 4 && switches8[4] != 8) return snerf_set_error(SNERF_E_INVALID, "snerf_rows_debug_set: pf must be 0, 2, 4 or 8");
+    rows_debug_set(switches8, dry_run != 0, x_padded != 0);
+    return SNERF_OK;
+}
+int snerf_rows_record_reset(int on) {
+    rows_record_reset(on != 0);
+    return SNERF_OK;
+}
+int snerf_rows_record_read(int32_t* host_out, int max_entries) {
+    if (max_entries < 0 || (max_entries > 0 && !host_out)) return snerf_set_error(SNERF_E_INVALID, "snerf_rows_record_read: bad argument");
+    return rows_record_read(host_out, max_entries);
+}
+
 // ---- the three products of a Linear layer as stand-alone calls (building blocks of the training engine; tests)
 size_t snerf_linear_scratch_bytes(int n_out, int n_in) {
     const int64_t d = n_out > n_in ? n_out : n_in;
@@ -832,6 +847,7 @@ int snerf_linear_forward(int64_t n_points, int n_in, int n_out, const float* d_i
     Product p;
     p.M = n_points; p.n_in = n_in; p.n_out = n_out; p.alpha = alpha; p.W = d_weight; p.bias = d_bias; p.frag = (const uint16_t*)d_scratch;
     p.X = d_in; p.ldx = ld_in; p.tab = d_act_tab; p.tab_cols = d_act_tab ? act_cols : 0; p.Y = d_out; p.ldy = ld_out; p.stats = d_stats;
+    p.x_padded = rows_x_padded();      // snerf_rows_debug_set: the caller guarantees zero columns n_in .. next multiple of 16
     const Route r = route_fwd(p, public_policy(precision));
     if (r == Route::Rows && (!d_scratch || scratch_bytes < snerf_linear_scratch_bytes(n_out, n_in))) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: scratch too small");
     if (r == Route::Fp32 && (d_stats || d_act_tab)) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_forward: column statistics / activation on load need the bf16x3 path");
@@ -851,6 +867,7 @@ int snerf_linear_dgrad(int64_t n_points, int n_in, int n_out, const float* d_gra
     Product p;
     p.M = n_points; p.n_in = n_in; p.n_out = n_out; p.alpha = alpha; p.W = d_weight; p.Y = const_cast<float*>(d_grad_out); p.ldy = ld_go;      // (Y: read-only here)
     p.dX = d_grad_in; p.lddx = ld_gi; p.n_cols = n_cols; p.accumulate = accumulate != 0; p.frag = (const uint16_t*)d_scratch;
+    p.x_padded = rows_x_padded();
     if (d_below_z) { p.below.z = d_below_z; p.below.ld = ld_below_z; p.below.tab = d_below_tab; p.below.mu = d_below_mu; p.below.istd = d_below_istd; p.below.sums = d_sums; }
     const Route r = route_dgrad(p, public_policy(precision));
     if (r == Route::Fp32 && d_below_z) return snerf_set_error(SNERF_E_INVALID, "snerf_linear_dgrad: the activation-backward epilogue needs the bf16x3 path");

@@ -1,6 +1,8 @@
 """gemm_areg_kernel (csrc/gemm_areg.hip: K = 256 / 512 row GEMM, activations resident in AGPRs, weights streamed through the LDS ring) against the
-column-group row GEMMs of gemm.hip: same fragments, same product order, same k order - bit for bit on the outputs, fp32-partial-sum rounding on the
-BatchNorm column sums - and timed at the training step's size.  One child process per mode (the switch is read once per process).
+column-group row GEMMs of gemm.hip: same fragments, same product order, same k order - the same accumulator bits; the forward epilogue folds the bias in
+as fma(alpha, acc, alpha * bias) where the column-group kernels compute alpha * (acc + bias), so with a bias (as here) the outputs are 1 ulp apart and
+the bitwise comparison below reports DIFF (tests/test_gpu_rows_instances.py holds the bitwise claim without a bias and the rounding bound with one);
+fp32-partial-sum rounding on the BatchNorm column sums - and timed at the training step's size.  One child process per mode (the switch is read once per process).
 usage (GPU box): python3 tools/areg_check.py"""
 import os
 import subprocess
