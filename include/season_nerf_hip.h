@@ -254,6 +254,23 @@ int snerf_composite_sun_walk(int64_t n_rays, int n_samples, int n_classes, int n
                              const float* d_adjust, const float* d_solar_vis, const float* d_sky, const float* d_class_vecs,
                              int flags, const snerf_sun_walk_out* out, void* stream);
 
+/* ---- ray surface: height maps from a density-only ray pass with the compositing inside the field kernel.
+ * The reference forms its height maps from the density along a ray alone: Quick_Run_Net.get_DSM (Quick_Run.py:207-226, :37-40),
+ * Eval_funcs.eval_HM / gen_results (T_NeRF_Eval_Utils/Eval_funcs.py:268-319) and the surface location / distance of Net_tool.eval_img
+ * (mg_run_NeRF.py:188-189).  One launch walks the S samples of every ray from t = 0 (d_top) to d_bot, 32 per pass, through the density-only
+ * network and the transmittance scan of snerf_composite_rays, and stores four numbers per ray, d_out [n_rays,4] (16-byte aligned):
+ *   [0] acc   = sum_s PS_s                       the opacity; Est_HM's denominator (Eval_funcs.py:319), the quotients of mg_run_NeRF.py:188-189
+ *   [1] mt    = sum_s PS_s t_s                   surface location = (top (acc - mt) + bot mt) / (acc + 1e-8)        (mg_run_NeRF.py:188)
+ *   [2] mi    = sum_s PS_s s                     height = acc - 2 mi / (S - 1) = sum_s PS_s linspace(1, -1, S)[s]   (Quick_Run.py:39, Eval_funcs.py:319);
+ *                                                surface distance = delta (mi + acc) / acc                          (mg_run_NeRF.py:189)
+ *   [3] carry = sum of rho_s delta_s walked      transmittance behind the walked samples = exp(-carry)
+ * with PS_s = exp(-sum_{j<s} rho_j delta_j) (1 - exp(-rho_s delta_s)), delta = ||top - bot|| / S, all S samples counting.
+ * flags bit1 = a sample outside [-1,1]^3 gets delta 0; bit2 = no early-out.  Early-out: once every ray of a workgroup has walked past
+ * optical depth 18 its remaining passes are skipped (every PS left is below exp(-18) = 1.5e-8); carry then holds the depth walked.
+ * SNERF_E_INVALID for bad arguments and unless the model's resolved precision is SNERF_PREC_BF16X3 (width 64, 256 or 512). */
+int snerf_field_ray_surface(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot,
+                            const float* d_tvals, int flags, float* d_out, void* stream);
+
 /* ---- training engine: the device side of Net_tool.train_step (mg_run_NeRF.py:288-326) = All_in_One_Eval.get_loss
  * (Eval_Tools_2.py:340-459) forward passes in .train() mode, backward, Adam.  Layer-wise, fp32 storage, 3-term split bf16 MFMA
  * GEMMs (exact-fp32 MFMA under SNERF_TRAIN_GEMM=fp32), batch-statistics BatchNorm1d (momentum 0.01, misc.py:170) with running-stat EMA, activations stashed in HBM.

@@ -10,11 +10,11 @@ from .network import T_NeRF, SineLayer
 from .evaluator import All_in_One_Eval, sample_parameters, get_PV
 from .render import (Quick_Run_Net, component_render_by_dir, component_render_by_P, get_imgs_from_Img_Dict, get_imgs_from_Img_Dict_t_step,
                      render_season_sweep, world_angle_2_local_vec, encode_time, component_render_sun_walk, render_sun_season_walk,
-                     SunWalkRender)
+                     SunWalkRender, RaySurface, ray_surface, height_map)
 
 __all__ = ["T_NeRF", "SineLayer", "All_in_One_Eval", "sample_parameters", "get_PV", "Quick_Run_Net", "component_render_by_dir", "component_render_by_P",
            "get_imgs_from_Img_Dict", "get_imgs_from_Img_Dict_t_step", "render_season_sweep", "world_angle_2_local_vec",
-           "encode_time", "component_render_sun_walk", "render_sun_season_walk", "SunWalkRender", "parallel", "raytable", "FusedAdam", "TrainEngine", "create_solor_rays_uniform", "_lib"]
+           "encode_time", "component_render_sun_walk", "render_sun_season_walk", "SunWalkRender", "RaySurface", "ray_surface", "height_map", "parallel", "raytable", "FusedAdam", "TrainEngine", "create_solor_rays_uniform", "_lib"]
 from .adaptive_loss import AdaptiveLossFunction  # noqa: E402,F401
 from . import validation  # noqa: E402,F401
 from .validation import DSM_Distance, eval_img, image_error  # noqa: E402,F401

@@ -55,6 +55,14 @@ struct SunWalkArgs {
     int n_suns;
 };
 
+// Ray surface (ray_surface_kernel / ray_surface_ks_kernel, mlp_device.h RaySurf): the density-only walk of VARIANT 3 with the compositing scan inside.
+// Wraps MlpArgs as SunWalkArgs does.  m.n = rays, m.stream = the field stream cycled over the layers of variant 3, m.ray_flags bit 3 always set
+// (passes from t = 0 downwards); out [n,4] = {sum PS, sum PS t, sum PS s, optical depth walked} per ray, 16-byte aligned.
+struct RaySurfaceArgs {
+    MlpArgs m;
+    float* out;
+};
+
 struct CompOutDev {
     float *rgb, *albedo, *pv, *pe, *ps, *delta, *shadow, *acc, *surf_loc, *surf_dist;
 };
@@ -132,7 +140,10 @@ __host__ __device__ inline int64_t field_tiles(int64_t n, int variant, int pts, 
 // persistent launch of a fused kernel: min(n_tiles, n_cu) workgroups (at least one) of `block` threads with `lds_bytes` of dynamic LDS (kernels.hip)
 hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_fused(void (*kernel)(RaySurfaceArgs), int64_t n_tiles, int block, int lds_bytes, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
+hipError_t launch_ray_surface_ks(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);                          // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)

@@ -929,4 +929,73 @@ hipError_t launch_composite(const CompArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+
+// =====================================================================================================
+// Ray surface: the VARIANT 3 walk of mlp_kernel (a wave owns a ray, 32 samples per pass, the density-only stream) with the compositing scan in the pass
+// end (mlp_device.h RaySurf): four floats out per ray, from which the height map (Quick_Run.py:37-40), eval_HM's columns (Eval_funcs.py:299-319) and the
+// surface location / distance (mg_run_NeRF.py:188-189) follow.  No per-sample array, no compositing launch.
+template <int W>
+__global__ __launch_bounds__(256, 1) void ray_surface_kernel(const RaySurfaceArgs RA) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MlpArgs& A = RA.m;
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    lds_char* lds = (lds_char*)smem;
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5;
+
+    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
+
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
+    __syncthreads();
+
+    const int64_t n_tiles = field_tiles(A.n, 3, TILE_PTS, 4);      // a tile is a group of 4 rays, one per wave
+    const int passes = (A.n_samples + 31) / 32;
+    int pass = 0;
+    RaySurf rs;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;) {
+        float x0, x1, x2;
+        raysurf_point(rs, A, tile, 4, wave, pass, lane, x0, x1, x2);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KW = W / 16, KW2 = W2 / 16;
+        Frag hA[KW], hB[KW];
+        f32x16 raw;
+#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
+    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
+        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
+        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
+        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        Frag x1f[KW2];
+        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
+        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+#undef LAYER
+        const float rho_raw = raw[3];       // lane-half 0 holds the density row
+        RAYSURF_PASS_END(rs, A, RA.out, tile, pass, passes, 4, wave, wave, 4, true, lane, rho_raw, bias_lds + A.bias_floats);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_fused(void (*kernel)(RaySurfaceArgs), int64_t n_tiles, int block, int lds_bytes, const RaySurfaceArgs& a, int n_cu, hipStream_t st) {
+    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
+}
+
+hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st) {
+    if (W == 512) return launch_ray_surface_ks(W, a, n_cu, st);
+    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats);
+    const int64_t tiles = field_tiles(a.m.n, 3, TILE_PTS, 4);
+    if (W == 64) return launch_fused(ray_surface_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
+    if (W == 256) return launch_fused(ray_surface_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace snerf

@@ -277,6 +277,80 @@ __device__ __forceinline__ void raysum_end(RaySum& q, const MlpArgs& A, int64_t 
         }                                                                                                                       \
     }
 
+// Ray surface (ray_surface_kernel, ray_surface_ks_kernel): the walk of VARIANT 3 - same density-only stream, ring and vote - with the compositing
+// scan of composite_kernel run on each pass's 32 densities, so that a height map needs no [R,S] array at all (Quick_Run.py:37-40,207-226;
+// Eval_funcs.py:299-319; mg_run_NeRF.py:188-189).  The transmittance is a prefix: the passes run from the ray's top (t = 0) downwards (raysum_block with
+// ray_flags bit 3, which the host always sets), and every one of the S samples counts.  Four floats per lane live across the MFMA chain.
+struct RaySurf {
+    float carry;                    // optical depth of the samples of the passes walked so far (the same in lanes 0..31, 0 in the others)
+    float acc, mt, mi;              // this lane's partial sums of PS, PS t_s and PS s
+};
+// sample position of this lane in pass p: raysum_point's; the first pass of a ray clears its sums
+__device__ __forceinline__ void raysurf_point(RaySurf& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
+    RaySum unused;
+    raysum_point(unused, A, group, waves, wave, p, lane, x0, x1, x2);
+    if (p == 0) { q.carry = 0.f; q.acc = 0.f; q.mt = 0.f; q.mi = 0.f; }
+}
+// The pass's 32 samples into the sums: composite_kernel's y, scan, PV, PE and PS (kernels.hip) over the 32 lanes of half 0.  A basic block of its own and the
+// end points and t re-read behind the chain, both for the reasons given in raysum_add.  The exclusive prefix is the inclusive value of the lane below
+// (kernels.hip wave_excl_of), never incl - y.
+__device__ __forceinline__ void raysurf_add(RaySurf& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float rho_raw) {
+    if (lane >= 32) return;
+    const int64_t ray = group * waves + wave;
+    const int64_t r = ray < A.n ? ray : A.n - 1;
+    const float tx = A.top[r * 3], ty = A.top[r * 3 + 1], tz = A.top[r * 3 + 2];
+    const float bx = A.bot[r * 3], by = A.bot[r * 3 + 1], bz = A.bot[r * 3 + 2];
+    const float dx = tx - bx, dy = ty - by, dz = tz - bz;
+    float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    const int s = raysum_block(A, p) * 32 + lane;
+    const bool in = s < A.n_samples;
+    const float t = A.tvals[in ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
+    const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
+    const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
+    const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
+    if ((A.ray_flags & 2) && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+    const float y = in ? softplus_f(rho_raw) * delta : 0.f;
+    float incl = y;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+        const float u = __shfl_up(incl, o, 32);
+        if (lane >= o) incl += u;
+    }
+    const float below = __shfl_up(incl, 1, 32);
+    const float excl = q.carry + (lane == 0 ? 0.f : below);
+    q.carry += __shfl(incl, 31, 32);
+    const float pv = expf(-excl);
+    const float pe = 1.f - expf(-y);
+    const float ps = in ? pv * pe : 0.f;
+    q.acc += ps;
+    q.mt += ps * t;
+    q.mi += ps * (float)s;
+}
+// the ray's four numbers {sum PS, sum PS t, sum PS s, optical depth walked}: one 16-byte store by lane 0
+__device__ __forceinline__ void raysurf_end(const RaySurf& q, const MlpArgs& A, float* out, int64_t ray, int lane) {
+    float acc = q.acc, mt = q.mt, mi = q.mi;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_xor(acc, o, 64);
+        mt += __shfl_xor(mt, o, 64);
+        mi += __shfl_xor(mi, o, 64);
+    }
+    if (lane == 0 && ray < A.n) *reinterpret_cast<f32x4*>(out + ray * 4) = f32x4{acc, mt, mi, q.carry};
+}
+// The end of a pass, as RAYSUM_PASS_END (a macro for the same reason).  The early-out is the vote of raysum_saturated on the optical depth walked so far:
+// lane 0 carries it into the vote's butterfly sum, the other lanes add zero.  Behind depth 18 every further PS is below exp(-18) = 1.5e-8.
+#define RAYSURF_PASS_END(q, A, out, tile, pass, passes, rays, ray_wave, slot, n_slots, writer, lane, rho_raw, vote)                 \
+    {                                                                                                                           \
+        raysurf_add(q, A, tile, rays, ray_wave, pass, lane, rho_raw);                                                           \
+        RaySum depth;                                                                                                           \
+        depth.sum = lane == 0 ? q.carry : 0.f;                                                                                  \
+        if (++pass == (passes) || raysum_saturated(depth, A, tile * (rays) + (ray_wave), slot, n_slots, lane, vote)) {          \
+            if (writer) raysurf_end(q, A, out, tile * (rays) + (ray_wave), lane);                                               \
+            pass = 0;                                                                                                           \
+            tile += gridDim.x;                                                                                                  \
+        }                                                                                                                       \
+    }
+
 // output non-linearities of the field program (T_NeRF_net_v2.py:91-98) for one point; called by the lanes that hold the head rows
 template <int VARIANT>
 __device__ __forceinline__ void store_field_outputs(const snerf_field_out_dev& O, int64_t n, int C, float x0, float x1, float x2,

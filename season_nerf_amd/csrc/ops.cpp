@@ -20,6 +20,7 @@
 //        -> [rho[R,S,1], solar_vis[M,R,S,1], col_raw[R,S,3], adjust[R,S,C,3], points[R,S,3]]             (mg_Season_Eval.py:74-98; `model` = Model.handle())
 //   season_nerf::composite_sun_walk(top, bot, tvals, rho, col_raw, adjust, solar_vis[M,R,S], sky[M,3], class_vecs[T,C], flags, deltas?)
 //        -> [shaded[M,T,R,3], season[T,R,3], base[R,3], raw_shadow[M,R], shadow_adjust[M,R,3]]           the M x T grid of a view
+//   season_nerf::ray_surface(model, top[R,3], bot[R,3], tvals[S], flags) -> [R,4] {sum PS, sum PS t, sum PS s, optical depth}      height maps from a density-only ray pass
 //   season_nerf::fused_adam_(param!, grad, m!, v!, lr, b1, b2, eps, step) -> ()                         mg_run_NeRF.py:312-320
 // Training engine (csrc/train.cpp; `trainer` = the snerf_trainer handle a season_nerf_amd.training.TrainEngine owns and has bound to its
 // parameter / gradient / workspace tensors).  The forward ops are functional in their tensor arguments (torch.library.register_autograd
@@ -277,6 +278,23 @@ std::vector<Tensor> sun_walk_fwd(int64_t model, const Tensor& top, const Tensor&
     ck(snerf_field_sun_walk_rays(m, R, (int)S, fptr(top), fptr(bot), fptr(tvals), (int)M, fptr(suns), classes.has_value() ? fptr(*classes) : nullptr, &fo,
                                  cur_stream(top)), "sun_walk_fwd");
     return r;      // rho, solar_vis, col_raw, adjust, points
+}
+
+// Ray surface (include/season_nerf_hip.h snerf_field_ray_surface): the four sums per ray a height map is formed from.  The model travels as an
+// integer, as in sun_walk_fwd, so that the op has a fake kernel.
+Tensor ray_surface(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, int64_t flags) {
+    TORCH_CHECK(model != 0, "season_nerf::ray_surface: NULL model handle");
+    check_shape(top, "top", -1, 3);
+    const int64_t R = top.size(0);
+    check_shape(bot, "bot", R, 3);
+    check_dev_f32(tvals, "tvals");
+    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    TORCH_CHECK(flags >= 0 && (flags & ~(int64_t)6) == 0, "flags must be a combination of 2 (zero delta outside the cube) and 4 (no early-out), got ", flags);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
+    Tensor out = at::empty({R, 4}, top.options());
+    if (R == 0) return out;
+    ck(snerf_field_ray_surface((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(tvals), (int)flags, mptr(out), cur_stream(top)), "ray_surface");
+    return out;
 }
 
 std::vector<Tensor> composite_sun_walk(const Tensor& top, const Tensor& bot, const Tensor& tvals, const Tensor& rho, const Tensor& col_raw, const Tensor& adjust,
@@ -585,6 +603,7 @@ TORCH_LIBRARY(season_nerf, m) {
     m.def("composite_sweep(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
           "int flags, bool classic) -> Tensor[]");
     m.def("sun_walk_fwd(int model, Tensor top, Tensor bot, Tensor tvals, Tensor suns, Tensor? classes) -> Tensor[]");
+    m.def("ray_surface(int model, Tensor top, Tensor bot, Tensor tvals, int flags) -> Tensor");
     m.def("composite_sun_walk(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
           "int flags, Tensor? deltas=None) -> Tensor[]");
     m.def("fused_adam_(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, int step) -> ()");
@@ -617,6 +636,7 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("composite_sweep", composite_sweep);
     m.impl("sun_walk_fwd", sun_walk_fwd);
     m.impl("composite_sun_walk", composite_sun_walk);
+    m.impl("ray_surface", ray_surface);
     m.impl("trainer_adam_step_", trainer_adam_step_);
     m.impl("trainer_adam_step_dev_", trainer_adam_step_dev_);
     m.impl("trainer_zero_grad_", trainer_zero_grad_);

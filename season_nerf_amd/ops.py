@@ -54,6 +54,10 @@ def _register_fakes():
         R, T, M, e = top.shape[0], class_vecs.shape[0], sky.shape[0], top.new_empty
         return [e(M, T, R, 3), e(T, R, 3), e(R, 3), e(M, R), e(M, R, 3)]
 
+    @reg("season_nerf::ray_surface")
+    def _(model, top, bot, tvals, flags):
+        return top.new_empty(top.shape[0], 4)
+
     @reg("season_nerf::fused_adam_")
     def _(param, grad, m, v, lr, beta1, beta2, eps, step):
         return None

@@ -118,6 +118,106 @@ def _ray_grid(mode, rows, cols, params, device, lo=0, hi=None, want_pixels=False
     return (top, bot, valid.bool()) + ((pix,) if want_pixels else ())
 
 
+# ------------------------------------------------------------------------------------------------ height maps from the density alone
+class RaySurface:
+    """What `ray_surface` returns: four float32 device tensors [R] per ray (include/season_nerf_hip.h snerf_field_ray_surface) -
+    `acc` = sum PS, `mt` = sum PS t, `mi` = sum PS s, `carry` = the optical depth walked - and the products the reference forms from
+    the PS of a ray, formed from them in float64 on the device."""
+
+    def __init__(self, acc, mt, mi, carry, n_samples, delta):
+        self.acc, self.mt, self.mi, self.carry, self.n_samples = acc, mt, mi, carry, int(n_samples)
+        self.delta = delta           # [R] float64: ||top - bot|| / S
+
+    def dsm(self):
+        """sum_s PS_s linspace(1, -1, S)[s]  (Quick_Run.py:39)."""
+        if self.n_samples == 1:
+            return self.acc.double()
+        return self.acc.double() - 2.0 * self.mi.double() / (self.n_samples - 1)
+
+    def expected_height(self):
+        """Est_HM of eval_HM: dsm / sum PS  (Eval_funcs.py:319)."""
+        return self.dsm() / self.acc.double()
+
+    def surface_location(self, top, bot):
+        """sum_s PS_s p_s / (sum PS + 1e-8), p_s = top (1 - t_s) + bot t_s  (mg_run_NeRF.py:188) -> [R,3]."""
+        acc, mt = self.acc.double().unsqueeze(1), self.mt.double().unsqueeze(1)
+        return (top.double() * (acc - mt) + bot.double() * mt) / (acc + 1e-8)
+
+    def surface_distance(self):
+        """sum_s PS_s cumsum(delta)_s / sum PS  (mg_run_NeRF.py:189)."""
+        return self.delta * (self.mi.double() + self.acc.double()) / self.acc.double()
+
+    def opacity(self):
+        return self.acc.double()
+
+    def transmittance(self):
+        """exp(-optical depth walked): what is left of the ray behind its last walked sample."""
+        return torch.exp(-self.carry.double())
+
+
+def _surface_layerwise(net, tops, bots, tv, S, zero_oob):
+    """The four numbers of `ray_surface` for a chunk of rays from the density pass the network has (`forward_Classic_Sigma_Only`) and float64 sums:
+    networks the ray-surface kernels do not serve.  PV is the exclusive prefix formed as get_PV forms it (Eval_Tools_2.py:13-16)."""
+    n = tops.shape[0]
+    t = tv.reshape(1, S, 1)
+    p = tops.unsqueeze(1) * (1.0 - t) + bots.unsqueeze(1) * t
+    delta = (torch.sqrt(torch.sum((tops - bots) ** 2, 1)) / S).reshape(n, 1).expand(n, S)
+    if zero_oob:
+        delta = torch.where((p.abs() > 1).any(2), torch.zeros_like(delta), delta)
+    rho = net.forward_Classic_Sigma_Only(p.reshape(-1, 3)).reshape(n, S)
+    y = rho.double() * delta.double()
+    c = torch.cumsum(torch.cat([torch.zeros_like(y[:, :1]), y], 1), 1)
+    ps = torch.exp(-c[:, :-1]) * (1.0 - torch.exp(-y))
+    idx = torch.arange(S, device=tops.device, dtype=torch.float64)
+    return torch.stack([ps.sum(1), (ps * tv.double().reshape(1, S)).sum(1), (ps * idx).sum(1), c[:, -1]], 1).float()
+
+
+def ray_surface(net, top, bot, S, *, include_end_pt=False, zero_oob=False, early_out=True):
+    """The surface statistics of rays top -> bot from the density alone -> `RaySurface`.  S samples at t_s = s / S (s / (S - 1) with include_end_pt),
+    every one counting; zero_oob: a sample outside [-1,1]^3 gets delta 0 (mg_Img_Eval.py:42); early_out: a workgroup whose rays have all passed
+    optical depth 18 skips their remaining samples (what is left of them is below exp(-18) = 1.5e-8).
+
+    On a fused bf16x3 model (widths 64 / 256 / 512) one launch of `season_nerf::ray_surface` per chunk: the density-only network with the transmittance
+    scan in the kernel, 16 bytes out per ray and no [R,S] array.  Anything else (int8-resolved models, a width without a fused kernel, the one-term
+    "bf16" mode, a module in training mode) gets the same four numbers from its own density pass and float64 sums: slower, and correct."""
+    with torch.no_grad():
+        dev = top.device
+        top, bot = top.float().contiguous(), bot.float().contiguous()
+        R = top.shape[0]
+        tv = sample_parameters_on(dev, S, eval_mode=True, include_end_pt=include_end_pt)
+        out = torch.empty(R, 4, device=dev)
+        if _walks(net) and not net.training:
+            from .network import _ops
+            flags = (2 if zero_oob else 0) | (0 if early_out else 4)
+            chunk = 1 << 22
+            for i in range(0, R, chunk):
+                j = min(R, i + chunk)
+                out[i:j] = _ops().ray_surface(net.device_model(), top[i:j], bot[i:j], tv, flags)
+        else:
+            # sized as _exact_solar_visibility sizes the layer-wise engine's chunks: ~32 [points x width] fp32 arrays, ~12 GB of workspace
+            chunk = min(1 << 16, max(64, int(12e9 / (128.0 * net.layer_width)) // S))
+            for i in range(0, R, chunk):
+                j = min(R, i + chunk)
+                out[i:j] = _surface_layerwise(net, top[i:j], bot[i:j], tv, S, zero_oob)
+        delta = torch.sqrt(torch.sum((top.double() - bot.double()) ** 2, 1)) / S
+        return RaySurface(out[:, 0].contiguous(), out[:, 1].contiguous(), out[:, 2].contiguous(), out[:, 3].contiguous(), S, delta)
+
+
+def height_map(the_network, shape, n_samples, device):
+    """`eval_HM`'s height estimate (T_NeRF_Eval_Utils/Eval_funcs.py:299-319) in cube units, without its confidence range and alignment: column
+    (i, j) of the H x W lattice stands at x = 2 i / H - 1, y = 2 j / W - 1 and is sampled at z = 1 - 2 k / n, k = 0 .. n - 1, with delta = 2 / n,
+    i.e. the ray top z = +1 -> bot z = -1 at t_k = k / n.  -> {"Est_HM": sum_k P_Surf linspace(1, -1, n) / sum_k P_Surf, "P_Surf_sum": sum_k P_Surf},
+    float64 numpy [H, W]."""
+    H, W = int(shape[0]), int(shape[1])
+    dev = torch.device(device)
+    ii, jj = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    xy = np.stack([ii.reshape(-1) * (1.0 / H) * 2 - 1, jj.reshape(-1) * (1.0 / W) * 2 - 1], 1)      # XYZ * s * 2 - 1 in float64 (Eval_funcs.py:302,311)
+    top = _f32(np.concatenate([xy, np.ones([H * W, 1])], 1), dev)
+    bot = _f32(np.concatenate([xy, -np.ones([H * W, 1])], 1), dev)
+    rs = ray_surface(the_network, top, bot, n_samples)
+    return {"Est_HM": rs.expected_height().reshape(H, W).cpu().numpy(), "P_Surf_sum": rs.opacity().reshape(H, W).cpu().numpy()}
+
+
 # ------------------------------------------------------------------------------------------------ path A
 class Quick_Run_Net:
     def __init__(self, network, args, world_center_LLA, World_2_Local_H, device, max_input_size=50000, use_tqdm=False,
@@ -181,12 +281,22 @@ class Quick_Run_Net:
                 imgs["Estimated_Shadow_Mask"] = est
         return imgs, mask
 
-    def get_DSM(self, out_img_size, region=None):
-        """Nadir rays; height = sum_s PS * linspace(1, -1, 96)  (Quick_Run.py:207-226, :37-40; 96 hard-coded there)."""
+    def get_DSM(self, out_img_size, region=None, *, density_only=False):
+        """Nadir rays; height = sum_s PS * linspace(1, -1, 96)  (Quick_Run.py:207-226, :37-40; 96 hard-coded there).
+
+        density_only (keyword-only, not in the reference): the same rays through `ray_surface` - the density-only network with the compositing
+        inside the kernel - instead of the whole field program, its per-sample arrays and a compositing launch.  Same image, NaN where there is no ray."""
         with torch.no_grad():
             d = self._get_input_dict([90, 0], [90, 0], 0.0, out_img_size, region)
-            out = self.eval_tool.eval(d, self.network, -1, False)
             hw = out_img_size if isinstance(out_img_size, tuple) else (out_img_size, out_img_size)
+            if density_only:
+                if self.n_samples != 96:
+                    raise ValueError(f"get_DSM: the height levels are linspace(1, -1, 96) (Quick_Run.py:39); n_samples is {self.n_samples}")
+                img = np.full([hw[0], hw[1]], np.nan)
+                if d["Top"].shape[0] > 0:
+                    img[d["XY"][:, 0], d["XY"][:, 1]] = ray_surface(self.network, d["Top"], d["Bot"], 96).dsm().cpu().numpy()
+                return img
+            out = self.eval_tool.eval(d, self.network, -1, False)
             img = np.full([hw[0], hw[1]], np.nan)
             z = torch.linspace(1, -1, 96, device=out["PS"].device, dtype=torch.float64).reshape(1, -1, 1)
             img[d["XY"][:, 0], d["XY"][:, 1]] = (out["PS"].double() * z).sum(1)[:, 0].cpu().numpy()
