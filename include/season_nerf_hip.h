@@ -271,6 +271,23 @@ int snerf_composite_sun_walk(int64_t n_rays, int n_samples, int n_classes, int n
 int snerf_field_ray_surface(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot,
                             const float* d_tvals, int flags, float* d_out, void* stream);
 
+/* ---- shadow walk: the reference's shadow test with the sun-ray walk scored inside the field kernel.
+ * The reference ends an evaluation by comparing, sample by sample along rays laid through ground points towards the sun, the solar visibility the network
+ * has learned with the one its own density implies: eval_shadow_data and shadow_anaylysis (T_NeRF_Eval_Utils/mg_Shadow_Eval.py:72-104,134-163).  One launch
+ * walks the S samples of every ray from t = 0 (d_top) to d_bot, 32 per pass, through the trunk, the density head and fc_solar_1..4 with the ray's own sun
+ * direction d_sun [n_rays,3] (not normalised here: the vector goes into the encoding as the caller gives it), forms
+ *   PV_s  = exp(-sum_{j<s} rho_j delta_j)        the exact visibility, get_PV's exclusive prefix (delta = ||top - bot|| / S, all S samples counting)
+ *   vis_s = sigmoid(fc_solar_4)                  the learned one
+ *   PS_s  = PV_s (1 - exp(-rho_s delta_s))
+ * and stores eight numbers per ray, d_out [n_rays,8] (32-byte aligned):
+ *   [0] number of samples with PV > .5 and vis > .5      [1] with PV > .5      [2] with vis > .5          (floats holding integers)
+ *   [3] sum_s (PV_s - vis_s)^2       [4] sum_s |PV_s - vis_s|       [5] sum_s PS_s vis_s       [6] sum_s PS_s       [7] sum_s rho_s delta_s
+ * The sums over rays, and the scores formed from them, are the caller's.  flags bit1 = a sample outside [-1,1]^3 gets delta 0
+ * (deltas[Zero_Tool(Xs)] = 0); no other bit is read, and there is no early-out: the learned visibility behind a surface is scored like any other.
+ * SNERF_E_INVALID for bad arguments and unless the model's resolved precision is SNERF_PREC_BF16X3 (width 64, 256 or 512). */
+int snerf_field_shadow_walk(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_sun,
+                            const float* d_tvals, int flags, float* d_out, void* stream);
+
 /* ---- training engine: the device side of Net_tool.train_step (mg_run_NeRF.py:288-326) = All_in_One_Eval.get_loss
  * (Eval_Tools_2.py:340-459) forward passes in .train() mode, backward, Adam.  Layer-wise, fp32 storage, 3-term split bf16 MFMA
  * GEMMs (exact-fp32 MFMA under SNERF_TRAIN_GEMM=fp32), batch-statistics BatchNorm1d (momentum 0.01, misc.py:170) with running-stat EMA, activations stashed in HBM.

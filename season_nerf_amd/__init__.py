@@ -16,6 +16,8 @@ __all__ = ["T_NeRF", "SineLayer", "All_in_One_Eval", "sample_parameters", "get_P
            "get_imgs_from_Img_Dict", "get_imgs_from_Img_Dict_t_step", "render_season_sweep", "world_angle_2_local_vec",
            "encode_time", "component_render_sun_walk", "render_sun_season_walk", "SunWalkRender", "RaySurface", "ray_surface", "height_map", "parallel", "raytable", "FusedAdam", "TrainEngine", "create_solor_rays_uniform", "_lib"]
 from .adaptive_loss import AdaptiveLossFunction  # noqa: E402,F401
+from . import shadow_eval  # noqa: E402,F401
+from .shadow_eval import ShadowWalk, shadow_walk, eval_shadow_data, shadow_anaylysis, Test_Shadow_Points  # noqa: E402,F401
 from . import validation  # noqa: E402,F401
 from .validation import DSM_Distance, eval_img, image_error  # noqa: E402,F401
 from .trainer import GraphedTrainStep, Net_tool, T_NeRF_Net_Tool  # noqa: E402,F401

@@ -63,6 +63,16 @@ struct RaySurfaceArgs {
     float* out;
 };
 
+// Shadow walk (shadow_walk_kernel / shadow_walk_ks_kernel, mlp_device.h RayShadow): the ray surface's walk through the layers of variant 1 with the
+// reference's shadow test inside.  m as in RaySurfaceArgs, with m.stream = the field stream cycled over the layers of variant 1; sun [n,3] = one sun
+// direction per ray, as the caller gives it; out [n,8] = {n(PV > .5 and vis > .5), n(PV > .5), n(vis > .5), sum (PV - vis)^2, sum |PV - vis|, sum PS vis,
+// sum PS, optical depth walked} per ray, 32-byte aligned.
+struct ShadowWalkArgs {
+    MlpArgs m;
+    const float* sun;
+    float* out;
+};
+
 struct CompOutDev {
     float *rgb, *albedo, *pv, *pe, *ps, *delta, *shadow, *acc, *surf_loc, *surf_dist;
 };
@@ -141,9 +151,12 @@ __host__ __device__ inline int64_t field_tiles(int64_t n, int variant, int pts, 
 hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_fused(void (*kernel)(RaySurfaceArgs), int64_t n_tiles, int block, int lds_bytes, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_fused(void (*kernel)(ShadowWalkArgs), int64_t n_tiles, int block, int lds_bytes, const ShadowWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_ray_surface_ks(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_shadow_walk(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
+hipError_t launch_shadow_walk_ks(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);                          // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)

@@ -998,4 +998,80 @@ hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStrea
     return hipErrorInvalidValue;
 }
 
+// =====================================================================================================
+// Shadow walk: the ray surface's walk (a wave owns a ray, 32 samples per pass from t = 0 downwards) through the layers of VARIANT 1 - trunk, density head,
+// fc_solar_1..4 with the ray's own sun direction - and the reference's shadow test in the pass end (mlp_device.h RayShadow; mg_Shadow_Eval.py:72-104,
+// 134-163): eight sums out per ray, no per-sample array, no transmittance launch.  Every pass of every ray runs.
+template <int W>
+__global__ __launch_bounds__(256, 1) void shadow_walk_kernel(const ShadowWalkArgs SA) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MlpArgs& A = SA.m;
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    lds_char* lds = (lds_char*)smem;
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5;
+
+    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
+
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
+    __syncthreads();
+
+    const int64_t n_tiles = field_tiles(A.n, 3, TILE_PTS, 4);      // a tile is a group of 4 rays, one per wave
+    const int passes = (A.n_samples + 31) / 32;
+    int pass = 0;
+    RayShadow rs;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;) {
+        float x0, x1, x2, s0, s1, s2;
+        rayshadow_point(rs, A, SA.sun, tile, 4, wave, pass, lane, x0, x1, x2, s0, s1, s2);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KW = W / 16, KW2 = W2 / 16;
+        Frag hA[KW], hB[KW];
+        f32x16 raw;
+#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
+    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
+        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
+        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
+        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        Frag x1f[KW2];
+        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
+        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+        const float rho_raw = raw[3];       // lane-half 0 holds the density row
+        Frag ps[PESUN_KS];
+        make_pe_sun(s0, s1, s2, h, ps);
+        Frag sA[KW2], sB[KW2];
+        LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
+        LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
+        LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
+        LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
+#undef LAYER
+        const float sv_raw = raw[0];
+        RAYSHADOW_PASS_END(rs, A, SA.out, tile, pass, passes, 4, wave, true, lane, rho_raw, sv_raw);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_fused(void (*kernel)(ShadowWalkArgs), int64_t n_tiles, int block, int lds_bytes, const ShadowWalkArgs& a, int n_cu, hipStream_t st) {
+    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
+}
+
+hipError_t launch_shadow_walk(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st) {
+    if (W == 512) return launch_shadow_walk_ks(W, a, n_cu, st);
+    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats);
+    const int64_t tiles = field_tiles(a.m.n, 3, TILE_PTS, 4);
+    if (W == 64) return launch_fused(shadow_walk_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
+    if (W == 256) return launch_fused(shadow_walk_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace snerf

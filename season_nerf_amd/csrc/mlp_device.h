@@ -351,6 +351,98 @@ __device__ __forceinline__ void raysurf_end(const RaySurf& q, const MlpArgs& A, 
         }                                                                                                                       \
     }
 
+// Shadow walk (shadow_walk_kernel, shadow_walk_ks_kernel): the ray surface's walk through the layers of VARIANT 1 - density head and fc_solar_1..4 -
+// with the reference's shadow test in the pass end (T_NeRF_Eval_Utils/mg_Shadow_Eval.py:72-104,134-163): per sample the exact visibility PV (get_PV: the
+// exclusive-prefix transmittance along the sun ray, formed as raysurf_add forms it) against the learned one, vis = sigmoid(fc_solar_4).  Seven partial
+// sums and the carry live across the MFMA chain; no early-out, since the learned visibility behind a surface is scored like any other.
+struct RayShadow {
+    float carry;                    // optical depth of the samples of the passes walked so far (the same in lanes 0..31, 0 in the others): slot 7
+    float tp, ne, nv;               // this lane's counts of samples with PV > .5 and vis > .5, with PV > .5, with vis > .5 (floats: exact below 2^24)
+    float se, ae;                   // sum (PV - vis)^2, sum |PV - vis|
+    float psv, acc;                 // sum PS vis, sum PS
+};
+// sample position of this lane in pass p (raysum_point's) and the ray's sun direction; the first pass of a ray clears its sums.  The sun direction is a
+// per-tile input: loaded here, before the MFMA chain (field_tile_inputs).
+__device__ __forceinline__ void rayshadow_point(RayShadow& q, const MlpArgs& A, const float* sun, int64_t group, int waves, int wave, int p, int lane,
+                                                float& x0, float& x1, float& x2, float& s0, float& s1, float& s2) {
+    RaySum unused;
+    raysum_point(unused, A, group, waves, wave, p, lane, x0, x1, x2);
+    const int64_t ray = group * waves + wave;
+    const int64_t r = ray < A.n ? ray : A.n - 1;
+    s0 = sun[r * 3]; s1 = sun[r * 3 + 1]; s2 = sun[r * 3 + 2];
+    if (p == 0) { q.carry = 0.f; q.tp = 0.f; q.ne = 0.f; q.nv = 0.f; q.se = 0.f; q.ae = 0.f; q.psv = 0.f; q.acc = 0.f; }
+}
+// The pass's 32 samples into the sums.  y, the scan, PV, PE and PS are raysurf_add's, operation for operation (acc and carry come out as the ray surface's);
+// a basic block of its own and the end points and t re-read behind the chain, for the reasons given in raysum_add.  Padding samples (s >= S) count nowhere.
+__device__ __forceinline__ void rayshadow_add(RayShadow& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float rho_raw, float sv_raw) {
+    if (lane >= 32) return;
+    const int64_t ray = group * waves + wave;
+    const int64_t r = ray < A.n ? ray : A.n - 1;
+    const float tx = A.top[r * 3], ty = A.top[r * 3 + 1], tz = A.top[r * 3 + 2];
+    const float bx = A.bot[r * 3], by = A.bot[r * 3 + 1], bz = A.bot[r * 3 + 2];
+    const float dx = tx - bx, dy = ty - by, dz = tz - bz;
+    float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    const int s = raysum_block(A, p) * 32 + lane;
+    const bool in = s < A.n_samples;
+    const float t = A.tvals[in ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
+    const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
+    const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
+    const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
+    if ((A.ray_flags & 2) && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+    const float y = in ? softplus_f(rho_raw) * delta : 0.f;
+    float incl = y;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+        const float u = __shfl_up(incl, o, 32);
+        if (lane >= o) incl += u;
+    }
+    const float below = __shfl_up(incl, 1, 32);
+    const float excl = q.carry + (lane == 0 ? 0.f : below);
+    q.carry += __shfl(incl, 31, 32);
+    const float pv = expf(-excl);
+    const float pe = 1.f - expf(-y);
+    const float ps = in ? pv * pe : 0.f;
+    const float vis = sigmoid_f(sv_raw);
+    const bool ex = in && pv > .5f, es = in && vis > .5f;
+    const float d = in ? pv - vis : 0.f;
+    q.tp += (ex && es) ? 1.f : 0.f;
+    q.ne += ex ? 1.f : 0.f;
+    q.nv += es ? 1.f : 0.f;
+    q.se += d * d;
+    q.ae += fabsf(d);
+    q.psv += ps * vis;
+    q.acc += ps;
+}
+// the ray's eight numbers {n(PV > .5 and vis > .5), n(PV > .5), n(vis > .5), sum (PV - vis)^2, sum |PV - vis|, sum PS vis, sum PS, optical depth walked}:
+// one 32-byte row, two 16-byte stores by lane 0
+__device__ __forceinline__ void rayshadow_end(const RayShadow& q, const MlpArgs& A, float* out, int64_t ray, int lane) {
+    float tp = q.tp, ne = q.ne, nv = q.nv, se = q.se, ae = q.ae, psv = q.psv, acc = q.acc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        tp += __shfl_xor(tp, o, 64);
+        ne += __shfl_xor(ne, o, 64);
+        nv += __shfl_xor(nv, o, 64);
+        se += __shfl_xor(se, o, 64);
+        ae += __shfl_xor(ae, o, 64);
+        psv += __shfl_xor(psv, o, 64);
+        acc += __shfl_xor(acc, o, 64);
+    }
+    if (lane == 0 && ray < A.n) {
+        *reinterpret_cast<f32x4*>(out + ray * 8) = f32x4{tp, ne, nv, se};
+        *reinterpret_cast<f32x4*>(out + ray * 8 + 4) = f32x4{ae, psv, acc, q.carry};
+    }
+}
+// The end of a pass, as RAYSURF_PASS_END without its vote: every pass of every ray runs.
+#define RAYSHADOW_PASS_END(q, A, out, tile, pass, passes, rays, ray_wave, writer, lane, rho_raw, sv_raw)                            \
+    {                                                                                                                           \
+        rayshadow_add(q, A, tile, rays, ray_wave, pass, lane, rho_raw, sv_raw);                                                 \
+        if (++pass == (passes)) {                                                                                               \
+            if (writer) rayshadow_end(q, A, out, tile * (rays) + (ray_wave), lane);                                             \
+            pass = 0;                                                                                                           \
+            tile += gridDim.x;                                                                                                  \
+        }                                                                                                                       \
+    }
+
 // output non-linearities of the field program (T_NeRF_net_v2.py:91-98) for one point; called by the lanes that hold the head rows
 template <int VARIANT>
 __device__ __forceinline__ void store_field_outputs(const snerf_field_out_dev& O, int64_t n, int C, float x0, float x1, float x2,

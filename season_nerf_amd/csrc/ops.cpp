@@ -21,6 +21,7 @@
 //   season_nerf::composite_sun_walk(top, bot, tvals, rho, col_raw, adjust, solar_vis[M,R,S], sky[M,3], class_vecs[T,C], flags, deltas?)
 //        -> [shaded[M,T,R,3], season[T,R,3], base[R,3], raw_shadow[M,R], shadow_adjust[M,R,3]]           the M x T grid of a view
 //   season_nerf::ray_surface(model, top[R,3], bot[R,3], tvals[S], flags) -> [R,4] {sum PS, sum PS t, sum PS s, optical depth}      height maps from a density-only ray pass
+//   season_nerf::shadow_walk(model, top[R,3], bot[R,3], sun[R,3], tvals[S], flags) -> [R,8]           the shadow test's per-ray sums (mg_Shadow_Eval.py:72-104,134-163)
 //   season_nerf::fused_adam_(param!, grad, m!, v!, lr, b1, b2, eps, step) -> ()                         mg_run_NeRF.py:312-320
 // Training engine (csrc/train.cpp; `trainer` = the snerf_trainer handle a season_nerf_amd.training.TrainEngine owns and has bound to its
 // parameter / gradient / workspace tensors).  The forward ops are functional in their tensor arguments (torch.library.register_autograd
@@ -294,6 +295,25 @@ Tensor ray_surface(int64_t model, const Tensor& top, const Tensor& bot, const Te
     Tensor out = at::empty({R, 4}, top.options());
     if (R == 0) return out;
     ck(snerf_field_ray_surface((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(tvals), (int)flags, mptr(out), cur_stream(top)), "ray_surface");
+    return out;
+}
+
+// Shadow walk (include/season_nerf_hip.h snerf_field_shadow_walk): the eight sums per ray the reference's shadow scores are formed from.  The model
+// travels as an integer, as in ray_surface.
+Tensor shadow_walk(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& sun, const Tensor& tvals, int64_t flags) {
+    TORCH_CHECK(model != 0, "season_nerf::shadow_walk: NULL model handle");
+    check_shape(top, "top", -1, 3);
+    const int64_t R = top.size(0);
+    check_shape(bot, "bot", R, 3);
+    check_shape(sun, "sun", R, 3);
+    check_dev_f32(tvals, "tvals");
+    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    TORCH_CHECK(flags == 0 || flags == 2, "flags must be 0 or 2 (zero delta outside the cube), got ", flags);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
+    Tensor out = at::empty({R, 8}, top.options());
+    if (R == 0) return out;
+    ck(snerf_field_shadow_walk((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(sun), fptr(tvals), (int)flags, mptr(out),
+                               cur_stream(top)), "shadow_walk");
     return out;
 }
 
@@ -604,6 +624,7 @@ TORCH_LIBRARY(season_nerf, m) {
           "int flags, bool classic) -> Tensor[]");
     m.def("sun_walk_fwd(int model, Tensor top, Tensor bot, Tensor tvals, Tensor suns, Tensor? classes) -> Tensor[]");
     m.def("ray_surface(int model, Tensor top, Tensor bot, Tensor tvals, int flags) -> Tensor");
+    m.def("shadow_walk(int model, Tensor top, Tensor bot, Tensor sun, Tensor tvals, int flags) -> Tensor");
     m.def("composite_sun_walk(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
           "int flags, Tensor? deltas=None) -> Tensor[]");
     m.def("fused_adam_(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, int step) -> ()");
@@ -637,6 +658,7 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("sun_walk_fwd", sun_walk_fwd);
     m.impl("composite_sun_walk", composite_sun_walk);
     m.impl("ray_surface", ray_surface);
+    m.impl("shadow_walk", shadow_walk);
     m.impl("trainer_adam_step_", trainer_adam_step_);
     m.impl("trainer_adam_step_dev_", trainer_adam_step_dev_);
     m.impl("trainer_zero_grad_", trainer_zero_grad_);

@@ -58,6 +58,10 @@ def _register_fakes():
     def _(model, top, bot, tvals, flags):
         return top.new_empty(top.shape[0], 4)
 
+    @reg("season_nerf::shadow_walk")
+    def _(model, top, bot, sun, tvals, flags):
+        return top.new_empty(top.shape[0], 8)
+
     @reg("season_nerf::fused_adam_")
     def _(param, grad, m, v, lr, beta1, beta2, eps, step):
         return None
