@@ -288,6 +288,27 @@ int snerf_field_ray_surface(const snerf_model* m, int64_t n_rays, int n_samples,
 int snerf_field_shadow_walk(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_sun,
                             const float* d_tvals, int flags, float* d_out, void* stream);
 
+/* ---- frame walk: the frames of the reference's fly-through films with the shading and compositing inside the field kernel.
+ * The reference renders a film frame from a slab of parallel rays (sample_rays_projective, T_NeRF_Eval_Utils/mg_movie_maker.py:52-70): T_NeRF.forward on
+ * every sample, the density zeroed outside the cube, and a compositing of its own with the learned visibility applied per sample (get_Img.eval_rays,
+ * :108-177; eval_rays_advanced re-runs the network once per season shown, :179-187).  One launch walks the S >= 2 samples of every ray from d_top (t = 0) to
+ * d_bot, 32 per pass, through the whole field network - trunk, head, fc_solar_1..4, the colour-adjust branch - and forms, with the frame's one `delta`
+ * (||top - bot|| / (S - 1), the spacing of end-point-inclusive samples; d_tvals holds t_s = s / (S - 1)),
+ *   PS_s    = exp(-sum_{j<s} rho_j delta) (1 - exp(-rho_s delta))
+ *   vis_s   = sigmoid(fc_solar_4),   shade_s = vis_s + (1 - vis_s) sky
+ *   col_k,s = sigmoid(col_raw_s + class_vecs[k] @ adjust_s)            for the n_times seasons, 1 <= n_times <= 4: only the class vector depends on the time
+ * and stores sixteen numbers per ray, d_out [n_rays,16] (64-byte aligned):
+ *   [3k .. 3k+2] sum_s PS_s shade_s col_k,s   (Out_Img of season k, :153-161; 0 for k >= n_times)
+ *   [12] sum_s PS_s        [13] sum_s PS_s s   (HM = 2 [13] / (S - 1), :185-186)        [14] optical depth walked        [15] sum_s PS_s vis_s
+ * The same for every ray of the launch, all in device memory: d_sun [3] (into the encoding as given), d_sky [3] (sigmoided: it depends on the sun only),
+ * d_class_vecs [n_times, C].  flags bit1 = a sample outside [-1,1]^3 gets delta 0 (Rho[Zero_Tool(Xs)] = 0, :141); bit2 = no early-out: otherwise a
+ * workgroup whose rays have all passed optical depth 18 skips their remaining passes (every further PS < exp(-18)).
+ * SNERF_E_INVALID for a NULL input, n_rays < 0, n_samples < 2, n_times outside 1..4, a delta that is not finite and positive, a d_out off 64 bytes, and
+ * unless the model's resolved precision is SNERF_PREC_BF16X3 (width 64, 256 or 512). */
+int snerf_field_frame_walk(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals, float delta,
+                           const float* d_sun, const float* d_sky, int n_times, const float* d_class_vecs, int flags, float* d_out, void* stream);
+#define SNERF_MAX_FRAME_TIMES 4
+
 /* ---- training engine: the device side of Net_tool.train_step (mg_run_NeRF.py:288-326) = All_in_One_Eval.get_loss
  * (Eval_Tools_2.py:340-459) forward passes in .train() mode, backward, Adam.  Layer-wise, fp32 storage, 3-term split bf16 MFMA
  * GEMMs (exact-fp32 MFMA under SNERF_TRAIN_GEMM=fp32), batch-statistics BatchNorm1d (momentum 0.01, misc.py:170) with running-stat EMA, activations stashed in HBM.

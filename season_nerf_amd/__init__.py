@@ -18,6 +18,8 @@ __all__ = ["T_NeRF", "SineLayer", "All_in_One_Eval", "sample_parameters", "get_P
 from .adaptive_loss import AdaptiveLossFunction  # noqa: E402,F401
 from . import shadow_eval  # noqa: E402,F401
 from .shadow_eval import ShadowWalk, shadow_walk, eval_shadow_data, shadow_anaylysis, Test_Shadow_Points  # noqa: E402,F401
+from . import movie  # noqa: E402,F401
+from .movie import FrameWalk, frame_walk, frame_end_planes, sample_rays_projective, get_Img  # noqa: E402,F401
 from . import validation  # noqa: E402,F401
 from .validation import DSM_Distance, eval_img, image_error  # noqa: E402,F401
 from .trainer import GraphedTrainStep, Net_tool, T_NeRF_Net_Tool  # noqa: E402,F401

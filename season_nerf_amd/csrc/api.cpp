@@ -633,6 +633,41 @@ int snerf_field_shadow_walk(const snerf_model* m, int64_t n_rays, int n_samples,
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "shadow walk kernel launch");
 }
 
+int snerf_field_frame_walk(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals, float delta,
+                           const float* d_sun, const float* d_sky, int n_times, const float* d_class_vecs, int flags, float* d_out, void* stream) {
+    if (n_rays < 0 || n_samples < 2 || !d_top || !d_bot || !d_tvals || !d_sun || !d_sky || !d_class_vecs || !d_out || ((uintptr_t)d_out & 63) ||
+        n_times < 1 || n_times > kMaxFrameTimes || !std::isfinite(delta) || !(delta > 0.f))
+        return fail(SNERF_E_INVALID, "snerf_field_frame_walk: bad argument (n_samples >= 2, n_times in [1," + std::to_string(kMaxFrameTimes) +
+                                         "], delta finite and positive, d_out 64-byte aligned)");
+    int rc = check_ready(m);
+    if (rc) return rc;
+    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
+        return fail(SNERF_E_INVALID, "snerf_field_frame_walk: the frame-walk kernels exist for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
+    if (n_rays == 0) return SNERF_OK;
+    const bool ks = ks_width(m->W);
+    FrameWalkArgs a{};
+    a.m.stream = ks ? m->d_stream_ks : m->d_stream[PROG_FIELD];
+    a.m.stream_bytes = (uint32_t)(ks ? field_variant_chunks_ks(m->W, m->C, 0) : field_variant_chunks(m->W, m->C, 0)) * kChunkBytes;
+    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
+    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
+    a.m.n = n_rays;                // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples
+    a.m.n_classes = m->C;
+    a.m.top = d_top;
+    a.m.bot = d_bot;
+    a.m.tvals = d_tvals;
+    a.m.n_samples = n_samples;
+    a.m.group_size = 1;
+    a.m.ray_flags = (flags & 6) | 8;      // bit 3: passes from t = 0 downwards, the order of the prefix
+    a.sun = d_sun;
+    a.sky = d_sky;
+    a.class_vecs = d_class_vecs;
+    a.n_times = n_times;
+    a.delta = delta;
+    a.out = d_out;
+    hipError_t e = launch_frame_walk(m->W, a, m->n_cu, (hipStream_t)stream);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "frame walk kernel launch");
+}
+
 static int composite_rays(int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals,
                           const float* d_rho, const float* d_col, const float* d_solar_vis, const float* d_sky,
                           int flags, const float* d_rho_prior, float trust, const float* d_trust, const snerf_composite_out* out, void* stream) {

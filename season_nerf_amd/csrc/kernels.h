@@ -73,6 +73,21 @@ struct ShadowWalkArgs {
     float* out;
 };
 
+// Film frame (frame_walk_kernel / frame_walk_ks_kernel, mlp_device.h RayFrame): the ray surface's walk through the layers of variant 0 with the shading and
+// compositing of the reference's film frames inside.  m as in RaySurfaceArgs, with m.stream = the unchanged variant-0 field stream.  The same for every ray:
+// sun [3], sky [3] (sigmoided), class_vecs [n_times, m.n_classes] with 1 <= n_times <= kMaxFrameTimes, delta.  out [n,16] = {rgb of season k at 3k..3k+2
+// (0 for k >= n_times), [12] sum PS, [13] sum PS s, [14] optical depth walked, [15] sum PS vis} per ray, 64-byte aligned.
+constexpr int kMaxFrameTimes = 4;
+struct FrameWalkArgs {
+    MlpArgs m;
+    const float* sun;
+    const float* sky;
+    const float* class_vecs;
+    int n_times;
+    float delta;
+    float* out;
+};
+
 struct CompOutDev {
     float *rgb, *albedo, *pv, *pe, *ps, *delta, *shadow, *acc, *surf_loc, *surf_dist;
 };
@@ -152,11 +167,14 @@ hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int
 hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_fused(void (*kernel)(RaySurfaceArgs), int64_t n_tiles, int block, int lds_bytes, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_fused(void (*kernel)(ShadowWalkArgs), int64_t n_tiles, int block, int lds_bytes, const ShadowWalkArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_fused(void (*kernel)(FrameWalkArgs), int64_t n_tiles, int block, int lds_bytes, const FrameWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_ray_surface_ks(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_shadow_walk(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_shadow_walk_ks(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_frame_walk(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st);                      // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
+hipError_t launch_frame_walk_ks(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);                          // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)

@@ -1074,4 +1074,95 @@ hipError_t launch_shadow_walk(int W, const ShadowWalkArgs& a, int n_cu, hipStrea
     return hipErrorInvalidValue;
 }
 
+// =====================================================================================================
+// Film frame: the ray surface's walk (a wave owns a ray, 32 samples per pass from t = 0 downwards, the early-out vote) through the layer list of
+// mlp_kernel<PROG_FIELD, W, 0> on its unchanged stream and bias table, and the shading and compositing of the reference's film frames in the pass end
+// (mlp_device.h RayFrame; mg_movie_maker.py:108-187): sixteen floats out per ray, up to kMaxFrameTimes seasons from one field pass, no per-sample array.
+// The launch's sun direction, sky colour and class vectors are staged in LDS behind the vote words (sun_walk_kernel does the same with its suns).
+template <int W>
+__global__ __launch_bounds__(256, 1) void frame_walk_kernel(const FrameWalkArgs FA) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MlpArgs& A = FA.m;
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    lds_char* lds = (lds_char*)smem;
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
+    __attribute__((address_space(3))) float* fin = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + A.bias_floats * 4 + kVoteBytes);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5;
+
+    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
+    frame_stage_inputs(FA, fin);
+
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
+    __syncthreads();
+
+    const int64_t n_tiles = field_tiles(A.n, 3, TILE_PTS, 4);      // a tile is a group of 4 rays, one per wave
+    const int passes = (A.n_samples + 31) / 32;
+    int pass = 0;
+    RayFrame rf;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;) {
+        float x0, x1, x2;
+        rayframe_point(rf, A, tile, 4, wave, pass, lane, x0, x1, x2);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KW = W / 16, KW2 = W2 / 16;
+        Frag hA[KW], hB[KW];
+        f32x16 raw;
+#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
+    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
+        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
+        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
+        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        Frag x1f[KW2];
+        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
+        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+        const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
+        float sv_raw;
+        {
+            const float s0 = fin[0], s1 = fin[1], s2 = fin[2];      // wave-uniform
+            Frag ps[PESUN_KS];
+            make_pe_sun(s0, s1, s2, h, ps);
+            Frag sA[KW2], sB[KW2];
+            LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
+            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
+            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
+            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
+            sv_raw = raw[0];
+        }
+        LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr);
+        LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
+        LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
+        LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw);
+        float adj[3 * C_MAX];
+#pragma unroll
+        for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
+#undef LAYER
+        RAYFRAME_PASS_END(rf, A, FA, fin, tile, pass, passes, 4, wave, wave, 4, true, lane, col_r, col_g, col_b, rho_raw, sv_raw, adj, bias_lds + A.bias_floats);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_fused(void (*kernel)(FrameWalkArgs), int64_t n_tiles, int block, int lds_bytes, const FrameWalkArgs& a, int n_cu, hipStream_t st) {
+    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
+}
+
+hipError_t launch_frame_walk(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st) {
+    if (a.n_times < 1 || a.n_times > kMaxFrameTimes || a.m.n_classes > kMaxClasses) return hipErrorInvalidValue;      // the kernels stage kFrameLdsFloats floats in LDS
+    if (W == 512) return launch_frame_walk_ks(W, a, n_cu, st);
+    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats) + kFrameLdsFloats * 4;
+    const int64_t tiles = field_tiles(a.m.n, 3, TILE_PTS, 4);
+    if (W == 64) return launch_fused(frame_walk_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
+    if (W == 256) return launch_fused(frame_walk_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace snerf

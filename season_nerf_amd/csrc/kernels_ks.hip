@@ -782,4 +782,104 @@ int field_variant_chunks_ks(int W, int C, int variant) {
 int mlp_ks_lds_bytes(int bias_floats) { return ks_lds_bytes(bias_floats); }
 int mlp_ks_tile_points() { return KS_TILE_PTS; }
 
+// Film frame at this width: the ray surface's walk (a wave pair owns a ray, the early-out vote) through the layer list of mlp_ks_kernel's VARIANT 0 on its
+// unchanged stream, with the film frame's shading and compositing in the pass end (kernels.hip frame_walk_kernel, mlp_device.h RayFrame).  Both waves of a
+// pair hold the same head rows and the same sums and vote alike; wave 0 of the pair stores.  F_AC is followed by the next pass's F_FC1, as in VARIANT 0.
+// The launch's inputs wait in LDS behind the vote words, as sun_walk_ks_kernel's suns do.
+template <int W>
+__global__ __launch_bounds__(256, 1) void frame_walk_ks_kernel(const FrameWalkArgs FA) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MlpArgs& A = FA.m;
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    lds_char* lds = (lds_char*)smem;
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
+    __attribute__((address_space(3))) float* fin = (__attribute__((address_space(3))) float*)(lds + ks_lds_bytes(A.bias_floats));
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pair = wave >> 1, par = wave & 1;
+    const int h = lane >> 5;
+
+    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
+    frame_stage_inputs(FA, fin);
+    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
+    KsCtx cx;
+    cx.lds = lds;
+    cx.par_off = par * KS_PAR_BYTES;
+    {
+        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
+        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
+        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
+    }
+    __attribute__((address_space(3))) float* vote_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + (A.bias_floats + 32) * 4 + 4 * KS_XBUF_BYTES);
+
+    Pend pd;
+    pd.goff = 0;
+    pd.wr = 0;
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
+    __syncthreads();
+
+    const int64_t n_tiles = field_tiles(A.n, 3, KS_TILE_PTS, 2);      // a tile is a group of 2 rays, one per wave pair
+    const int passes = (A.n_samples + 31) / 32;
+    int pass = 0;
+    RayFrame rf;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;) {
+        float x0, x1, x2;
+        rayframe_point(rf, A, tile, 2, pair, pass, lane, x0, x1, x2);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KH = W / 32, KH2 = W2 / 32;
+        constexpr int NBW = W / 64, NBW2 = W2 / 64;
+        Frag hA[KH], hB[KH];
+#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
+#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
+#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
+        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
+        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
+        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
+        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
+        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
+        Frag x1f[KH2];
+        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
+        f32x16 raw = HEADL(F_HEAD, KH2, x1f);
+        const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
+        float sv_raw;
+        {
+            const float s0 = fin[0], s1 = fin[1], s2 = fin[2];      // wave-uniform
+            Frag ps[PESUN_KS];
+            make_pe_sun(s0, s1, s2, h, ps);
+            Frag sA[KH2], sB[KH2];
+            LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);
+            LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);
+            LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);
+            raw = HEADL(F_S4, KH2, sA);
+            sv_raw = raw[0];
+        }
+        LAYER(F_A1, NBW, KH2, 0, x1f, nullptr, hA);
+        LAYER(F_A2, NBW, KH, 0, hA, nullptr, hB);
+        LAYER(F_A3, NBW, KH, 0, hB, nullptr, hA);
+        raw = HEADL(F_AC, KH, hA);
+        float adj[3 * C_MAX];
+#pragma unroll
+        for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
+#undef LAYER
+#undef HEADL
+#undef OWNB
+        RAYFRAME_PASS_END(rf, A, FA, fin, tile, pass, passes, 2, pair, wave, 4, par == 0, lane, col_r, col_g, col_b, rho_raw, sv_raw, adj, vote_lds);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_frame_walk_ks(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st) {
+    if (W != 512 || a.n_times < 1 || a.n_times > kMaxFrameTimes || a.m.n_classes > kMaxClasses) return hipErrorInvalidValue;
+    const int lds_bytes = ks_lds_bytes(a.m.bias_floats) + kFrameLdsFloats * 4;
+    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    return launch_fused(frame_walk_ks_kernel<512>, field_tiles(a.m.n, 3, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
+}
+
 }  // namespace snerf

@@ -443,6 +443,136 @@ __device__ __forceinline__ void rayshadow_end(const RayShadow& q, const MlpArgs&
         }                                                                                                                       \
     }
 
+// Film frame (frame_walk_kernel, frame_walk_ks_kernel): the ray surface's walk through the whole layer list of VARIANT 0 - trunk, head, fc_solar_1..4,
+// the colour-adjust branch - with the shading and compositing of the reference's film frames in the pass end (T_NeRF_Eval_Utils/mg_movie_maker.py:108-187):
+//   Out_Img = sum_s PS_s (vis_s + (1 - vis_s) sky) col_s,    HM = sum_s PS_s linspace(0, 2, S)[s]
+// with the learned visibility applied per sample and one colour per season shown in the frame: only the class vector depends on the time, so up to
+// kMaxFrameTimes seasons come from one field pass.  The sun direction, the sky colour, the class vectors and delta are the same for every ray of a launch;
+// they wait in LDS (`fin`, staged by the kernel before its first barrier: sun 3 | sky 3 | pad 2 | class vectors kMaxFrameTimes x kMaxClasses, zero filled),
+// since a plain load inside the chain drains the LDS-DMA pipeline (field_tile_inputs).  Sixteen floats per lane live across the MFMA chain.
+constexpr int kFrameLdsFloats = 8 + kMaxFrameTimes * kMaxClasses;
+struct RayFrame {
+    float carry;                    // optical depth of the samples of the passes walked so far (the same in lanes 0..31, 0 in the others): slot 14
+    float acc, mi, psv;             // this lane's partial sums of PS, PS s and PS vis
+    float rgb[3 * kMaxFrameTimes];  // ... of PS shade_c col_k[c] at [3 k + c]
+};
+// the launch's inputs into LDS, by all 256 threads before the kernel's first barrier
+__device__ __forceinline__ void frame_stage_inputs(const FrameWalkArgs& FA, __attribute__((address_space(3))) float* fin) {
+    const int i = threadIdx.x, C = FA.m.n_classes;
+    if (i < kFrameLdsFloats) {
+        float v = 0.f;
+        if (i < 3) v = FA.sun[i];
+        else if (i < 6) v = FA.sky[i - 3];
+        else if (i >= 8) {
+            const int k = (i - 8) / kMaxClasses, c = (i - 8) % kMaxClasses;
+            if (k < FA.n_times && c < C) v = FA.class_vecs[k * C + c];
+        }
+        fin[i] = v;
+    }
+}
+// sample position of this lane in pass p: raysum_point's; the first pass of a ray clears its sums
+__device__ __forceinline__ void rayframe_point(RayFrame& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
+    RaySum unused;
+    raysum_point(unused, A, group, waves, wave, p, lane, x0, x1, x2);
+    if (p == 0) {
+        q.carry = 0.f; q.acc = 0.f; q.mi = 0.f; q.psv = 0.f;
+#pragma unroll
+        for (int i = 0; i < 3 * kMaxFrameTimes; ++i) q.rgb[i] = 0.f;
+    }
+}
+// The pass's 32 samples into the sums.  The scan, PV, PE and PS are raysurf_add's, operation for operation, on y = softplus(rho) delta with the frame's one
+// delta (the spacing of end-point-inclusive samples; the ray's own length is not used); the colour mixing is store_field_outputs'.  A basic block of its
+// own and the end points and t re-read behind the chain, for the reasons given in raysum_add.  Padding samples (s >= S) count nowhere.
+__device__ __forceinline__ void rayframe_add(RayFrame& q, const MlpArgs& A, float frame_delta, __attribute__((address_space(3))) const float* fin,
+                                             int64_t group, int waves, int wave, int p, int lane, float col_r, float col_g, float col_b, float rho_raw,
+                                             float sv_raw, const float* adj) {
+    if (lane >= 32) return;
+    const int64_t ray = group * waves + wave;
+    const int64_t r = ray < A.n ? ray : A.n - 1;
+    const float tx = A.top[r * 3], ty = A.top[r * 3 + 1], tz = A.top[r * 3 + 2];
+    const float bx = A.bot[r * 3], by = A.bot[r * 3 + 1], bz = A.bot[r * 3 + 2];
+    float delta = frame_delta;
+    const int s = raysum_block(A, p) * 32 + lane;
+    const bool in = s < A.n_samples;
+    const float t = A.tvals[in ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
+    const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
+    const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
+    const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
+    if ((A.ray_flags & 2) && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+    const float y = in ? softplus_f(rho_raw) * delta : 0.f;
+    float incl = y;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+        const float u = __shfl_up(incl, o, 32);
+        if (lane >= o) incl += u;
+    }
+    const float below = __shfl_up(incl, 1, 32);
+    const float excl = q.carry + (lane == 0 ? 0.f : below);
+    q.carry += __shfl(incl, 31, 32);
+    const float pv = expf(-excl);
+    const float pe = 1.f - expf(-y);
+    const float ps = in ? pv * pe : 0.f;
+    const float vis = sigmoid_f(sv_raw);
+    const float sh0 = ps * (vis + (1.f - vis) * fin[3]), sh1 = ps * (vis + (1.f - vis) * fin[4]), sh2 = ps * (vis + (1.f - vis) * fin[5]);
+    q.acc += ps;
+    q.mi += ps * (float)s;
+    q.psv += ps * vis;
+#pragma unroll
+    for (int k = 0; k < kMaxFrameTimes; ++k) {      // seasons past n_times mix a zero class vector; their slots are cleared at the ray's end
+        float ac0 = 0.f, ac1 = 0.f, ac2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < kMaxClasses; ++c) {
+            if (c < A.n_classes) {
+                const float pc = fin[8 + k * kMaxClasses + c];
+                ac0 = __fadd_rn(ac0, __fmul_rn(adj[3 * c], pc));
+                ac1 = __fadd_rn(ac1, __fmul_rn(adj[3 * c + 1], pc));
+                ac2 = __fadd_rn(ac2, __fmul_rn(adj[3 * c + 2], pc));
+            }
+        }
+        q.rgb[3 * k] += sh0 * sigmoid_f(col_r + ac0);
+        q.rgb[3 * k + 1] += sh1 * sigmoid_f(col_g + ac1);
+        q.rgb[3 * k + 2] += sh2 * sigmoid_f(col_b + ac2);
+    }
+}
+// the ray's sixteen numbers {rgb of season 0, 1, 2, 3 (0 past n_times), sum PS, sum PS s, optical depth walked, sum PS vis}: one 64-byte row, four
+// 16-byte stores by lane 0
+__device__ __forceinline__ void rayframe_end(const RayFrame& q, const MlpArgs& A, int n_times, float* out, int64_t ray, int lane) {
+    float acc = q.acc, mi = q.mi, psv = q.psv, rgb[3 * kMaxFrameTimes];
+#pragma unroll
+    for (int i = 0; i < 3 * kMaxFrameTimes; ++i) rgb[i] = q.rgb[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_xor(acc, o, 64);
+        mi += __shfl_xor(mi, o, 64);
+        psv += __shfl_xor(psv, o, 64);
+#pragma unroll
+        for (int i = 0; i < 3 * kMaxFrameTimes; ++i) rgb[i] += __shfl_xor(rgb[i], o, 64);
+    }
+#pragma unroll
+    for (int i = 0; i < 3 * kMaxFrameTimes; ++i) if (i >= 3 * n_times) rgb[i] = 0.f;
+    if (lane == 0 && ray < A.n) {
+        static_assert(kMaxFrameTimes == 4, "the row has twelve colour slots");
+        float* row = out + ray * 16;
+        *reinterpret_cast<f32x4*>(row) = f32x4{rgb[0], rgb[1], rgb[2], rgb[3]};
+        *reinterpret_cast<f32x4*>(row + 4) = f32x4{rgb[4], rgb[5], rgb[6], rgb[7]};
+        *reinterpret_cast<f32x4*>(row + 8) = f32x4{rgb[8], rgb[9], rgb[10], rgb[11]};
+        *reinterpret_cast<f32x4*>(row + 12) = f32x4{acc, mi, q.carry, psv};
+    }
+}
+// The end of a pass, as RAYSURF_PASS_END: the same vote on the optical depth walked so far.  Behind depth 18 every further PS is below exp(-18) = 1.5e-8,
+// and shade and colour lie in [0, 1].
+#define RAYFRAME_PASS_END(q, A, FA, fin, tile, pass, passes, rays, ray_wave, slot, n_slots, writer, lane, col_r, col_g, col_b, rho_raw, sv_raw, adj, vote) \
+    {                                                                                                                           \
+        rayframe_add(q, A, (FA).delta, fin, tile, rays, ray_wave, pass, lane, col_r, col_g, col_b, rho_raw, sv_raw, adj);       \
+        RaySum depth;                                                                                                           \
+        depth.sum = lane == 0 ? q.carry : 0.f;                                                                                  \
+        if (++pass == (passes) || raysum_saturated(depth, A, tile * (rays) + (ray_wave), slot, n_slots, lane, vote)) {          \
+            if (writer) rayframe_end(q, A, (FA).n_times, (FA).out, tile * (rays) + (ray_wave), lane);                           \
+            pass = 0;                                                                                                           \
+            tile += gridDim.x;                                                                                                  \
+        }                                                                                                                       \
+    }
+
 // output non-linearities of the field program (T_NeRF_net_v2.py:91-98) for one point; called by the lanes that hold the head rows
 template <int VARIANT>
 __device__ __forceinline__ void store_field_outputs(const snerf_field_out_dev& O, int64_t n, int C, float x0, float x1, float x2,

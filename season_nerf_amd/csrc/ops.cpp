@@ -22,6 +22,7 @@
 //        -> [shaded[M,T,R,3], season[T,R,3], base[R,3], raw_shadow[M,R], shadow_adjust[M,R,3]]           the M x T grid of a view
 //   season_nerf::ray_surface(model, top[R,3], bot[R,3], tvals[S], flags) -> [R,4] {sum PS, sum PS t, sum PS s, optical depth}      height maps from a density-only ray pass
 //   season_nerf::shadow_walk(model, top[R,3], bot[R,3], sun[R,3], tvals[S], flags) -> [R,8]           the shadow test's per-ray sums (mg_Shadow_Eval.py:72-104,134-163)
+//   season_nerf::frame_walk(model, top[R,3], bot[R,3], tvals[S], delta, sun[3], sky[3], class_vecs[T,C], flags) -> [R,16]   a film frame's per-ray sums, T <= 4 seasons (mg_movie_maker.py:108-187)
 //   season_nerf::fused_adam_(param!, grad, m!, v!, lr, b1, b2, eps, step) -> ()                         mg_run_NeRF.py:312-320
 // Training engine (csrc/train.cpp; `trainer` = the snerf_trainer handle a season_nerf_amd.training.TrainEngine owns and has bound to its
 // parameter / gradient / workspace tensors).  The forward ops are functional in their tensor arguments (torch.library.register_autograd
@@ -314,6 +315,32 @@ Tensor shadow_walk(int64_t model, const Tensor& top, const Tensor& bot, const Te
     if (R == 0) return out;
     ck(snerf_field_shadow_walk((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(sun), fptr(tvals), (int)flags, mptr(out),
                                cur_stream(top)), "shadow_walk");
+    return out;
+}
+
+// Frame walk (include/season_nerf_hip.h snerf_field_frame_walk): sixteen sums per ray of a film frame, up to four seasons from one field pass.  The model
+// travels as an integer, as in ray_surface.
+Tensor frame_walk(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, double delta, const Tensor& sun, const Tensor& sky,
+                  const Tensor& class_vecs, int64_t flags) {
+    TORCH_CHECK(model != 0, "season_nerf::frame_walk: NULL model handle");
+    check_shape(top, "top", -1, 3);
+    const int64_t R = top.size(0);
+    check_shape(bot, "bot", R, 3);
+    check_dev_f32(tvals, "tvals");
+    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 2, "tvals must be [S] with S >= 2");
+    check_dev_f32(sun, "sun");
+    check_dev_f32(sky, "sky");
+    TORCH_CHECK(sun.dim() == 1 && sun.numel() == 3 && sky.dim() == 1 && sky.numel() == 3, "sun and sky must be [3]");
+    check_shape(class_vecs, "class_vecs", -1, snerf_model_classes((const snerf_model*)model));
+    TORCH_CHECK(class_vecs.size(0) >= 1 && class_vecs.size(0) <= SNERF_MAX_FRAME_TIMES, "class_vecs must be [T,C] with 1 <= T <= ", SNERF_MAX_FRAME_TIMES,
+                ", got T = ", class_vecs.size(0));
+    TORCH_CHECK(std::isfinite(delta) && delta > 0, "delta must be finite and positive, got ", delta);
+    TORCH_CHECK((flags & ~(int64_t)6) == 0, "flags must be a combination of 2 (zero delta outside the cube) and 4 (no early-out), got ", flags);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
+    Tensor out = at::empty({R, 16}, top.options());
+    if (R == 0) return out;
+    ck(snerf_field_frame_walk((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(tvals), (float)delta, fptr(sun), fptr(sky),
+                              (int)class_vecs.size(0), fptr(class_vecs), (int)flags, mptr(out), cur_stream(top)), "frame_walk");
     return out;
 }
 
@@ -625,6 +652,7 @@ TORCH_LIBRARY(season_nerf, m) {
     m.def("sun_walk_fwd(int model, Tensor top, Tensor bot, Tensor tvals, Tensor suns, Tensor? classes) -> Tensor[]");
     m.def("ray_surface(int model, Tensor top, Tensor bot, Tensor tvals, int flags) -> Tensor");
     m.def("shadow_walk(int model, Tensor top, Tensor bot, Tensor sun, Tensor tvals, int flags) -> Tensor");
+    m.def("frame_walk(int model, Tensor top, Tensor bot, Tensor tvals, float delta, Tensor sun, Tensor sky, Tensor class_vecs, int flags) -> Tensor");
     m.def("composite_sun_walk(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
           "int flags, Tensor? deltas=None) -> Tensor[]");
     m.def("fused_adam_(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, float lr, float beta1, float beta2, float eps, int step) -> ()");
@@ -659,6 +687,7 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("composite_sun_walk", composite_sun_walk);
     m.impl("ray_surface", ray_surface);
     m.impl("shadow_walk", shadow_walk);
+    m.impl("frame_walk", frame_walk);
     m.impl("trainer_adam_step_", trainer_adam_step_);
     m.impl("trainer_adam_step_dev_", trainer_adam_step_dev_);
     m.impl("trainer_zero_grad_", trainer_zero_grad_);

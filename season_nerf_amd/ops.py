@@ -62,6 +62,10 @@ def _register_fakes():
     def _(model, top, bot, sun, tvals, flags):
         return top.new_empty(top.shape[0], 8)
 
+    @reg("season_nerf::frame_walk")
+    def _(model, top, bot, tvals, delta, sun, sky, class_vecs, flags):
+        return top.new_empty(top.shape[0], 16)
+
     @reg("season_nerf::fused_adam_")
     def _(param, grad, m, v, lr, beta1, beta2, eps, step):
         return None
