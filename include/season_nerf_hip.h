@@ -95,7 +95,8 @@ int snerf_model_resolve_precision(snerf_model* m);
  * program 0 = per-point field network, 1 = per-group (time/sun) network (bf16 hi/lo fragment pairs + bias table);
  * program 2 = the field network in the int8-digit format (T/L digit fragment pairs + per-row [scale | bias] tables),
  * only under SNERF_PREC_I8X3; program 3 = the field network's bf16 pairs in the K-split order of the width-512 kernel
- * (csrc/program.h ks_*: a permutation of program 0's pairs, same bias table), program 4 = program 1's pairs in that order; 3 and 4: width 512 only.
+ * (csrc/program.h ks_*: a permutation of program 0's pairs, same bias table), program 4 = program 1's pairs in that order; 3 and 4: width 512 only;
+ * program 5 = program 2's digits in the layout of the 16x16x64 int8 matrix instruction (csrc/program.h k64_*), only under SNERF_PREC_I8X3 at width 256.
  * Buffers may be NULL to query sizes. */
 int snerf_model_pack_host(snerf_model* m, int program, uint8_t* stream_out, size_t* stream_bytes,
                           float* bias_out, size_t* bias_floats);

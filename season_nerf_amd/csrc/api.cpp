@@ -41,6 +41,7 @@ struct snerf_model {
     bool finalized = false;
     Packed host[2];
     Packed host_i8;                  // field program in the int8-digit format (precision SNERF_PREC_I8X3 only)
+    Packed host_k64;                 // ... its digits in the layout of v_mfma_i32_16x16x64_i8 (program.h "k64": what kernels_i8x2.hip runs at W = 256)
     Packed host_ks;                  // field program in the K-split order of kernels_ks.hip (W = 512 under SNERF_PREC_BF16X3)
     Packed host_ksg;                 // per-ray (group) program in the same order: W = 512 under every precision (round 6; exact fp32 layer by layer before)
     // Widths without a bf16 group kernel (512): the per-ray networks (time -> class softmax, sun -> sky colour: one row per ray,
@@ -52,6 +53,8 @@ struct snerf_model {
     float* d_bias[2] = {nullptr, nullptr};
     uint8_t* d_stream_i8 = nullptr;
     float* d_table_i8 = nullptr;
+    uint8_t* d_stream_k64 = nullptr;
+    float* d_table_k64 = nullptr;
     uint8_t* d_stream_ks = nullptr;
     float* d_bias_ks = nullptr;
     uint8_t* d_stream_ksg = nullptr;
@@ -190,6 +193,14 @@ static int pack_both(snerf_model* m, bool want_bf16_field = false) {
             return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
         m->host_i8 = std::move(tmp);
     }
+    // the two-wave kernel's instances on the 16x16x64 shape read their own stream; every other int8 kernel keeps the one above
+    if (m->precision == SNERF_PREC_I8X3 && i8x2_k64_built(m->W, 0) && m->host_k64.stream.empty()) {
+        std::string err;
+        Packed tmp;
+        if (!pack_program_k64(m->w, m->W, m->C, /*fold_bn=*/true, &tmp, &err))
+            return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
+        m->host_k64 = std::move(tmp);
+    }
     return SNERF_OK;
 }
 
@@ -201,14 +212,16 @@ int snerf_model_resolve_precision(snerf_model* m) {
 
 int snerf_model_pack_host(snerf_model* m, int program, uint8_t* stream_out, size_t* stream_bytes, float* bias_out,
                           size_t* bias_floats) {
-    if (!m || program < 0 || program > 4) return fail(SNERF_E_INVALID, "snerf_model_pack_host: bad argument");
+    if (!m || program < 0 || program > 5) return fail(SNERF_E_INVALID, "snerf_model_pack_host: bad argument");
+    if (program == 5 && (m->precision != SNERF_PREC_I8X3 || !i8x2_k64_built(m->W, 0)))
+        return fail(SNERF_E_STATE, "program 5 (int8 digits for the 16x16x64 matrix instruction) exists only under SNERF_PREC_I8X3 at width 256");
     if (program == 2 && m->precision != SNERF_PREC_I8X3)
         return fail(SNERF_E_STATE, "program 2 (int8-digit field network) exists only under SNERF_PREC_I8X3");
     if (program == 3 && !ks_width(m->W)) return fail(SNERF_E_STATE, "program 3 (K-split bf16 field network) exists only at width 512");
     if (program == 4 && !ks_width(m->W)) return fail(SNERF_E_STATE, "program 4 (K-split per-ray networks) exists only at width 512");
     int rc = pack_both(m, program == PROG_FIELD || program == 3);
     if (rc) return rc;
-    const Packed& P = program == 4 ? m->host_ksg : program == 3 ? m->host_ks : program == 2 ? m->host_i8 : m->host[program];
+    const Packed& P = program == 5 ? m->host_k64 : program == 4 ? m->host_ksg : program == 3 ? m->host_ks : program == 2 ? m->host_i8 : m->host[program];
     if (stream_bytes) *stream_bytes = P.stream.size();
     if (bias_floats) *bias_floats = P.bias.size();
     if (stream_out) std::memcpy(stream_out, P.stream.data(), P.stream.size());
@@ -263,6 +276,13 @@ int snerf_model_finalize(snerf_model* m) {
         if ((e = hipMemcpy(m->d_table_i8, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
             return fail_hip(e, "hipMemcpy");
     }
+    if (m->precision == SNERF_PREC_I8X3 && !m->host_k64.stream.empty()) {
+        const Packed& P = m->host_k64;
+        if ((e = hipMalloc((void**)&m->d_stream_k64, P.stream.size())) != hipSuccess) return fail_hip(e, "hipMalloc");
+        if ((e = hipMalloc((void**)&m->d_table_k64, P.bias.size() * 4)) != hipSuccess) return fail_hip(e, "hipMalloc");
+        if ((e = hipMemcpy(m->d_stream_k64, P.stream.data(), P.stream.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+        if ((e = hipMemcpy(m->d_table_k64, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+    }
     if (!bf16_width(m->W)) {      // fp32 weights of the per-ray networks
         static const char* keys[5] = {"time_layer_1.linear", "time_layer_2.linear", "get_class_layer", "G_NeRF_net.fc_sky_color_1.linear",
                                       "G_NeRF_net.fc_sky_color_2"};
@@ -297,6 +317,8 @@ void snerf_model_destroy(snerf_model* m) {
     }
     if (m->d_stream_i8) (void)hipFree(m->d_stream_i8);
     if (m->d_table_i8) (void)hipFree(m->d_table_i8);
+    if (m->d_stream_k64) (void)hipFree(m->d_stream_k64);
+    if (m->d_table_k64) (void)hipFree(m->d_table_k64);
     if (m->d_stream_ks) (void)hipFree(m->d_stream_ks);
     if (m->d_bias_ks) (void)hipFree(m->d_bias_ks);
     if (m->d_stream_ksg) (void)hipFree(m->d_stream_ksg);
@@ -425,8 +447,18 @@ static int field_launch(const snerf_model* m, int variant, MlpArgs& a, const sne
         a.bias_floats = (int)m->host_i8.bias.size();
         // two waves per SIMD wherever the activations leave room for it (kernels_i8x2.hip); SNERF_I8_ONE_WAVE=1: A/B switch
         static const bool one_wave = getenv("SNERF_I8_ONE_WAVE") != nullptr;
-        if (m->W <= 256 && !one_wave) e = launch_mlp_i8x2(m->W, variant, a, m->n_cu, (hipStream_t)stream);
-        else e = launch_mlp_i8(m->W, variant, a, m->n_cu, (hipStream_t)stream);
+        // the two-wave kernel's instances built on v_mfma_i32_16x16x64_i8 (W = 256) read the k64 stream; SNERF_I8X2_MFMA32=1: their 32x32x32 code (A/B)
+        static const bool mfma32 = getenv("SNERF_I8X2_MFMA32") != nullptr;
+        if (m->W <= 256 && !one_wave) {
+            if (!mfma32 && m->d_stream_k64 && i8x2_k64_built(m->W, variant)) {
+                a.stream = m->d_stream_k64;
+                a.stream_bytes = (uint32_t)k64_chunk_start(m->W, m->C, field_variant_layers(variant)) * kChunkBytes;
+                a.bias = m->d_table_k64;
+                a.bias_floats = (int)m->host_k64.bias.size();
+                a.k64 = 1;
+            }
+            e = launch_mlp_i8x2(m->W, variant, a, m->n_cu, (hipStream_t)stream);
+        } else e = launch_mlp_i8(m->W, variant, a, m->n_cu, (hipStream_t)stream);
     } else if (ks_width(m->W)) {
         a.stream = m->d_stream_ks;
         a.stream_bytes = (uint32_t)field_variant_chunks_ks(m->W, m->C, variant) * kChunkBytes;
@@ -863,7 +895,9 @@ int snerf_field_kernel_info(const snerf_model* m, int64_t n_points, int* grid, i
     if (grid) *grid = (int)(tiles < ncu ? tiles : ncu);
     if (block) *block = two_waves ? 512 : 256;
     if (lds_bytes) {
-        if (i8) *lds_bytes = (m->W > 256 ? 5 : 7) * kChunkBytes + (int)m->host_i8.bias.size() * 4 + kVoteBytes;
+        static const bool mfma32 = getenv("SNERF_I8X2_MFMA32") != nullptr;      // as field_launch: the tables of the stream the launch gets
+        const bool k64 = two_waves && !mfma32 && !m->host_k64.stream.empty();
+        if (i8) *lds_bytes = (m->W > 256 ? 5 : 7) * kChunkBytes + (int)(k64 ? m->host_k64 : m->host_i8).bias.size() * 4 + kVoteBytes;
         else if (ks) *lds_bytes = mlp_ks_lds_bytes((int)m->host_ks.bias.size());
         else *lds_bytes = mlp_lds_bytes((int)m->host[PROG_FIELD].bias.size());
     }

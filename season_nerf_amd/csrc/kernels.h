@@ -43,6 +43,7 @@ struct MlpArgs {
     uint32_t debug;            // only read by -DSNERF_ABLATE builds
     // VARIANT 3 (ray visibility: the density-only program with the sum over a ray's samples kept in registers): n = rays, every wave
     // owns one ray of a group of `waves per workgroup` rays and walks its samples 32 at a time
+    int k64;                   // mlp_i8x2_kernel: stream and tables are in the 16x16x64 layout (program.h "k64"); 0 everywhere else
     int ray_flags;             // bit 1: a sample outside [-1,1]^3 contributes nothing (mg_Img_Eval.py:42,65-66); bit 2: no early-out (A/B); bit 3: passes from the sun side inwards (the order before round 6's reversal, A/B)
 };
 
@@ -180,6 +181,7 @@ hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t
 hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)
 int field_variant_chunks_i8(int W, int C, int variant);
 hipError_t launch_mlp_i8x2(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8x2.hip (W <= 256)
+bool i8x2_k64_built(int W, int variant);                                                                   // ... is this instance built on v_mfma_i32_16x16x64_i8 (and reads the k64 stream)?
 hipError_t launch_mlp_ks(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_ks.hip (W = 512, bf16x3, K split over wave pairs)
 hipError_t launch_mlp_ks_group(int W, const MlpArgs& a, int n_cu, hipStream_t st);                         // ... its per-ray (time / sun) networks
 hipError_t launch_mlp_group_split(int W, const MlpArgs& a, int n_cu, hipStream_t st);                   // kernels_group.hip (W <= 256: the per-ray networks, output blocks split over the waves)

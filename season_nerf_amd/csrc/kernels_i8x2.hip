@@ -18,6 +18,9 @@
 //  SNERF_X2_GROUPS switch below), waves 4-7 running their epilogue slices in the odd k-steps and waves 0-3 in the even ones.
 //  So the two waves running in step is not what leaves the matrix pipe 40 % idle; the chip holds 1.8 GHz in this kernel.
 //  Weight stream, tables, digit formats, accuracy: exactly those of kernels_i8.hip (same packed model, bit-identical results).
+//  At W = 256 the kernel runs the same digits on v_mfma_i32_16x16x64_i8 from a stream of its own (run_layer16, field_tiles16 below; program.h "k64"):
+//  9 % more cycles at a 15 % higher clock, 0.773 -> 0.716 ms per step (profiles/r13), bit-identical results.  The 32x32x32 code stays for W = 64 and
+//  behind SNERF_I8X2_MFMA32=1 (api.cpp field_launch: which stream a launch gets decides the code it runs).
 #include <type_traits>
 
 #include "mlp_i8_device.h"
@@ -457,9 +460,217 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
 #undef REQUEST_NEXT
 }
 
+// ---- the same layer on v_mfma_i32_16x16x64_i8 (program.h "k64", mlp_i8_device.h FragK): where the chip holds its clock down, the clock depends on the
+// MFMA shape.  Same output tile per wave - 32 points, as two 16-point column groups - and the same ring, chunks and pair size: a weight
+// pair read from LDS feeds 3 products x 2 column groups = 6 MFMAs, so the LDS weight bytes per MAC are those of run_layer8x2.
+//   * a block is 16 rows x 32 points: accumulators M, X of 2 x 4 registers each, merged into m[8] (m[4 cg + i] = row 4 g + i of point 16 cg + c);
+//   * its epilogue is two quads - one per column group, same rows, so ONE table entry (and one set of raw-coordinate weights) per block, requested with
+//     the merge - and rides in the next block's k-steps 0 and KS / 2; four blocks fill one k-step of the next layer (out[b / 4], dword b % 4);
+//   * PEND / HANDOFF / PRE_IN / PRE_OUT, the s_setprio alternation per k-step and the compiler constraints are those of run_layer8x2.  A carried block that
+//     is an operand (Carry::DEP) is dword 3 of the receiver's k-step (NBP - 1) / 4: both quads run before it.
+// Per element the arithmetic is epi_quad's, on the same integers: results are bit-identical to run_layer8x2's.
+struct BoundaryK {
+    int m[8];
+    i32x4 fT[PFX], fL[PFX];
+};
+struct CarryDstK {
+    FragK* out;
+    float* raw;            // [8]
+    const float (*rawx)[3];   // [column group][dim]
+};
+__host__ __device__ constexpr bool carry_fits_k64(int nb, bool dep) { return !dep || nb >= 5; }
+__host__ __device__ constexpr bool field_carries_k64(int W, int variant, int C, int l) {
+#ifdef SNERF_X2_NO_CARRY
+    return false;
+#endif
+    return l != field_last(variant) && carry_fits_k64(k64_blocks(k64_layer(W, C, l)), field_feeds_next(l));
+}
+// quad cg of a block from its merged sums: epi_quad on m[4 cg ..], the digits into dword `dw` of the k-step fragment `ob`
+template <bool SIN, bool RAWL>
+__device__ __forceinline__ void epi_quad_k64(const int* m, int cg, const TabQ& t, const f32x4* rq, const float (*rawx)[3], FragK* ob, int dw, float* raw) {
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf((float)m[4 * cg + j], t.sc[j], t.bi[j]);
+    if constexpr (RAWL) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            v[j] = __builtin_fmaf(rq[0][j], rawx[cg][0], __builtin_fmaf(rq[1][j], rawx[cg][1], __builtin_fmaf(rq[2][j], rawx[cg][2], v[j])));
+    }
+    if constexpr (SIN) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = sin2pi(v[j]);
+        int hi, lo;
+        digits4(v[0], v[1], v[2], v[3], hi, lo);
+        asm volatile("" : "+v"(hi), "+v"(lo));       // the digits exist HERE
+        ob->hi[cg][dw] = hi;
+        ob->lo[cg][dw] = lo;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) raw[4 * cg + j] = v[j];
+    }
+}
+
+template <int NB, int KS0, int KS1, bool SIN, bool RAWL = false, int PHASE = 0, class PEND = NoCarry, bool HANDOFF = false, bool PRE_IN = false,
+          bool PRE_OUT = false>
+__device__ __forceinline__ void run_layer16(Ring2& rg, const uint8_t* stream, uint32_t stream_bytes, lds_char* lds, lds_cfloat* tab0, lds_cfloat* tab_l,
+                                            const FragK* in0, const FragK* in1, FragK* out, float* raw, BoundaryK& bd, const CarryDstK& pd,
+                                            int wave, int lane, const float (*rawx)[3] = nullptr) {
+    constexpr int KS = KS0 + KS1, NP = NB * KS;
+    constexpr int NBP = PEND::NB;
+    static_assert(!PRE_OUT || (NP >= PFX && NP % PFX == 0), "the successor expects its pair j in fragment slot j");
+    static_assert(!PRE_IN || NP >= PFX, "the predecessor requested PFX pairs of this layer");
+    static_assert(!PEND::on || carry_fits_k64(NBP, PEND::DEP), "a carried block that is an operand of k-step 0 has no k-step to run in");
+    static_assert(!(PEND::on && PEND::DEP) || NBP == 4 * KS0, "Carry::DEP: the producer's output is in0");
+    int (&m)[8] = bd.m;
+    i32x4 (&fT)[PFX] = bd.fT;
+    i32x4 (&fL)[PFX] = bd.fL;
+    typedef volatile const __attribute__((address_space(3))) f32x4 lds_vf32x4;      // volatile: see load_tab_quad_h
+    // table addresses: one per-lane base per layer (this lane group's rows of block 0 of the lower of the two tables read here), every block an immediate
+    // offset from it.  The lane group is made opaque per layer: every layer's base is a loop invariant of the persistent tile loop, and left visible hipcc
+    // computes all of them in front of the loop and keeps them alive across the whole chain (35 registers measured, the allocation spilled).
+    int g = lane >> 4;
+    asm volatile("" : "+v"(g));
+    lds_cfloat* ptab_l = tab0 + PEND::TAB;
+    lds_cfloat* lo_l = PEND::on ? ptab_l : tab_l;
+    lds_cfloat* base_g = lo_l + 8 * g;
+    lds_cfloat* rbase_g = lo_l + 12 * g;
+    const int d_own = (int)(tab_l - lo_l);
+    auto tabq = [&](int b_) {
+        lds_vf32x4* tp = (lds_vf32x4*)(base_g + d_own + b_ * 32);
+        TabQ t;
+        t.sc = tp[0];
+        t.bi = tp[1];
+        return t;
+    };
+    auto ptabq = [&]() {
+        lds_vf32x4* tp = (lds_vf32x4*)(base_g + (NBP - 1) * 32);
+        TabQ t;
+        t.sc = tp[0];
+        t.bi = tp[1];
+        return t;
+    };
+    f32x4 rq[3];           // raw-coordinate weights of the previous block's rows (RAWL), requested with its table entry
+    auto load_rq = [&](int b_of) {
+        if constexpr (RAWL) {
+            lds_vf32x4* tp = (lds_vf32x4*)(rbase_g + d_own + 2 * 16 * NB + b_of * 48);
+            rq[0] = tp[0]; rq[1] = tp[1]; rq[2] = tp[2];
+        }
+    };
+    auto load_prq = [&]() {
+        if constexpr (PEND::RAWL) {
+            lds_vf32x4* tp = (lds_vf32x4*)(rbase_g + 2 * 16 * NBP + (NBP - 1) * 48);
+            rq[0] = tp[0]; rq[1] = tp[1]; rq[2] = tp[2];
+        }
+    };
+#define REQUEST(QN, SLOT)                                                                              \
+    do {                                                                                               \
+        if ((QN) % kChunkPairs == 0) {                                                                 \
+            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                              \
+            if ((QN) > 0) rg.cur = ring2_next(rg.cur);                                                 \
+        }                                                                                              \
+        lds_char* ap_ = lds + rg.cur + ((QN) % kChunkPairs) * kPairBytes + lane * 16;                  \
+        fT[SLOT] = *(lds_ci32x4*)ap_;                                                                  \
+        fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                                   \
+    } while (0)
+#define REQUEST_NEXT(J, SLOT)                                                                          \
+    do {                                                                                               \
+        if ((J) == 0) {                                                                                \
+            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                              \
+            rg.cur = ring2_next(rg.cur);                                                               \
+        }                                                                                              \
+        lds_char* ap_ = lds + rg.cur + (J) * kPairBytes + lane * 16;                                   \
+        fT[SLOT] = *(lds_ci32x4*)ap_;                                                                  \
+        fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                                   \
+    } while (0)
+    if constexpr (!PRE_IN) {
+#pragma unroll
+        for (int q = 0; q < PFX; ++q) {
+            if (q < NP) REQUEST(q, q);
+        }
+    }
+    AccK acc;
+    TabQ tq;               // table entry of the previous block (both quads: a block's two column groups are the same rows)
+    auto quad = [&](int cg, int b_of) { epi_quad_k64<SIN, RAWL>(m, cg, tq, rq, rawx, out + b_of / 4, b_of % 4, raw); };
+    auto pquad = [&](int cg) { epi_quad_k64<PEND::SIN, PEND::RAWL>(m, cg, tq, rq, pd.rawx, pd.out + (NBP - 1) / 4, (NBP - 1) % 4, pd.raw); };
+    // k-step of a block in which quad cg of the block before runs; the carried block where it is an operand: before k-step (NBP - 1) / 4
+    auto slot = [](int cg, bool carried) constexpr { return carried && PEND::DEP ? (cg * ((NBP - 1) / 4) * 2) / 3 : (cg * KS) / 2; };
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const bool carried = b == 0;
+        if (b > 0 || PEND::on) {
+            if (b > 0) {
+                tq = tabq(b - 1);
+                load_rq(b - 1);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) m[i] = (int)(((uint32_t)acc.M[i >> 2][i & 3] << 8) + (uint32_t)acc.X[i >> 2][i & 3]);
+            } else {
+                tq = ptabq();
+                load_prq();
+            }
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int cg = 0; cg < 2; ++cg)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { acc.M[cg][i] = 0; acc.X[cg][i] = 0; }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int q = b * KS + s;
+            const i32x4 aT = fT[q % PFX], aL = fL[q % PFX];
+#ifndef SNERF_X2_NOPRIO
+            if (((s + PHASE) & 1) == 0) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3);
+#endif
+            if (q + PFX < NP) REQUEST(q + PFX, q % PFX);
+            else if constexpr (PRE_OUT) REQUEST_NEXT(q + PFX - NP, q % PFX);
+            mfma_k64x3(aT, aL, s < KS0 ? in0[s] : in1[s - KS0], acc);
+            if (b > 0 || PEND::on) {
+#pragma unroll
+                for (int cg = 0; cg < 2; ++cg)
+                    if (slot(cg, carried) == s) {
+                        if (b > 0) quad(cg, b - 1);
+                        else pquad(cg);
+                    }
+            }
+            asm volatile("" ::: "memory");          // table loads stay in their k-step
+            __builtin_amdgcn_sched_barrier(0);      // ... and so do requests, MFMAs and epilogue slices (register pressure)
+        }
+    }
+    // the last block of the layer: handed to the next layer, or finished here
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m[i] = (int)(((uint32_t)acc.M[i >> 2][i & 3] << 8) + (uint32_t)acc.X[i >> 2][i & 3]);
+    if constexpr (HANDOFF) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+        asm volatile("" ::: "memory");
+        tq = tabq(NB - 1);
+        load_rq(NB - 1);
+#pragma unroll
+        for (int cg = 0; cg < 2; ++cg) {
+            quad(cg, NB - 1);
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if constexpr (!PRE_OUT) rg.cur = ring2_next(rg.cur);          // the next layer starts on the next chunk
+#undef REQUEST
+#undef REQUEST_NEXT
+}
+
+// instances built on the 16x16x64 shape (the others, and every instance under SNERF_I8X2_MFMA32=1, run the 32x32x32 code above)
+#ifndef SNERF_K64_VARIANTS
+#define SNERF_K64_VARIANTS 0xf      // bit v = variant v
+#endif
+__host__ __device__ constexpr bool k64_built(int W, int variant) { return W == 256 && ((SNERF_K64_VARIANTS >> variant) & 1); }
+bool i8x2_k64_built(int W, int variant) { return variant >= 0 && variant <= 3 && k64_built(W, variant); }
+
 template <int W, int VARIANT, int PHASE>
 __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_char* lds, __attribute__((address_space(3))) float* tab_lds,
                                              int wave, int lane);
+template <int W, int VARIANT, int PHASE>
+__device__ __forceinline__ void field_tiles16(const MlpArgs& A, Ring2& rg, lds_char* lds, __attribute__((address_space(3))) float* tab_lds,
+                                              int wave, int lane);
 
 template <int W, int VARIANT>
 __global__ __launch_bounds__(64 * NW2, 1) void mlp_i8x2_kernel(const MlpArgs A) {
@@ -496,9 +707,133 @@ __global__ __launch_bounds__(64 * NW2, 1) void mlp_i8x2_kernel(const MlpArgs A) 
     }
     __syncthreads();   // table visible (drains the prologue DMAs once; harmless)
 
-    if (wave < 4) field_tiles2<W, VARIANT, 0>(A, rg, lds, tab_lds, wave, lane);
-    else field_tiles2<W, VARIANT, 1>(A, rg, lds, tab_lds, wave, lane);
+    // the MFMA shape: by width and variant at compile time (k64_built), and there by the stream the host handed over (A.k64: api.cpp field_launch)
+    bool k64 = false;
+    if constexpr (k64_built(W, VARIANT)) k64 = A.k64 != 0;
+    if (k64) {
+        if constexpr (k64_built(W, VARIANT)) {
+            if (wave < 4) field_tiles16<W, VARIANT, 0>(A, rg, lds, tab_lds, wave, lane);
+            else field_tiles16<W, VARIANT, 1>(A, rg, lds, tab_lds, wave, lane);
+        }
+    } else {
+        if (wave < 4) field_tiles2<W, VARIANT, 0>(A, rg, lds, tab_lds, wave, lane);
+        else field_tiles2<W, VARIANT, 1>(A, rg, lds, tab_lds, wave, lane);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+// the tile loop of field_tiles2 on the 16x16x64 shape.  Around the chain a lane keeps field_tiles2's form (lane l & 31 = point: inputs, outputs, the ray sum
+// of VARIANT 3 are its code); inside, lane 16 g + c works for points c and 16 + c (mlp_i8_device.h): the coordinates go in and the raw heads' rows come
+// out through a few cross-lane reads per tile.
+template <int W, int VARIANT, int PHASE>
+__device__ __forceinline__ void field_tiles16(const MlpArgs& A, Ring2& rg, lds_char* lds, __attribute__((address_space(3))) float* tab_lds,
+                                              int wave, int lane) {
+    constexpr int C_MAX = kMaxClasses;
+    constexpr int W2 = W / 2;
+    const int h = lane >> 5, gq = lane >> 4;
+    const int C = A.n_classes;
+    const int64_t n_tiles = field_tiles(A.n, VARIANT, TILE2, NW2);
+    const int passes = VARIANT == 3 ? (A.n_samples + 31) / 32 : 1;
+    int pass = 0;
+    RaySum rs;
+    for (int64_t tile = blockIdx.x; tile < n_tiles;) {
+        const int64_t n = tile * TILE2 + wave * 32 + (lane & 31);
+        const bool valid = n < A.n;
+        const int64_t nc = valid ? n : A.n - 1;
+        const int64_t g = VARIANT == 3 ? 0 : nc / A.group_size;
+
+        float x0, x1, x2;
+        if constexpr (VARIANT == 3) raysum_point(rs, A, tile, NW2, wave, pass, lane, x0, x1, x2);
+        else field_point(A, nc, x0, x1, x2);
+        float s0, s1, s2, pcls[C_MAX];
+        field_tile_inputs<VARIANT>(A, g, s0, s1, s2, pcls);
+        float rx_p[2][3], rx_s[2][3];      // raw coordinates of this lane's two points: fp32, no digit range
+        k64_two_points(x0, x1, x2, lane, rx_p);
+        FragK pe;
+        make_pe_pos_k64(rx_p, gq, pe);
+
+        constexpr int KW = W / 64, KW2 = W2 / 64;
+        FragK hA[KW], hB[KW];
+        float raw[8];
+        BoundaryK bd;
+#define TAB(L) k64_table_start(W, C_MAX, L)
+#define NBLK(L) k64_blocks(k64_layer(W, C_MAX, L))
+#define HAND(L) field_carries_k64(W, VARIANT, C_MAX, L)
+#define PRE_I(L) (L != F_FC1)
+#define PRE_O(L) (L != field_last(VARIANT))
+#define PEND_T(P, PSIN, PRAWL) std::conditional_t<HAND(P), Carry<TAB(P), NBLK(P), PSIN, PRAWL, field_feeds_next(P)>, NoCarry>
+#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW, PEND, PDST, HANDv)                                                     \
+    run_layer16<NBv, K0, K1, SINv, false, PHASE, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),  \
+                                                 IN0, IN1, OUT, RAW, bd, PDST, wave, lane, nullptr)
+#define LAYER_RAW(L, NBv, K0, K1, IN0, IN1, OUT, RX, PEND, PDST, HANDv)                                                        \
+    run_layer16<NBv, K0, K1, true, true, PHASE, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),   \
+                                                IN0, IN1, OUT, nullptr, bd, PDST, wave, lane, RX)
+        const CarryDstK none{nullptr, nullptr, nullptr};
+        static_assert(NBLK(F_FC1) == 4 * KW && NBLK(F_FC9) == 4 * KW2 && NBLK(F_HEAD) == 1 && NBLK(F_S4) == 1 && NBLK(F_A1) == 4 * KW, "block counts below");
+        // trunk
+        LAYER_RAW(F_FC1, W / 16, 1, 0, &pe, nullptr, hA, rx_p, NoCarry, none, HAND(F_FC1));
+        LAYER(F_FC2, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC1, true, true), (CarryDstK{hA, nullptr, rx_p}), HAND(F_FC2));
+        LAYER(F_FC3, W / 16, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC2, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC3));
+        LAYER(F_FC4, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC3, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_FC4));
+        LAYER_RAW(F_FC5, W / 16, KW, 1, hB, &pe, hA, rx_p, PEND_T(F_FC4, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC5));
+        LAYER(F_FC6, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC5, true, true), (CarryDstK{hA, nullptr, rx_p}), HAND(F_FC6));
+        // the lane's own point (l & 31) is one of its two: from here on its coordinates (for the stores) replace the pair's, whose last reader was fc6
+        if constexpr (VARIANT != 3) {
+            const bool up = (lane & 16) != 0;
+            x0 = up ? rx_p[1][0] : rx_p[0][0]; x1 = up ? rx_p[1][1] : rx_p[0][1]; x2 = up ? rx_p[1][2] : rx_p[0][2];
+        }
+        LAYER(F_FC7, W / 16, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC6, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC7));
+        LAYER(F_FC8, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC7, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_FC8));
+        FragK x1f[KW2];
+        LAYER(F_FC9, W2 / 16, KW, 0, true, hB, nullptr, x1f, nullptr, PEND_T(F_FC8, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC9));
+        // sigma / colour head: rows 0..2 colour, 3 density (lane group 0); with the solar branch behind it the block finishes inside fc_solar_1
+        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, raw, PEND_T(F_FC9, true, false), (CarryDstK{x1f, nullptr, nullptr}), HAND(F_HEAD));
+        float col_r, col_g, col_b, rho_raw;
+        float sv_raw = 0.f;
+        float adj[3 * C_MAX];
+#pragma unroll
+        for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = 0.f;
+#define HEAD_OUT() col_r = k64_head_row(raw, 0, lane), col_g = k64_head_row(raw, 1, lane), col_b = k64_head_row(raw, 2, lane), rho_raw = k64_head_row(raw, 3, lane)
+        if constexpr (VARIANT <= 1) {
+            k64_two_points(s0, s1, s2, lane, rx_s);
+            FragK ps;
+            make_pe_sun_k64(rx_s, gq, ps);
+            FragK sA[KW2], sB[KW2];
+            LAYER_RAW(F_S1, W2 / 16, KW2, 1, x1f, &ps, sA, rx_s, PEND_T(F_HEAD, false, false), (CarryDstK{nullptr, raw, nullptr}), HAND(F_S1));
+            HEAD_OUT();
+            LAYER(F_S2, W2 / 16, KW2, 0, true, sA, nullptr, sB, nullptr, PEND_T(F_S1, true, true), (CarryDstK{sA, nullptr, rx_s}), HAND(F_S2));
+            LAYER(F_S3, W2 / 16, KW2, 0, true, sB, nullptr, sA, nullptr, PEND_T(F_S2, true, false), (CarryDstK{sB, nullptr, nullptr}), HAND(F_S3));
+            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, raw, PEND_T(F_S3, true, false), (CarryDstK{sA, nullptr, nullptr}), HAND(F_S4));
+            if constexpr (VARIANT == 1) sv_raw = k64_head_row(raw, 0, lane);
+        } else {
+            HEAD_OUT();
+        }
+        if constexpr (VARIANT == 0) {
+            LAYER(F_A1, W / 16, KW2, 0, true, x1f, nullptr, hA, nullptr, PEND_T(F_S4, false, false), (CarryDstK{nullptr, raw, nullptr}), HAND(F_A1));
+            sv_raw = k64_head_row(raw, 0, lane);
+            LAYER(F_A2, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_A1, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_A2));
+            LAYER(F_A3, W / 16, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_A2, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_A3));
+            LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, raw, PEND_T(F_A3, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_AC));
+#pragma unroll
+            for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = k64_head_row(raw, i, lane);
+        }
+#undef HEAD_OUT
+#undef LAYER
+#undef LAYER_RAW
+#undef PEND_T
+#undef HAND
+#undef PRE_I
+#undef PRE_O
+#undef TAB
+#undef NBLK
+        if constexpr (VARIANT == 3) {
+            RAYSUM_PASS_END(rs, A, tile, pass, passes, NW2, wave, wave, NW2, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
+        } else {
+            if (h == 0 && valid) store_field_outputs<VARIANT>(A.out, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, sv_raw, adj, pcls);
+            tile += gridDim.x;
+        }
+    }
+    __builtin_amdgcn_s_setprio(0);
 }
 
 // the persistent tile loop of one wave group (PHASE: see run_layer8x2); the two groups run two copies of the code

@@ -142,4 +142,84 @@ __device__ __forceinline__ void make_pe_sun8(float x0, float x1, float x2, int h
     pack16(v, pe[0]);
 }
 
+// ---- the same digits on v_mfma_i32_16x16x64_i8 (program.h "k64"; kernels_i8x2.hip run_layer16).  Lane l = 16 g + c works for the TWO points c and 16 + c
+// of its wave's 32 (column groups 0 and 1) and holds, of each, the 16 k bytes of lane group g.
+struct FragK {          // B operand of one 64-slot k-step, per column group: 16 high digits + 16 low digits
+    i32x4 hi[2], lo[2];
+};
+struct AccK {           // M, X as in Acc8: rows 4 g + i of column c, per column group
+    i32x4 M[2], X[2];
+};
+// the digit products of one weight pair: six MFMAs, the two column groups alternating (no MFMA waits for the one issued before it)
+__device__ __forceinline__ void mfma_k64x3(const i32x4& aT, const i32x4& aL, const FragK& b, AccK& acc) {
+    acc.M[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aT, b.hi[0], acc.M[0], 0, 0, 0);
+    acc.M[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aT, b.hi[1], acc.M[1], 0, 0, 0);
+    acc.X[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aT, b.lo[0], acc.X[0], 0, 0, 0);
+    acc.X[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aT, b.lo[1], acc.X[1], 0, 0, 0);
+    acc.X[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aL, b.hi[0], acc.X[0], 0, 0, 0);
+    acc.X[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aL, b.hi[1], acc.X[1], 0, 0, 0);
+}
+// the coordinates of this lane's two points from the one-point-per-lane form around the chain (lane l & 31 = point): xq[column group][dim]
+__device__ __forceinline__ void k64_two_points(float x0, float x1, float x2, int lane, float (*xq)[3]) {
+    asm volatile("" : "+v"(lane));      // the source lanes are formed here, per tile (not hoisted out of the tile loop and kept across the chain)
+#pragma unroll
+    for (int cg = 0; cg < 2; ++cg) {
+        const int src = 16 * cg + (lane & 15);
+        xq[cg][0] = __shfl(x0, src, 64); xq[cg][1] = __shfl(x1, src, 64); xq[cg][2] = __shfl(x2, src, 64);
+    }
+}
+// row r of a raw head's block (raw[4 cg + i] = row 4 g + i of point 16 cg + c) as one value per point, in lane l & 31 = point
+__device__ __forceinline__ float k64_head_row(const float* raw, int r, int lane) {
+    asm volatile("" : "+v"(lane));      // as in k64_two_points
+    const int src = 16 * (r / 4) + (lane & 15);
+    const float a = __shfl(raw[r % 4], src, 64), b = __shfl(raw[4 + r % 4], src, 64);
+    return (lane & 16) ? b : a;
+}
+// PE(pos): pairs p = 8 g + q (k64_pepos_feature), cos in byte 2 q, sin in 2 q + 1.  The per-lane pair indices are made opaque per tile: left visible, hipcc
+// hoists what it derives from them out of the persistent tile loop and keeps it alive across the whole chain.
+__device__ __forceinline__ void make_pe_pos_k64(const float (*xq)[3], int g, FragK& pe) {
+    int gv = g;
+    asm volatile("" : "+v"(gv));
+#pragma unroll
+    for (int cg = 0; cg < 2; ++cg) {
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int p = 8 * gv + q, d = p / 10, f = p - 10 * d;
+            const PeArg a = pe_arg(d == 0 ? xq[cg][0] : d == 1 ? xq[cg][1] : xq[cg][2]);
+            pe_sincos_exp(a, f, v[2 * q], v[2 * q + 1]);
+            if (q >= 6) {                         // pairs 30, 31 of lane group 3: pads (their weights are zero)
+                v[2 * q] = p < 30 ? v[2 * q] : 0.f;
+                v[2 * q + 1] = p < 30 ? v[2 * q + 1] : 0.f;
+            }
+        }
+        Frag8 f8;
+        pack16(v, f8);
+        pe.hi[cg] = f8.hi;
+        pe.lo[cg] = f8.lo;
+        __builtin_amdgcn_sched_barrier(0);        // one point's fp64 reductions at a time (register pressure)
+    }
+}
+// PE(sun): pairs p = 3 g + q in bytes 0..5 (k64_pesun_feature), the rest pads
+__device__ __forceinline__ void make_pe_sun_k64(const float (*sq)[3], int g, FragK& pe) {
+    int gv = g;
+    asm volatile("" : "+v"(gv));
+#pragma unroll
+    for (int cg = 0; cg < 2; ++cg) {
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int p = 3 * gv + q, d = p >> 2, f = p & 3;
+            const PeArg a = pe_arg(d == 0 ? sq[cg][0] : d == 1 ? sq[cg][1] : sq[cg][2]);
+            pe_sincos_exp(a, f, v[2 * q], v[2 * q + 1]);
+        }
+#pragma unroll
+        for (int e = 6; e < 16; ++e) v[e] = 0.f;
+        Frag8 f8;
+        pack16(v, f8);
+        pe.hi[cg] = f8.hi;
+        pe.lo[cg] = f8.lo;
+    }
+}
+
 }  // namespace snerf

@@ -338,6 +338,83 @@ bool pack_program_i8(const Weights& w, int prog, int W, int C, bool fold_bn, Pac
     });
 }
 
+// ---- the same digits for v_mfma_i32_16x16x64_i8 (program.h "k64") ------------------------------------------------------------
+// Row scales, integers wq, digits T / L, table values: the expressions of pack_program_i8, so a row's integers are the same in both streams
+// (a row's wsum runs over the same columns in another order; integer sums do not care).  What differs is where they are put.
+bool pack_program_k64(const Weights& w, int W, int C, bool fold_bn, Packed* out, std::string* err) {
+    if (!k64_width(W)) { *err = "the 16x16x64 stream needs a layer width that is a multiple of 128 (got " + std::to_string(W) + ")"; return false; }
+    if (C < 1 || C > kMaxClasses) { *err = "n_classes must be in [1," + std::to_string(kMaxClasses) + "]"; return false; }
+    out->stream.assign((size_t)k64_chunk_start(W, C, F_NUM) * kChunkBytes, 0);
+    out->bias.assign((size_t)k64_table_start(W, C, F_NUM), 0.f);
+    return parallel_layers(F_NUM, err, [&](int l, std::string* err) {
+        const LayerShape s = k64_layer(W, C, l);
+        Dense d;
+        if (!dense_layer(w, PROG_FIELD, W, C, l, fold_bn, &d, err)) return false;
+        const int f0 = s.kind0 == IN_H ? 64 * s.ks0 : kind_features(s.kind0, s.ks0);
+        auto column = [&](int ks, int g, int j) {
+            int col = -1;
+            if (ks < s.ks0) { const int f = k64_slot_feature(s.kind0, ks, g, j); if (f >= 0) col = f; }
+            else { const int f = k64_slot_feature(s.kind1, ks - s.ks0, g, j); if (f >= 0) col = f0 + f; }
+            return (col >= 0 && col < d.k) ? col : -1;
+        };
+        const int rk = raw_kind(s), rdims = raw_dims(rk), rbase = (rk != IN_NONE && rk == s.kind1 && rk != s.kind0) ? f0 : 0;
+        auto is_raw_col = [&](int c) { return rk != IN_NONE && c >= rbase && c < rbase + rdims; };
+        auto row_of = [&](int n) { return n < s.n_ref ? n : -1; };          // every row map is the identity here: output i is row i of block 0
+        const int n_pad = s.n_out;
+        std::vector<double> scale(n_pad, 0.0);
+        std::vector<long long> wsum(n_pad, 0);
+        std::vector<int> wq((size_t)n_pad * d.k, 0);
+        for (int n = 0; n < n_pad; ++n) {
+            const int rr = row_of(n);
+            if (rr < 0) continue;
+            double mx = 0.0;
+            for (int c = 0; c < d.k; ++c) if (!is_raw_col(c)) mx = std::fmax(mx, std::fabs(d.W[(size_t)rr * d.k + c]));
+            const double sn = mx > 0.0 ? mx / 32512.0 : 1.0;
+            scale[n] = sn;
+            for (int c = 0; c < d.k; ++c) wq[(size_t)n * d.k + c] = (int)std::llround(d.W[(size_t)rr * d.k + c] / sn);
+        }
+        uint8_t* base = out->stream.data() + (size_t)k64_chunk_start(W, C, l) * kChunkBytes;
+        const int nb = k64_blocks(s);
+        for (int b = 0; b < nb; ++b)
+            for (int ks = 0; ks < s.ks(); ++ks) {
+                int8_t* Tf = (int8_t*)(base + (size_t)(b * s.ks() + ks) * kPairBytes);
+                int8_t* Lf = Tf + kFragBytes;
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int r = lane & 15, g = lane >> 4, n = 16 * b + r;
+                    for (int j = 0; j < 16; ++j) {
+                        const int col = column(ks, g, j);
+                        int q = 0;
+                        if (col >= 0 && !is_raw_col(col) && row_of(n) >= 0) { q = wq[(size_t)n * d.k + col]; wsum[n] += q; }
+                        const int T = (q + 128) >> 8;
+                        Tf[lane * 16 + j] = (int8_t)T;
+                        Lf[lane * 16 + j] = (int8_t)(q - 256 * T);
+                    }
+                }
+            }
+        float* tab = out->bias.data() + k64_table_start(W, C, l);
+        for (int b = 0; b < nb; ++b)
+            for (int g = 0; g < 4; ++g)
+                for (int i = 0; i < 4; ++i) {
+                    const int n = 16 * b + 4 * g + i, rr = row_of(n);
+                    float* t = tab + (b * 4 + g) * 8;
+                    t[i] = rr >= 0 ? (float)(256.0 * scale[n] / 32767.0) : 0.f;
+                    t[4 + i] = rr >= 0 ? (float)(d.b[rr] + 128.0 * scale[n] * (double)wsum[n] / 32767.0) : 0.f;
+                }
+        if (rk != IN_NONE) {      // fp32 weights of the raw coordinates: [block][lane group][dim][4 elements]
+            float* rt = tab + 2 * s.n_out;
+            for (int b = 0; b < nb; ++b)
+                for (int g = 0; g < 4; ++g)
+                    for (int i = 0; i < 4; ++i) {
+                        const int n = 16 * b + 4 * g + i, rr = row_of(n);
+                        for (int dd = 0; dd < 3; ++dd)
+                            rt[((b * 4 + g) * 3 + dd) * 4 + i] =
+                                (rr >= 0 && dd < rdims && rbase + dd < d.k) ? (float)d.W[(size_t)rr * d.k + rbase + dd] : 0.f;
+                    }
+        }
+        return true;
+    });
+}
+
 // ---- error model of the int8-digit format ------------------------------------------------------------------
 // Input of layer l of a program: index of the layer whose activations form its IN_H block, or -1 (encodings only).
 static int hidden_source(int prog, int l) {

@@ -32,6 +32,8 @@ bool pack_program(const Weights& w, int prog, int W, int C, bool fold_bn, Packed
 bool permute_program_ks(const Packed& canon, int W, int C, Packed* out, std::string* err, int prog = PROG_FIELD);
 // int8-digit format (FMT_I8): stream of T/L digit fragment pairs, `bias` = per-row [scale | bias] tables
 bool pack_program_i8(const Weights& w, int prog, int W, int C, bool fold_bn, Packed* out, std::string* err);
+// the FIELD program's int8 digits in the layout of v_mfma_i32_16x16x64_i8 (program.h "k64"): the same integers, scales and biases as pack_program_i8
+bool pack_program_k64(const Weights& w, int W, int C, bool fold_bn, Packed* out, std::string* err);
 
 // Pack-time error model of the int8-digit format (what SNERF_PREC_AUTO decides on; include/season_nerf_hip.h snerf_i8_estimate).
 // For every output row of every layer: the variance of the pre-activation error the format adds - weight rounding

@@ -238,4 +238,50 @@ __host__ __device__ constexpr int kind_features(int kind, int ks, int fmt = FMT_
          : kind == IN_PETIME ? PE_TIME_F : 0;
 }
 
+// ---- Third operand format ("k64", the field program at widths that are a multiple of 128): the int8 digits of FMT_I8 - the same integers, scales and
+// biases - laid out for v_mfma_i32_16x16x64_i8 (kernels_i8x2.hip, run_layer16).
+//   * a weight pair (T, L) covers 16 output rows x 64 k-slots: 1 KiB each, lane l = 16 g + r holds row r and the 16 k bytes of lane group g;
+//     pairs, chunks and "every layer starts on a chunk" as in FMT_I8.  A full layer has as many pairs as before; the one-block heads pad to 16 rows;
+//   * the result of one MFMA is 4 registers per lane: rows 4 g + i of column l % 16.  A wave's 32 points are two 16-point column groups, so a lane
+//     holds the digits of TWO points (l % 16 and 16 + l % 16), a quarter of the k range each;
+//   * four consecutive 16-row output blocks b = 0..3 are one k-step of the next layer: lane group g holds, as byte 4 b + i, feature 64 s + 16 b + 4 g + i;
+//   * the encodings choose their own slot order (k64_pepos_feature, k64_pesun_feature); their raw coordinates have no slot at all (fp32 table);
+//   * tables: [block][lane group g][4 scales | 4 biases], then for layers that read an encoding [block][lane group][dim 0..2][4 elements].
+__host__ __device__ constexpr bool k64_width(int W) { return W >= 128 && W % 128 == 0; }
+__host__ __device__ constexpr LayerShape k64_layer(int W, int C, int l) {
+    LayerShape s = field_layer(W, C, l, FMT_I8);
+    s.ks0 = s.kind0 == IN_H ? s.ks0 / 2 : 1;                // hidden: 64 slots per k-step; an encoding fits one k-step
+    s.ks1 = s.kind1 == IN_NONE ? 0 : 1;
+    if (s.out_kind == OUT_RAW) s.n_out = 16;
+    return s;
+}
+__host__ __device__ constexpr int k64_blocks(const LayerShape& s) { return s.n_out / 16; }
+__host__ __device__ constexpr int k64_pairs(const LayerShape& s) { return k64_blocks(s) * s.ks(); }
+__host__ __device__ constexpr int k64_chunks(const LayerShape& s) { return (k64_pairs(s) + kChunkPairs - 1) / kChunkPairs; }
+__host__ __device__ constexpr int k64_chunk_start(int W, int C, int l) {
+    int c = 0;
+    for (int i = 0; i < l; ++i) c += k64_chunks(k64_layer(W, C, i));
+    return c;
+}
+__host__ __device__ constexpr int k64_table_start(int W, int C, int l) {
+    int c = 0;
+    for (int i = 0; i < l; ++i) c += layer_table_floats(k64_layer(W, C, i));
+    return c;
+}
+// PE(pos): the 30 (coordinate, frequency) pairs p = 10 d + f in order, eight per lane group (group 3: six and two pads); byte j = 2 q + (sin ? 1 : 0)
+__host__ __device__ constexpr int k64_pepos_feature(int j, int g) {
+    const int p = 8 * g + j / 2;
+    return p < 30 ? 3 + 20 * (p / 10) + 10 * (j & 1) + p % 10 : -1;
+}
+// PE(sun): the 12 pairs p = 4 d + f, three per lane group in bytes 0..5
+__host__ __device__ constexpr int k64_pesun_feature(int j, int g) {
+    const int p = 3 * g + j / 2;
+    return j < 6 ? 3 + 8 * (p / 4) + 4 * (j & 1) + p % 4 : -1;
+}
+// k-step s of an input block of `kind`, lane group g, byte j -> feature of that block (-1: zero weight)
+__host__ __device__ constexpr int k64_slot_feature(int kind, int s, int g, int j) {
+    return kind == IN_H ? 64 * s + 16 * (j >> 2) + 4 * g + (j & 3) : s != 0 ? -1 : kind == IN_PEPOS ? k64_pepos_feature(j, g)
+         : kind == IN_PESUN ? k64_pesun_feature(j, g) : -1;
+}
+
 }  // namespace snerf
