@@ -411,6 +411,42 @@ int snerf_linear_wgrad(int64_t n_points, int n_in, int n_out, const float* d_gra
 /* test introspection: synchronous copy of an internal buffer ("d_rho", "d_col", "d_head", "d_sky", "d_sv_raw", "rho", "col", "sv", "sky", ...)
  * to the host.  "d_sv_raw": dL/dSolar_Vis of the classic solar model, as the pre-sigmoid gradient the network backward consumed. */
 int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out, int64_t n_floats);
+/* test introspection: ONE launcher of the training engine's element kernels (csrc/train.h, csrc/train_kernels.hip) on the caller's device buffers, without
+ * a trainer.  op names the launcher; sizes (counts, leading dimensions and flags), scalars and device pointers come in the order given below and in
+ * exactly these numbers.  Everything the launcher takes on trust is checked BEFORE any HIP call - required pointers non-null (and 4-byte aligned, the
+ * double sums 8-byte), counts non-negative, leading dimensions >= column counts, 1 <= n_classes <= 8 for the point outputs, K <= 4 and thin_dgrad_ok for
+ * the thin input gradient - otherwise SNERF_E_INVALID with a message and nothing is launched (no GPU is needed to be refused).  Asynchronous on `stream`.
+ * Returns a negative SNERF_E_* code or the kernel the launcher chose (its own decision, not a restatement of it):
+ *    0 pe_points_kernel          1 pe_small_kernel            2 colreduce_kernel           3..6 colpass_vec_kernel<1..4>
+ *    7 bn_bwd2_kernel            8 bn_finalize_kernel         9 bn_finalize_shifted_kernel 10 act_sums_finalize_kernel
+ *   11 act_table_kernel         12 sin_fwd_kernel            13 sin_fwd_vec_kernel         14 thin_dgrad_kernel<false>
+ *   15 thin_dgrad_kernel<true>  16 point_out_fwd_kernel      17 point_out_bwd_kernel       18 softmax_kernel
+ *   19 softmax_bwd_kernel       20 sigmoid_kernel            21 sigmoid_bwd_kernel         22 colsum_kernel
+ *   23 copy_cols_kernel         24 bcast_rows_kernel         25 reduce_rows_kernel         26 fill_zero_kernel
+ *   27 copy_f32_kernel          28 fill_zero_bytes_kernel    29 copy_bytes_kernel
+ * Operations - sizes | scalars | pointers ("?" = may be NULL):
+ *   pe_points            n, n_samples, ld2 | - | points?, top?, bot?, tvals?, pe, pts?, pe2?     (points, or top + bot + tvals with n_samples | n)
+ *   pe_small             rows, in_stride, n_dims, n_freq, out_stride | - | in, out
+ *   colreduce            mode (0..2), M, C, ld, ldd (0 = ld) | alpha0 | Z, D?, mu?, istd?, gamma?, beta?, out0, out1?   (mode 1 needs all, mode 2 needs D)
+ *   bn_bwd2              M, C, ld, ldd, M_global (>= M), d_is_dy | alpha | Z, D, mu, istd, gamma, beta, sdy, sdyx, dbias?
+ *   bn_finalize          M, C, stage (0..2) | - | colsum?, m2?, mean?, istd?, running_mean?, running_var?   (what the stage reads and writes)
+ *   bn_finalize_shifted  M, C | alpha | stats, bias, mean, istd, running_mean, running_var, gamma?, beta?, tab?
+ *   act_sums_finalize    C | scale0 | stats, out0?, out1?, acc0?, acc1?
+ *   act_table            n | - | mu?, istd?, gamma?, beta? (all or none), dst
+ *   sin_fwd              M, C, ldz, ldh | - | Z, H, mu?, istd?, gamma?, beta? (all or none)
+ *   thin_dgrad           M, N, K, ldd, ldw, ldc, accumulate, eld | alpha | D, W, W3?, C, ez?, etab?, emu?, eistd?, stats?
+ *   point_out_fwd / point_out_bwd   n, n_samples, n_classes | - | head, adj, sv_raw, cls, rho, col, sv, adjust_col, d_rho, d_col, d_sv, d_head, d_adj, d_cls,
+ *                        d_sv_raw   (each optional as the kernels allow)
+ *   softmax              rows, C | - | logits, p             softmax_bwd   rows, C | - | p, dp, dlogits
+ *   sigmoid              n | - | x, y                        sigmoid_bwd   n | - | y, dy, dx
+ *   colsum               M, C, ld | alpha | X, out           copy_cols     M, C, ld_src, ld_dst, accumulate | - | src, dst
+ *   bcast_rows           n, n_samples, C, ld_dst, col0 | - | src, dst      reduce_rows   n_groups, n_samples, C, ld_src, col0 | - | src, dst
+ *   fill_zero            n | - | p                           copy_f32      n | - | dst, src
+ *   fill_zero_bytes      bytes | - | p                       copy_bytes    bytes | - | dst, src
+ *   colpass_rows_per_block  M, C | - | -   and   thin_dgrad_rows_per_block  M, N | - | -   launch nothing: they return the rows one block (one chunk)
+ *                        of colpass_vec_kernel / thin_dgrad_kernel walks at this shape, as the launcher derives it. */
+int snerf_train_kernel_debug(const char* op, const int64_t* sizes, int n_sizes, const float* scalars, int n_scalars, void* const* d_ptrs, int n_ptrs,
+                             void* stream);
 /* test introspection of the bf16x3 row GEMMs' routing (csrc/gemm.hip plan_gemm_rows: which of the separately compiled kernel instances a product runs on).
  * snerf_rows_debug_set - state of the CALLING THREAD, (NULL, 0, 0) restores the default:
  *   switches8: NULL = the process's own environment switches, else eight ints that replace them for every reader - SNERF_GEMM_AREG, SNERF_GEMM_AREG_ACT,

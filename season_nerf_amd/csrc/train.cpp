@@ -814,6 +814,176 @@ int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out
     return SNERF_OK;
 }
 
+// Introspection for tests: one launcher of train.h on the caller's buffers (include/season_nerf_hip.h lists the operations and their arguments).
+// Everything a launcher takes on trust is checked here first; the return value is the launcher's own *_choice where it has one.
+int snerf_train_kernel_debug(const char* op, const int64_t* s, int n_sizes, const float* f, int n_scalars, void* const* p, int n_ptrs, void* stream) {
+    struct OpDesc { const char* name; int ns, nf, np; };
+    static const OpDesc ops[] = {
+        {"pe_points", 3, 0, 7}, {"pe_small", 5, 0, 2}, {"colreduce", 5, 1, 8}, {"bn_bwd2", 6, 1, 9}, {"bn_finalize", 3, 0, 6},
+        {"bn_finalize_shifted", 2, 1, 9}, {"act_sums_finalize", 1, 1, 5}, {"act_table", 1, 0, 5}, {"sin_fwd", 4, 0, 6},
+        {"thin_dgrad", 8, 1, 9}, {"point_out_fwd", 3, 0, 15}, {"point_out_bwd", 3, 0, 15}, {"softmax", 2, 0, 2}, {"softmax_bwd", 2, 0, 3},
+        {"sigmoid", 1, 0, 2}, {"sigmoid_bwd", 1, 0, 3}, {"colsum", 3, 1, 2}, {"copy_cols", 5, 0, 2}, {"bcast_rows", 5, 0, 2},
+        {"reduce_rows", 5, 0, 2}, {"fill_zero", 1, 0, 1}, {"copy_f32", 1, 0, 2}, {"fill_zero_bytes", 1, 0, 1}, {"copy_bytes", 1, 0, 2},
+        {"colpass_rows_per_block", 2, 0, 0}, {"thin_dgrad_rows_per_block", 2, 0, 0}};
+    if (!op) return snerf_set_error(SNERF_E_INVALID, "snerf_train_kernel_debug: NULL operation name");
+    const std::string k = op;
+    const OpDesc* d = nullptr;
+    for (const OpDesc& o : ops)
+        if (k == o.name) d = &o;
+    if (!d) return snerf_set_error(SNERF_E_INVALID, "snerf_train_kernel_debug: unknown operation " + k);
+    const auto bad = [&](const char* what) { return snerf_set_error(SNERF_E_INVALID, "snerf_train_kernel_debug: " + k + ": " + what); };
+    if (n_sizes != d->ns || n_scalars != d->nf || n_ptrs != d->np) return bad("wrong number of sizes, scalars or pointers");
+    if ((d->ns && !s) || (d->nf && !f) || (d->np && !p)) return bad("NULL argument array");
+    for (int i = 0; i < d->ns; ++i)
+        if (s[i] < 0 || s[i] > ((int64_t)1 << 40)) return bad("a size is negative or too large");
+    for (int i = 0; i < d->np; ++i)
+        if ((uintptr_t)p[i] % 4 != 0 && k != "fill_zero_bytes" && k != "copy_bytes") return bad("a float pointer is not 4-byte aligned");
+    const auto F = [&](int i) { return (float*)p[i]; };
+    const auto fits_int = [&](int64_t v) { return v <= 0x7fffffff; };
+    hipStream_t st = (hipStream_t)stream;
+    int kernel = -1;
+    hipError_t e = hipSuccess;
+    if (k == "colpass_rows_per_block" || k == "thin_dgrad_rows_per_block") {
+        if (s[1] < 4 || s[1] % 4 || s[1] > 1024) return bad("the column count must be a multiple of 4 in 4..1024");
+        return k[0] == 'c' ? colpass_rows_per_block(s[0], (int)s[1]) : thin_dgrad_rows_per_block(s[0], (int)s[1]);
+    } else if (k == "pe_points") {                  // sizes n, n_samples, ld2; pointers points, top, bot, tvals, pe, pts, pe2
+        PeArgs a{};
+        a.n = s[0]; a.n_samples = (int)s[1]; a.ld2 = s[2];
+        a.points = F(0); a.top = F(1); a.bot = F(2); a.tvals = F(3); a.pe = F(4); a.pts = F(5); a.pe2 = F(6);
+        if (!a.pe) return bad("pe is NULL");
+        if (!a.points && (!a.top || !a.bot || !a.tvals || s[1] < 1 || !fits_int(s[1]) || a.n % s[1] != 0)) return bad("the rays form needs top, bot, tvals and n a multiple of n_samples >= 1");
+        if (a.pe2 && a.ld2 < 64) return bad("ld2 < 64");
+        kernel = TK_PE_POINTS;
+        e = launch_pe_points(a, st);
+    } else if (k == "pe_small") {            // sizes rows, in_stride, n_dims, n_freq, out_stride; pointers in, out
+        if (!p[0] || !p[1]) return bad("NULL pointer");
+        if (s[2] < 1 || s[2] > 16 || s[3] > 30 || s[1] < s[2] || !fits_int(s[1]) || !fits_int(s[4]) || s[4] < s[2] * (2 * s[3] + 1)) return bad("bad dimensions, frequencies or strides");
+        kernel = TK_PE_SMALL;
+        e = launch_pe_small(F(0), (int)s[1], (int)s[2], (int)s[3], s[0], F(1), (int)s[4], st);
+    } else if (k == "colreduce") {           // sizes mode, M, C, ld, ldd; scalar alpha0; pointers Z, D, mu, istd, gamma, beta, out0, out1
+        ColArgs a{};
+        a.mode = (int)s[0]; a.M = s[1]; a.C = (int)s[2]; a.ld = s[3]; a.ldd = s[4]; a.alpha0 = f[0];
+        a.Z = F(0); a.D = F(1); a.mu = F(2); a.istd = F(3); a.gamma = F(4); a.beta = F(5); a.out0 = F(6); a.out1 = F(7);
+        if (s[0] > 2) return bad("mode must be 0, 1 or 2");
+        if (s[2] < 1 || !fits_int(s[2]) || a.ld < a.C || (a.ldd && a.ldd < a.C)) return bad("C < 1 or a leading dimension below C");
+        if (!a.Z || !a.out0 || (a.mode != 0 && !a.D)) return bad("Z, out0 or D is NULL");
+        if (a.mode == 1 && (!a.mu || !a.istd || !a.gamma || !a.beta || !a.out1)) return bad("mode 1 needs mu, istd, gamma, beta and out1");
+        kernel = colreduce_choice(a);
+        e = launch_colreduce(a, st);
+    } else if (k == "bn_bwd2") {             // sizes M, C, ld, ldd, M_global, d_is_dy; scalar alpha; pointers Z, D, mu, istd, gamma, beta, sdy, sdyx, dbias
+        if (s[1] < 1 || !fits_int(s[1]) || s[2] < s[1] || (s[3] && s[3] < s[1])) return bad("C < 1 or a leading dimension below C");
+        if (s[4] < s[0] || s[4] < 1) return bad("M_global must be at least M and 1");
+        if (s[5] > 1) return bad("d_is_dy must be 0 or 1");
+        for (int i = 0; i < 8; ++i)
+            if (!p[i]) return bad("NULL pointer (only dbias is optional)");
+        kernel = bn_bwd2_choice(F(0), F(1), (int)s[1], s[2], s[3], s[5] != 0);
+        e = launch_bn_bwd2(F(0), F(1), s[0], (int)s[1], s[2], s[3], F(2), F(3), F(4), F(5), F(6), F(7), F(8), f[0], s[4], st, s[5] != 0);
+    } else if (k == "bn_finalize") {         // sizes M, C, stage; pointers colsum, m2, mean, istd, running_mean, running_var
+        if (s[1] < 1 || !fits_int(s[1]) || s[2] > 2) return bad("C < 1 or stage outside 0..2");
+        if (s[2] != 2 && s[0] < 1) return bad("M < 1");
+        if (s[2] == 0 ? (!p[0] || !p[2]) : (!p[1] || !p[3])) return bad("NULL pointer");
+        if (s[2] == 1 && (!p[2] || !p[4] || !p[5])) return bad("stage 1 needs mean and the running statistics");
+        kernel = TK_BN_FINALIZE;
+        e = launch_bn_finalize(F(0), F(1), s[0], (int)s[1], F(2), F(3), F(4), F(5), (int)s[2], st);
+    } else if (k == "bn_finalize_shifted") { // sizes M, C; scalar alpha; pointers stats, bias, mean, istd, running_mean, running_var, gamma, beta, tab
+        if (s[0] < 1 || s[1] < 1 || !fits_int(s[1])) return bad("M < 1 or C < 1");
+        for (int i = 0; i < 6; ++i)
+            if (!p[i]) return bad("NULL pointer");
+        if ((uintptr_t)p[0] % 8) return bad("stats is not 8-byte aligned");
+        if (p[8] && (!p[6] || !p[7])) return bad("tab needs gamma and beta");
+        kernel = TK_BN_FINALIZE_SHIFTED;
+        e = launch_bn_finalize_shifted((double*)p[0], F(1), f[0], s[0], (int)s[1], F(2), F(3), F(4), F(5), F(6), F(7), F(8), st);
+    } else if (k == "act_sums_finalize") {   // size C; scalar scale0; pointers stats, out0, out1, acc0, acc1
+        if (s[0] < 1 || !fits_int(s[0])) return bad("C < 1");
+        if (!p[0] || (uintptr_t)p[0] % 8) return bad("stats is NULL or not 8-byte aligned");
+        kernel = TK_ACT_SUMS_FINALIZE;
+        e = launch_act_sums_finalize((double*)p[0], (int)s[0], f[0], F(1), F(2), F(3), F(4), st);
+    } else if (k == "act_table") {           // size n; pointers mu, istd, gamma, beta, dst
+        if (s[0] < 1 || !fits_int(s[0])) return bad("n < 1");
+        if (!p[4]) return bad("dst is NULL");
+        if (p[0] ? (!p[1] || !p[2] || !p[3]) : (p[1] || p[2] || p[3])) return bad("the statistics are all set or all NULL");
+        kernel = TK_ACT_TABLE;
+        e = launch_act_table(F(0), F(1), F(2), F(3), (int)s[0], F(4), st);
+    } else if (k == "sin_fwd") {             // sizes M, C, ldz, ldh; pointers Z, H, mu, istd, gamma, beta
+        if (s[1] < 1 || !fits_int(s[1]) || s[2] < s[1] || s[3] < s[1]) return bad("C < 1 or a leading dimension below C");
+        if (!p[0] || !p[1]) return bad("NULL pointer");
+        if (p[2] ? (!p[3] || !p[4] || !p[5]) : (p[3] || p[4] || p[5])) return bad("the statistics are all set or all NULL");
+        kernel = sin_fwd_choice(F(0), F(1), (int)s[1], s[2], s[3]);
+        e = launch_sin_fwd(F(0), F(1), s[0], (int)s[1], s[2], s[3], F(2), F(3), F(4), F(5), st);
+    } else if (k == "thin_dgrad") {          // sizes M, N, K, ldd, ldw, ldc, accumulate, eld; scalar alpha; pointers D, W, W3, C, ez, etab, emu, eistd, stats
+        ThinDgradArgs a{};
+        a.M = s[0]; a.N = (int)s[1]; a.K = (int)s[2]; a.ldd = s[3]; a.ldw = s[4]; a.ldc = s[5]; a.accumulate = (int)s[6]; a.eld = s[7]; a.alpha = f[0];
+        a.D = F(0); a.W = F(1); a.W3 = F(2); a.C = F(3); a.ez = F(4); a.etab = F(5); a.emu = F(6); a.eistd = F(7); a.stats = (double*)p[8];
+        if (s[2] < 1 || s[2] > 4) return bad("K must be 1..4");
+        if (s[1] < 4 || s[1] > 1024 || a.ldd < a.K || a.ldw < a.N || a.ldc < a.N || s[6] > 1) return bad("N outside 4..1024, a leading dimension below its column count, or accumulate not 0 / 1");
+        if (!a.D || !a.W || !a.C) return bad("NULL pointer");
+        if (a.W3 && a.K != 4) return bad("W3 needs K = 4");
+        if (a.ez && (a.eld < a.N || (uintptr_t)p[8] % 8 || !a.emu != !a.eistd)) return bad("the epilogue needs eld >= N, aligned sums and both or neither of emu / eistd");
+        if (!a.ez && (a.etab || a.emu || a.eistd || a.stats)) return bad("epilogue arguments without ez");
+        if (!thin_dgrad_ok(a)) return bad("thin_dgrad_ok refuses the shape (N, ldc, eld multiples of 4, 16-byte bases, table and sums with ez)");
+        kernel = thin_dgrad_choice(a);
+        e = launch_thin_dgrad(a, st);
+    } else if (k == "point_out_fwd" || k == "point_out_bwd") {      // sizes n, n_samples, C; pointers in the order of PointOutArgs
+        const bool bwd = k == "point_out_bwd";
+        PointOutArgs a{};
+        a.n = s[0]; a.n_samples = (int)s[1]; a.C = (int)s[2];
+        a.head = F(0); a.adj = F(1); a.sv_raw = F(2); a.cls = F(3); a.rho = F(4); a.col = F(5); a.sv = F(6); a.adjust_col = F(7);
+        a.d_rho = F(8); a.d_col = F(9); a.d_sv = F(10); a.d_head = F(11); a.d_adj = F(12); a.d_cls = F(13); a.d_sv_raw = F(14);
+        if (s[1] < 1 || !fits_int(s[1])) return bad("n_samples < 1");
+        if (!bwd) {
+            if ((a.rho || a.col) && !a.head) return bad("rho and col need head");
+            if (a.col && (s[2] < 1 || s[2] > 8 || !a.adj || !a.cls)) return bad("col needs 1 <= n_classes <= 8, adj and cls");
+            if (a.adjust_col && !a.col) return bad("adjust_col needs col");
+            if (a.sv && !a.sv_raw) return bad("sv needs sv_raw");
+            if (!a.rho && !a.col && !a.sv) return bad("no output");
+        } else {
+            if (a.d_head && (s[2] < 1 || s[2] > 8 || !a.head || !a.adj || !a.cls)) return bad("d_head needs 1 <= n_classes <= 8, head, adj and cls");
+            if (a.d_col && !a.col) return bad("d_col needs col");
+            if ((a.d_adj || a.d_cls) && !a.d_head) return bad("d_adj and d_cls need d_head");
+            if (!a.d_sv_raw != !a.d_sv || (a.d_sv && !a.sv)) return bad("d_sv_raw needs d_sv and sv");
+            if (!a.d_head && !a.d_sv_raw) return bad("no output");
+        }
+        kernel = bwd ? TK_POINT_OUT_BWD : TK_POINT_OUT_FWD;
+        e = launch_point_out(a, bwd, st);
+    } else if (k == "softmax" || k == "softmax_bwd") {              // sizes rows, C; pointers x, p / p, dp, dx
+        if (s[1] < 1 || !fits_int(s[1])) return bad("C < 1");
+        for (int i = 0; i < d->np; ++i)
+            if (!p[i]) return bad("NULL pointer");
+        kernel = d->np == 2 ? TK_SOFTMAX : TK_SOFTMAX_BWD;
+        e = d->np == 2 ? launch_softmax(F(0), F(1), s[0], (int)s[1], st) : launch_softmax_bwd(F(0), F(1), F(2), s[0], (int)s[1], st);
+    } else if (k == "sigmoid" || k == "sigmoid_bwd") {              // size n; pointers x, y / y, dy, dx
+        for (int i = 0; i < d->np; ++i)
+            if (!p[i]) return bad("NULL pointer");
+        kernel = d->np == 2 ? TK_SIGMOID : TK_SIGMOID_BWD;
+        e = d->np == 2 ? launch_sigmoid(F(0), F(1), s[0], st) : launch_sigmoid_bwd(F(0), F(1), F(2), s[0], st);
+    } else if (k == "colsum") {              // sizes M, C, ld; scalar alpha; pointers X, out
+        if (s[1] < 1 || !fits_int(s[1]) || s[2] < s[1]) return bad("C < 1 or ld < C");
+        if (!p[0] || !p[1]) return bad("NULL pointer");
+        kernel = TK_COLSUM;
+        e = launch_colsum(F(0), s[0], (int)s[1], s[2], f[0], F(1), st);
+    } else if (k == "copy_cols") {           // sizes M, C, ld_src, ld_dst, accumulate; pointers src, dst
+        if (s[1] < 1 || !fits_int(s[1]) || s[2] < s[1] || s[3] < s[1] || s[4] > 1) return bad("C < 1, a leading dimension below C, or accumulate not 0 / 1");
+        if (!p[0] || !p[1]) return bad("NULL pointer");
+        kernel = TK_COPY_COLS;
+        e = launch_copy_cols(F(0), s[2], F(1), s[3], s[0], (int)s[1], s[4] != 0, st);
+    } else if (k == "bcast_rows" || k == "reduce_rows") {           // sizes n (points) / n_groups, n_samples, C, ld of the per-point matrix, col0; pointers src, dst
+        if (s[1] < 1 || !fits_int(s[1]) || s[2] < 1 || !fits_int(s[2]) || !fits_int(s[4]) || s[3] < s[4] + s[2]) return bad("n_samples < 1, C < 1 or ld < col0 + C");
+        if (!p[0] || !p[1]) return bad("NULL pointer");
+        kernel = k[0] == 'b' ? TK_BCAST_ROWS : TK_REDUCE_ROWS;
+        e = k[0] == 'b' ? launch_bcast_rows(F(0), (int)s[2], F(1), s[3], (int)s[4], s[0], (int)s[1], st)
+                        : launch_reduce_rows(F(0), s[3], (int)s[4], (int)s[2], F(1), s[0], (int)s[1], st);
+    } else {                                 // fill_zero, copy_f32 (size: floats), fill_zero_bytes, copy_bytes (size: bytes); pointers dst [, src]
+        for (int i = 0; i < d->np; ++i)
+            if (!p[i]) return bad("NULL pointer");
+        if (k == "fill_zero") { kernel = TK_FILL_ZERO; e = launch_fill_zero(F(0), s[0], st); }
+        else if (k == "copy_f32") { kernel = TK_COPY_F32; e = launch_copy_f32(F(0), F(1), s[0], st); }
+        else if (k == "fill_zero_bytes") { kernel = TK_FILL_ZERO_BYTES; e = launch_fill_zero_bytes(p[0], (size_t)s[0], st); }
+        else { kernel = TK_COPY_BYTES; e = launch_copy_bytes(p[0], p[1], (size_t)s[0], st); }
+    }
+    if (e != hipSuccess) return snerf_set_error(SNERF_E_HIP, "snerf_train_kernel_debug: " + k + ": " + hipGetErrorString(e));
+    return kernel;
+}
+
 // Introspection for tests: the row GEMMs' routing (rows_debug.h).
 int snerf_rows_debug_set(const int* switches8, int dry_run, int x_padded) {
     if (switches8 && switches8[4] != 0 && switches8[4] != 2 && switches8[4] != 4 && switches8[4] != 8) return snerf_set_error(SNERF_E_INVALID, "snerf_rows_debug_set: pf must be 0, 2, 4 or 8");

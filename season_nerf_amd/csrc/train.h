@@ -72,6 +72,14 @@ hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t 
                                const WgradBN* bn = nullptr, int in_tab_stride = 0);      // in_tab_stride: see WgradX (0 = in_cols)
 
 // ---- elementwise / reduction kernels of the training path (train_kernels.hip)
+// The kernel a launcher runs, as the test hook snerf_train_kernel_debug returns it (include/season_nerf_hip.h documents the numbers).  Where a launcher
+// chooses between kernels, the *_choice function below IS its decision: the launcher branches on it and the hook reports it.
+enum TrainKernel : int {
+    TK_PE_POINTS = 0, TK_PE_SMALL, TK_COLREDUCE, TK_COLPASS_VEC1, TK_COLPASS_VEC2, TK_COLPASS_VEC3, TK_COLPASS_VEC4, TK_BN_BWD2, TK_BN_FINALIZE,
+    TK_BN_FINALIZE_SHIFTED, TK_ACT_SUMS_FINALIZE, TK_ACT_TABLE, TK_SIN_FWD, TK_SIN_FWD_VEC, TK_THIN_DGRAD, TK_THIN_DGRAD_ACT, TK_POINT_OUT_FWD,
+    TK_POINT_OUT_BWD, TK_SOFTMAX, TK_SOFTMAX_BWD, TK_SIGMOID, TK_SIGMOID_BWD, TK_COLSUM, TK_COPY_COLS, TK_BCAST_ROWS, TK_REDUCE_ROWS, TK_FILL_ZERO,
+    TK_COPY_F32, TK_FILL_ZERO_BYTES, TK_COPY_BYTES, TK_COUNT
+};
 struct PeArgs {            // positions (from rays or explicit) -> PE(pos) [N,64] (63 features + zero pad) and points [N,3]
     int64_t n;
     int n_samples;
@@ -101,6 +109,8 @@ struct ColArgs {
     float alpha0;          // scale of the out0 accumulation (mode 2: 30 = d bias of the Linear)
     int64_t M_global;      // mode 3: rows of the global batch the BatchNorm means were taken over (>= M)
 };
+int colreduce_choice(const ColArgs& a);                  // TK_COLREDUCE, TK_COLPASS_VEC1 or TK_COLPASS_VEC2
+int colpass_rows_per_block(int64_t M, int C);            // rows a block of colpass_vec_kernel walks (32..512)
 hipError_t launch_colreduce(const ColArgs& a, hipStream_t st);
 struct ThinDgradArgs {     // input gradient of a head with K <= 4 outputs as a stream over C (train_kernels.hip: thin_dgrad_kernel)
     const float* D;        // [M, ldd]: dL/d(head output), K leading columns
@@ -118,6 +128,8 @@ struct ThinDgradArgs {     // input gradient of a head with K <= 4 outputs as a 
     double* stats;
 };
 bool thin_dgrad_ok(const ThinDgradArgs& a);
+int thin_dgrad_choice(const ThinDgradArgs& a);           // TK_THIN_DGRAD or TK_THIN_DGRAD_ACT
+int thin_dgrad_rows_per_block(int64_t M, int N);         // rows of a chunk of thin_dgrad_kernel (32..256)
 hipError_t launch_thin_dgrad(const ThinDgradArgs& a, hipStream_t st);
 struct ThinFwdArgs {       // forward of heads with K <= 4 outputs in all as one stream over their common input (train_kernels.hip: thin_fwd_kernel)
     const float* In;       // [M, ldi], N columns (the first tab_cols of them stored as pre-activations: activation on load)
@@ -158,9 +170,11 @@ hipError_t launch_bn_finalize(const float* colsum, const float* m2, int64_t M, i
 hipError_t launch_bn_finalize_shifted(double* stats, const float* bias, float alpha, int64_t M, int C, float* mean, float* istd,
                                       float* running_mean, float* running_var, const float* gamma, const float* beta, float* tab,
                                       hipStream_t st);
+int sin_fwd_choice(const float* Z, const float* H, int C, int64_t ldz, int64_t ldh);      // TK_SIN_FWD or TK_SIN_FWD_VEC
 hipError_t launch_sin_fwd(const float* Z, float* H, int64_t M, int C, int64_t ldz, int64_t ldh, const float* mu, const float* istd,
                           const float* gamma, const float* beta, hipStream_t st);
 // BN backward second pass: dZ = gamma*istd*(dY - sdy/M - xhat*sdyx/M) in place; colsum(dZ) -> out (bias grad)
+int bn_bwd2_choice(const float* Z, const float* D, int C, int64_t ld, int64_t ldd, bool d_is_dy);      // TK_BN_BWD2, TK_COLPASS_VEC3 or TK_COLPASS_VEC4
 hipError_t launch_bn_bwd2(const float* Z, float* D, int64_t M, int C, int64_t ld, int64_t ldd, const float* mu, const float* istd,
                           const float* gamma, const float* beta, const float* sdy, const float* sdyx, float* dbias_sum, float alpha,
                           int64_t M_global, hipStream_t st, bool d_is_dy = false);

@@ -213,14 +213,21 @@ __global__ __launch_bounds__(256) void colpass_vec_kernel(const ColArgs A, int C
 static bool colpass_vec_ok(const ColArgs& a) {
     return a.C % 4 == 0 && a.C <= 1024 && a.ld % 4 == 0 && a.ldd % 4 == 0 && (uintptr_t)a.Z % 16 == 0 && (uintptr_t)a.D % 16 == 0;
 }
+// 512 rows per block for the per-point arrays; the per-ray branches (a few thousand rows) get shorter blocks so that they still fill the chip
+int colpass_rows_per_block(int64_t M, int C) {
+    const int C4 = C / 4;
+    int cpt = 1;
+    while (cpt < C4) cpt <<= 1;
+    int rpb = ROWS_PER_BLOCK;
+    while (rpb > 32 && rpb > 256 / cpt && (M + rpb - 1) / rpb < 512) rpb >>= 1;
+    return rpb;
+}
 template <int MODE>
 static hipError_t launch_colpass_vec(const ColArgs& a, const float* sdy, const float* sdyx, hipStream_t st) {
     const int C4 = a.C / 4;
     int cpt = 1;
     while (cpt < C4) cpt <<= 1;
-    // 512 rows per block for the per-point arrays; the per-ray branches (a few thousand rows) get shorter blocks so that they still fill the chip
-    int rpb = ROWS_PER_BLOCK;
-    while (rpb > 32 && rpb > 256 / cpt && (a.M + rpb - 1) / rpb < 512) rpb >>= 1;
+    const int rpb = colpass_rows_per_block(a.M, a.C);
     const int64_t blocks = (a.M + rpb - 1) / rpb;
     hipLaunchKernelGGL(colpass_vec_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt, sdy, sdyx, rpb);
     return hipGetLastError();
@@ -332,17 +339,25 @@ bool thin_dgrad_ok(const ThinDgradArgs& a) {
     return a.K >= 1 && a.K <= 4 && a.N % 4 == 0 && a.N <= 1024 && a.ldc % 4 == 0 && (uintptr_t)a.C % 16 == 0 &&
            (!a.ez || (a.eld % 4 == 0 && (uintptr_t)a.ez % 16 == 0 && a.etab && a.stats));
 }
+int thin_dgrad_rows_per_block(int64_t M, int N) {
+    const int C4 = N / 4;
+    int cpt = 1;
+    while (cpt < C4) cpt <<= 1;
+    int rpb = 256;
+    while (rpb > 32 && rpb > 256 / cpt && (M + rpb - 1) / rpb < 1024) rpb >>= 1;
+    return rpb;
+}
+int thin_dgrad_choice(const ThinDgradArgs& a) { return a.ez ? TK_THIN_DGRAD_ACT : TK_THIN_DGRAD; }
 hipError_t launch_thin_dgrad(const ThinDgradArgs& a, hipStream_t st) {
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (!thin_dgrad_ok(a)) return hipErrorInvalidValue;
     const int C4 = a.N / 4;
     int cpt = 1;
     while (cpt < C4) cpt <<= 1;
-    int rpb = 256;
-    while (rpb > 32 && rpb > 256 / cpt && (a.M + rpb - 1) / rpb < 1024) rpb >>= 1;
+    const int rpb = thin_dgrad_rows_per_block(a.M, a.N);
     int64_t blocks = (a.M + rpb - 1) / rpb;
     if (blocks > 1024) blocks = 1024;                       // four resident blocks per CU, each leaves its column sums once
-    if (a.ez) hipLaunchKernelGGL((thin_dgrad_kernel<true, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt, rpb);
+    if (thin_dgrad_choice(a) == TK_THIN_DGRAD_ACT) hipLaunchKernelGGL((thin_dgrad_kernel<true, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt, rpb);
     else hipLaunchKernelGGL((thin_dgrad_kernel<false, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt, rpb);
     return hipGetLastError();
 }
@@ -574,10 +589,16 @@ hipError_t launch_thin_wgrad(const ThinWgradArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+int colreduce_choice(const ColArgs& a) {
+    if (colpass_vec_ok(a) && a.mode == 1) return TK_COLPASS_VEC1;
+    if (colpass_vec_ok(a) && a.mode == 2) return TK_COLPASS_VEC2;
+    return TK_COLREDUCE;
+}
 hipError_t launch_colreduce(const ColArgs& a, hipStream_t st) {
     if (a.M <= 0) return hipSuccess;
-    if (colpass_vec_ok(a) && a.mode == 1) return launch_colpass_vec<1>(a, nullptr, nullptr, st);
-    if (colpass_vec_ok(a) && a.mode == 2) return launch_colpass_vec<2>(a, nullptr, nullptr, st);
+    const int choice = colreduce_choice(a);
+    if (choice == TK_COLPASS_VEC1) return launch_colpass_vec<1>(a, nullptr, nullptr, st);
+    if (choice == TK_COLPASS_VEC2) return launch_colpass_vec<2>(a, nullptr, nullptr, st);
     const int64_t blocks = (a.M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     hipLaunchKernelGGL(colreduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
     return hipGetLastError();
@@ -713,10 +734,13 @@ __global__ __launch_bounds__(256) void sin_fwd_vec_kernel(const float* Z, float*
         *(f32x4_t*)(H + r * ldh + tc * 4) = o;
     }
 }
+int sin_fwd_choice(const float* Z, const float* H, int C, int64_t ldz, int64_t ldh) {
+    return C % 4 == 0 && C <= 1024 && ldz % 4 == 0 && ldh % 4 == 0 && (uintptr_t)Z % 16 == 0 && (uintptr_t)H % 16 == 0 ? TK_SIN_FWD_VEC : TK_SIN_FWD;
+}
 hipError_t launch_sin_fwd(const float* Z, float* H, int64_t M, int C, int64_t ldz, int64_t ldh, const float* mu, const float* istd,
                           const float* gamma, const float* beta, hipStream_t st) {
     if (M <= 0 || C <= 0) return hipSuccess;
-    if (C % 4 == 0 && C <= 1024 && ldz % 4 == 0 && ldh % 4 == 0 && (uintptr_t)Z % 16 == 0 && (uintptr_t)H % 16 == 0) {
+    if (sin_fwd_choice(Z, H, C, ldz, ldh) == TK_SIN_FWD_VEC) {
         const int C4 = C / 4;
         int cpt = 1;
         while (cpt < C4) cpt <<= 1;                       // threads per row, power of two <= 256
@@ -761,6 +785,12 @@ __global__ __launch_bounds__(256) void bn_bwd2_kernel(const float* Z, float* D, 
         __syncthreads();
     }
 }
+int bn_bwd2_choice(const float* Z, const float* D, int C, int64_t ld, int64_t ldd, bool d_is_dy) {
+    ColArgs a{};
+    a.C = C; a.ld = ld; a.ldd = ldd; a.Z = Z; a.D = const_cast<float*>(D);
+    if (!colpass_vec_ok(a)) return TK_BN_BWD2;
+    return d_is_dy ? TK_COLPASS_VEC4 : TK_COLPASS_VEC3;
+}
 hipError_t launch_bn_bwd2(const float* Z, float* D, int64_t M, int C, int64_t ld, int64_t ldd, const float* mu, const float* istd,
                           const float* gamma, const float* beta, const float* sdy, const float* sdyx, float* dbias_sum, float alpha,
                           int64_t M_global, hipStream_t st, bool d_is_dy) {
@@ -768,7 +798,9 @@ hipError_t launch_bn_bwd2(const float* Z, float* D, int64_t M, int C, int64_t ld
     ColArgs a{};
     a.mode = 3; a.M = M; a.M_global = M_global; a.C = C; a.ld = ld; a.ldd = ldd; a.Z = Z; a.D = D; a.mu = mu; a.istd = istd; a.gamma = gamma; a.beta = beta;
     a.out0 = dbias_sum; a.alpha0 = alpha;
-    if (colpass_vec_ok(a)) return d_is_dy ? launch_colpass_vec<4>(a, sdy, sdyx, st) : launch_colpass_vec<3>(a, sdy, sdyx, st);
+    const int choice = bn_bwd2_choice(Z, D, C, ld, ldd, d_is_dy);
+    if (choice == TK_COLPASS_VEC4) return launch_colpass_vec<4>(a, sdy, sdyx, st);
+    if (choice == TK_COLPASS_VEC3) return launch_colpass_vec<3>(a, sdy, sdyx, st);
     const int64_t blocks = (M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     hipLaunchKernelGGL(bn_bwd2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Z, D, M, C, ld, ldd ? ldd : ld, mu, istd, gamma, beta, sdy, sdyx, dbias_sum, alpha,
                        1.f / (float)M_global, d_is_dy ? 1 : 0);

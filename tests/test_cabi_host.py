@@ -34,7 +34,7 @@ def test_exports_match_header(lib):
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
     import season_nerf_amd as sn
     assert sorted(sn._lib.EXPORTS) == declared
-    assert lib.snerf_abi_version() == 8
+    assert lib.snerf_abi_version() == 9
 
 
 def test_custom_op_library_registers_without_a_gpu():
@@ -696,3 +696,92 @@ def test_ksplit_stream_is_a_permutation_of_the_bf16_pairs(lib):
     assert pairs(g0) == pairs(g4) and len(pairs(g4)) > 280
     lib.snerf_model_destroy(m)
 
+
+
+def _tk_call(lib, op, sizes, scalars, ptrs):
+    s = (C.c_int64 * max(1, len(sizes)))(*sizes)
+    f = (C.c_float * max(1, len(scalars)))(*scalars)
+    p = (C.c_void_p * max(1, len(ptrs)))(*ptrs)
+    return lib.snerf_train_kernel_debug(op.encode() if op is not None else None, s, len(sizes), f, len(scalars), p, len(ptrs), None)
+
+
+def test_train_kernel_debug_refuses_before_any_launch(lib):
+    """snerf_train_kernel_debug checks what the launchers of csrc/train.h take on trust before any HIP call: unknown names, wrong argument counts, NULL
+    or misaligned pointers, negative counts, leading dimensions below the column counts, class counts outside 1..8, K outside 1..4, shapes
+    thin_dgrad_ok refuses.  No pointer is read - any aligned non-null address will do - and no GPU is needed to be refused."""
+    buf = np.zeros(64, dtype=np.float32)
+    a = (buf.ctypes.data + 63) // 64 * 64
+    bad = []
+
+    def refused(op, sizes, scalars, ptrs, word):
+        rc = _tk_call(lib, op, sizes, scalars, ptrs)
+        assert rc == -1, (op, sizes, rc)
+        assert word.encode() in lib.snerf_last_error(), (op, sizes, lib.snerf_last_error())
+        bad.append(op)
+
+    refused(None, [], [], [], "NULL operation")
+    refused("colpass", [1], [], [], "unknown operation")
+    refused("sin_fwd", [4, 4, 4], [], [a] * 6, "wrong number")                   # a size short
+    refused("sin_fwd", [4, 4, 4, 4], [1.0], [a] * 6, "wrong number")             # a scalar too many
+    refused("sin_fwd", [4, 4, 4, 4], [], [a] * 5, "wrong number")
+    refused("sin_fwd", [-1, 4, 4, 4], [], [a, a, None, None, None, None], "negative")
+    refused("sin_fwd", [4, 4, 3, 4], [], [a, a, None, None, None, None], "leading dimension")
+    refused("sin_fwd", [4, 4, 4, 4], [], [a, None, None, None, None, None], "NULL")
+    refused("sin_fwd", [4, 4, 4, 4], [], [a, a, a, None, a, a], "all set or all NULL")
+    refused("sin_fwd", [4, 4, 4, 4], [], [a + 2, a, None, None, None, None], "aligned")
+    refused("colreduce", [3, 8, 4, 4, 4], [1.0], [a] * 8, "mode")
+    refused("colreduce", [1, 8, 4, 4, 3], [1.0], [a] * 8, "leading dimension")
+    refused("colreduce", [1, 8, 4, 4, 4], [1.0], [a, a, a, a, a, a, a, None], "mode 1 needs")
+    refused("colreduce", [2, 8, 4, 4, 4], [1.0], [a, None, None, None, None, None, a, None], "NULL")
+    refused("bn_bwd2", [8, 4, 4, 4, 7, 0], [1.0], [a] * 9, "M_global")
+    refused("bn_bwd2", [8, 4, 4, 4, 8, 0], [1.0], [a] * 7 + [None, a], "NULL")
+    refused("bn_finalize", [8, 4, 3], [], [a] * 6, "stage")
+    refused("bn_finalize", [0, 4, 1], [], [a] * 6, "M < 1")
+    refused("bn_finalize", [8, 4, 1], [], [a, a, a, a, None, a], "running")
+    refused("bn_finalize_shifted", [8, 4], [1.0], [a + 4] + [a] * 8, "8-byte")
+    refused("bn_finalize_shifted", [8, 4], [1.0], [a] * 6 + [None, a, a], "gamma and beta")
+    refused("act_sums_finalize", [0], [1.0], [a] * 5, "C < 1")
+    refused("act_table", [4], [], [a, None, a, a, a], "all set or all NULL")
+    refused("thin_dgrad", [8, 8, 5, 8, 8, 8, 0, 0], [1.0], [a, a, None, a, None, None, None, None, None], "K must be")
+    refused("thin_dgrad", [8, 8, 0, 8, 8, 8, 0, 0], [1.0], [a, a, None, a, None, None, None, None, None], "K must be")
+    refused("thin_dgrad", [8, 8, 3, 2, 8, 8, 0, 0], [1.0], [a, a, None, a, None, None, None, None, None], "leading dimension")
+    refused("thin_dgrad", [8, 2048, 3, 4, 2048, 2048, 0, 0], [1.0], [a, a, None, a, None, None, None, None, None], "N outside")
+    refused("thin_dgrad", [8, 6, 3, 4, 8, 8, 0, 0], [1.0], [a, a, None, a, None, None, None, None, None], "thin_dgrad_ok")      # N % 4
+    refused("thin_dgrad", [8, 8, 3, 4, 8, 9, 0, 0], [1.0], [a, a, None, a, None, None, None, None, None], "thin_dgrad_ok")      # ldc % 4
+    refused("thin_dgrad", [8, 8, 3, 4, 8, 8, 0, 0], [1.0], [a, a, None, a + 4, None, None, None, None, None], "thin_dgrad_ok")  # C off 16 bytes
+    refused("thin_dgrad", [8, 8, 3, 4, 8, 8, 0, 8], [1.0], [a, a, None, a, a, None, None, None, a], "thin_dgrad_ok")            # epilogue without table
+    refused("thin_dgrad", [8, 8, 3, 4, 8, 8, 0, 8], [1.0], [a, a, a, a, None, None, None, None, None], "W3 needs")
+    refused("thin_dgrad", [8, 8, 3, 4, 8, 8, 0, 0], [1.0], [a, a, None, a, None, a, None, None, None], "without ez")
+    po = lambda **kw: [kw.get(k) for k in ("head", "adj", "sv_raw", "cls", "rho", "col", "sv", "adjust_col", "d_rho", "d_col", "d_sv", "d_head", "d_adj", "d_cls", "d_sv_raw")]
+    refused("point_out_fwd", [8, 0, 4], [], po(head=a, rho=a), "n_samples")
+    refused("point_out_fwd", [8, 2, 9], [], po(head=a, adj=a, cls=a, col=a), "n_classes")
+    refused("point_out_fwd", [8, 2, 0], [], po(head=a, adj=a, cls=a, col=a), "n_classes")
+    refused("point_out_fwd", [8, 2, 4], [], po(rho=a), "need head")
+    refused("point_out_fwd", [8, 2, 4], [], po(head=a), "no output")
+    refused("point_out_bwd", [8, 2, 9], [], po(head=a, adj=a, cls=a, d_head=a), "n_classes")
+    refused("point_out_bwd", [8, 2, 4], [], po(head=a, adj=a, d_head=a), "d_head needs")
+    refused("point_out_bwd", [8, 2, 4], [], po(head=a, adj=a, cls=a, d_cls=a), "need d_head")
+    refused("point_out_bwd", [8, 2, 4], [], po(sv=a, d_sv_raw=a), "d_sv_raw needs")
+    refused("pe_points", [8, 2, 0], [], [None, a, a, None, a, None, None], "rays form")
+    refused("pe_points", [7, 2, 0], [], [None, a, a, a, a, None, None], "rays form")
+    refused("pe_points", [8, 2, 63], [], [a, None, None, None, a, None, a], "ld2")
+    refused("pe_points", [8, 2, 0], [], [a, None, None, None, None, None, None], "pe is NULL")
+    refused("pe_small", [8, 2, 3, 4, 28], [], [a, a], "strides")
+    refused("pe_small", [8, 3, 3, 4, 26], [], [a, a], "strides")
+    refused("softmax", [8, 0], [], [a, a], "C < 1")
+    refused("softmax_bwd", [8, 4], [], [a, a, None], "NULL")
+    refused("sigmoid", [8], [], [None, a], "NULL")
+    refused("colsum", [8, 4, 3], [1.0], [a, a], "ld < C")
+    refused("copy_cols", [8, 4, 4, 3, 0], [], [a, a], "leading dimension")
+    refused("bcast_rows", [8, 2, 4, 5, 2], [], [a, a], "col0 + C")
+    refused("reduce_rows", [8, 0, 4, 6, 2], [], [a, a], "n_samples")
+    refused("fill_zero", [8], [], [None], "NULL")
+    refused("copy_bytes", [8], [], [a, None], "NULL")
+    refused("colpass_rows_per_block", [8, 6], [], [], "multiple of 4")
+    ops = {"pe_points", "pe_small", "colreduce", "bn_bwd2", "bn_finalize", "bn_finalize_shifted", "act_sums_finalize", "act_table", "sin_fwd", "thin_dgrad",
+           "point_out_fwd", "point_out_bwd", "softmax", "softmax_bwd", "sigmoid", "colsum", "copy_cols", "bcast_rows", "reduce_rows", "fill_zero", "copy_bytes"}
+    assert ops <= set(bad)
+    # what needs no launch answers without a GPU: the launchers' own block sizes
+    assert _tk_call(lib, "colpass_rows_per_block", [1221, 64], [], []) == 32
+    assert _tk_call(lib, "colpass_rows_per_block", [1 << 20, 64], [], []) == 512
+    assert _tk_call(lib, "thin_dgrad_rows_per_block", [100, 4], [], []) == 256
