@@ -163,12 +163,6 @@ int sun_walk_composite_lds_bytes(int n_samples, int n_suns);
 hipError_t launch_sun_walk_composite(const SunWalkCompArgs& a, hipStream_t st);
 // workgroup tiles of a fused field launch: `rays` rays per tile in VARIANT 3 (ray visibility), `pts` points per tile otherwise
 __host__ __device__ inline int64_t field_tiles(int64_t n, int variant, int pts, int rays) { return variant == 3 ? (n + rays - 1) / rays : (n + pts - 1) / pts; }
-// persistent launch of a fused kernel: min(n_tiles, n_cu) workgroups (at least one) of `block` threads with `lds_bytes` of dynamic LDS (kernels.hip)
-hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st);
-hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st);
-hipError_t launch_fused(void (*kernel)(RaySurfaceArgs), int64_t n_tiles, int block, int lds_bytes, const RaySurfaceArgs& a, int n_cu, hipStream_t st);
-hipError_t launch_fused(void (*kernel)(ShadowWalkArgs), int64_t n_tiles, int block, int lds_bytes, const ShadowWalkArgs& a, int n_cu, hipStream_t st);
-hipError_t launch_fused(void (*kernel)(FrameWalkArgs), int64_t n_tiles, int block, int lds_bytes, const FrameWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp(int prog, int W, int variant, bool fast, const MlpArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_ray_surface_ks(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st);

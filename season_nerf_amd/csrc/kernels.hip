@@ -104,29 +104,64 @@ __device__ __forceinline__ void run_layer(Ring& rg, const uint8_t* stream, uint3
     }
 }
 
+// ---- What the five field kernels of this file share, written once.  Macros, not functions, for the reason RING_PROLOGUE is one: their
+// expansion is what each kernel held as a copy, and the kernels are built around the register allocator (a function form changed their instructions).
+//
+// Kernel prologue.  Declares `lds` (the ring), `bias_lds`, `lane`, `wave`, `h` and the ring `rg`; copies the bias table of `A` to LDS, runs the
+// statements given after `A` (a kernel's own declarations and LDS staging, which need `lds` and must be in front of the barrier), issues the ring's
+// prologue and ends in the barrier that makes the LDS writes visible (it drains the prologue DMAs once; harmless).
+#define FIELD_PROLOGUE(A, ...)                                                                                                                      \
+    extern __shared__ __attribute__((aligned(16))) char smem[];                                                                                     \
+    lds_char* lds = (lds_char*)smem;                                                                                                                \
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);                               \
+    const int lane = threadIdx.x & 63;                                                                                                              \
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                                              \
+    const int h = lane >> 5;                                                                                                                        \
+    for (int i = threadIdx.x; i < (A).bias_floats; i += 256) bias_lds[i] = (A).bias[i];                                                             \
+    __VA_ARGS__                                                                                                                                     \
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)                                                                                                   \
+    __syncthreads();
 
+// The field network's layer lists.  LAYER(L, blocks, k-steps of IN0, k-steps of IN1, sine?, IN0, IN1, OUT, RAW) is the using kernel's: mlp_kernel's own,
+// which selects the FAST product, or FIELD_LAYER below.  W, W2 = W / 2, KW = W / 16 and KW2 = W2 / 16 are the kernel's too.  The weight stream cannot
+// branch: a kernel runs these lists in the order of its stream (program.h), and a change to a list is a change to every kernel and every stream.
+//   trunk (G_NeRF.py:80-91) and sigma / colour head (G_NeRF.py:93-98): pe -> x1f and raw (regs 0..2 colour, 3 density, lane-half 0); hA, hB are scratch
+#define FIELD_TRUNK(LAYER, pe, hA, hB, x1f, raw)                                                                                                    \
+    LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);                                                                              \
+    LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);                                                                                    \
+    LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);                                                                                    \
+    LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);                                                                                    \
+    LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);                                                                                  \
+    LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);                                                                                    \
+    LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);                                                                                    \
+    LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);                                                                                    \
+    LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);                                                                                  \
+    LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw)
+//   solar visibility branch (G_NeRF.py:100-108): x1f, ps = PE(sun) -> raw[0]; sA, sB are scratch
+#define FIELD_SOLAR(LAYER, x1f, ps, sA, sB, raw)                                                                                                    \
+    LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);                                                                                \
+    LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);                                                                                   \
+    LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);                                                                                   \
+    LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw)
+//   seasonal colour-adjust branch (T_NeRF_net_v2.py:83-87): x1f -> raw[0 .. 3 C_MAX); hA, hB are scratch
+#define FIELD_ADJUST(LAYER, x1f, hA, hB, raw)                                                                                                       \
+    LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr);                                                                                   \
+    LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);                                                                                     \
+    LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);                                                                                     \
+    LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw)
+// the plain LAYER of the field program: the 3-term product, activations with their low parts
+#define FIELD_LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                                                       \
+    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, kMaxClasses, L), IN0, IN1, OUT, RAW, wave, lane)
 
 // =====================================================================================================
 // FAST: every layer but the first multiplies the bf16-rounded operands once (first layer / positional encoding keep the
 // 3-term product); activations keep no low part.
 template <int PROG, int W, int VARIANT, bool FAST = false>
 __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
+    FIELD_PROLOGUE(A)
     const int C = A.n_classes;
-
-    // bias table -> LDS (once per workgroup)
-    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
-
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();   // bias table visible (drains the prologue DMAs once; harmless)
 
     // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 4 rays (one per wave), walked in passes of 32 samples
     const int64_t n_tiles = field_tiles(A.n, VARIANT, TILE_PTS, 4);
@@ -149,46 +184,26 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
             make_pe_pos(x0, x1, x2, h, pe);
 
             constexpr int KW = W / 16, KW2 = W2 / 16;
-            Frag hA[KW], hB[KW];
+            Frag hA[KW], hB[KW], x1f[KW2];
             f32x16 raw;
 #define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
     run_layer<NBv, K0, K1, SINv, (FAST && L != F_FC1) ? 1 : 3, !FAST>(rg, A.stream, A.stream_bytes, lds,                   \
                                  bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
-            // trunk (G_NeRF.py:80-91)
-            LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
-            LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-            LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-            LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-            LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
-            LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-            LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-            LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-            Frag x1f[KW2];
-            LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
-            // sigma / colour head (G_NeRF.py:93-98): regs 0..2 colour, 3 density (lane-half 0)
-            LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+            FIELD_TRUNK(LAYER, pe, hA, hB, x1f, raw);
             const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
             float sv_raw = 0.f;
             float adj[3 * C_MAX];
 #pragma unroll
             for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = 0.f;
             if constexpr (VARIANT <= 1) {
-                // solar visibility branch (G_NeRF.py:100-108)
                 Frag ps[PESUN_KS];
                 make_pe_sun(s0, s1, s2, h, ps);
                 Frag sA[KW2], sB[KW2];
-                LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
-                LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
-                LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
-                LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
+                FIELD_SOLAR(LAYER, x1f, ps, sA, sB, raw);
                 sv_raw = raw[0];
             }
             if constexpr (VARIANT == 0) {
-                // seasonal colour-adjust branch (T_NeRF_net_v2.py:83-87)
-                LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr);
-                LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-                LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-                LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw);
+                FIELD_ADJUST(LAYER, x1f, hA, hB, raw);
 #pragma unroll
                 for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
             }
@@ -246,11 +261,11 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpArgs A) {
 }
 
 // =====================================================================================================
-// Sun walk: the VARIANT 0 layer walk of mlp_kernel with fc_solar_1..4 (G_NeRF.py:100-108) run for n_suns sun directions.  The trunk, the density /
-// colour head and the colour-adjust branch do not depend on the sun: one pass feeds every sun direction of a season / shadow study of one view
-// (mg_Season_Eval.py:74-98).  The weights come from the walk stream (program.h sun_walk_*): the ring cannot branch, so the solar layers' chunks
-// are repeated in the stream.  x1f stays live as long as in VARIANT 0 (through the solar layers, last read by F_A1).  The sun directions are staged
-// in LDS behind the vote words: a global load inside the chain would make hipcc drain the LDS-DMA pipeline with vmcnt(0) (field_tile_inputs).
+// Sun walk: the VARIANT 0 layer walk of mlp_kernel (the lists FIELD_TRUNK, FIELD_SOLAR, FIELD_ADJUST) with FIELD_SOLAR, fc_solar_1..4 (G_NeRF.py:100-108), run
+// for n_suns sun directions.  The trunk, the density / colour head and the colour-adjust branch do not depend on the sun: one pass feeds every sun direction of
+// a season / shadow study of one view (mg_Season_Eval.py:74-98).  The weights come from the walk stream (program.h sun_walk_*): the ring cannot branch, so the
+// solar layers' chunks are repeated in the stream.  x1f stays live as long as in VARIANT 0 (through the solar layers, last read by F_A1).  The sun directions
+// are staged in LDS behind the vote words: a global load inside the chain would make hipcc drain the LDS-DMA pipeline with vmcnt(0) (field_tile_inputs).
 // Everything but solar_vis is stored once per point; solar_vis of sun j goes to out.solar_vis[j * n + point].
 __host__ __device__ constexpr int sun_walk_lds_extra() { return kMaxWalkSuns * 3 * 4; }
 
@@ -262,25 +277,14 @@ __device__ __attribute__((noinline)) void store_softplus(float* p, float x) { *p
 
 template <int W>
 __global__ __launch_bounds__(256, 1) void sun_walk_kernel(const SunWalkArgs SA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = SA.m;
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-    __attribute__((address_space(3))) float* sun_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + A.bias_floats * 4 + kVoteBytes);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
     const int C = A.n_classes;
     const int n_suns = SA.n_suns;
-
-    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
-    for (int i = threadIdx.x; i < 3 * n_suns; i += 256) sun_lds[i] = A.sun[i];
-
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    FIELD_PROLOGUE(A,
+        __attribute__((address_space(3))) float* sun_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + A.bias_floats * 4 + kVoteBytes);
+        for (int i = threadIdx.x; i < 3 * n_suns; i += 256) sun_lds[i] = A.sun[i];)
 
     const int64_t n_tiles = field_tiles(A.n, 0, TILE_PTS, 4);
     snerf_field_out_dev once = A.out;      // what is stored once per point (the density through store_softplus)
@@ -298,41 +302,22 @@ __global__ __launch_bounds__(256, 1) void sun_walk_kernel(const SunWalkArgs SA) 
         make_pe_pos(x0, x1, x2, h, pe);
 
         constexpr int KW = W / 16, KW2 = W2 / 16;
-        Frag hA[KW], hB[KW];
+        Frag hA[KW], hB[KW], x1f[KW2];
         f32x16 raw;
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
-    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
-        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        Frag x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+        FIELD_TRUNK(FIELD_LAYER, pe, hA, hB, x1f, raw);
         const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         for (int j = 0; j < n_suns; ++j) {
             const float s0 = sun_lds[3 * j], s1 = sun_lds[3 * j + 1], s2 = sun_lds[3 * j + 2];      // wave-uniform
             Frag ps[PESUN_KS];
             make_pe_sun(s0, s1, s2, h, ps);
             Frag sA[KW2], sB[KW2];
-            LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
-            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
-            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
-            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
+            FIELD_SOLAR(FIELD_LAYER, x1f, ps, sA, sB, raw);
             if (h == 0 && valid && A.out.solar_vis) A.out.solar_vis[(int64_t)j * A.n + n] = sigmoid_f(raw[0]);
         }
-        LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr);
-        LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw);
+        FIELD_ADJUST(FIELD_LAYER, x1f, hA, hB, raw);
         float adj[3 * C_MAX];
 #pragma unroll
         for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
-#undef LAYER
         if (h == 0 && valid) {
             if (A.out.rho) store_softplus(A.out.rho + n, rho_raw);
             store_field_outputs<0>(once, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, 0.f, adj, pcls);
@@ -862,31 +847,18 @@ hipError_t launch_ray_grid(const RayGridArgs& a, hipStream_t st) {
 }
 
 // =====================================================================================================
-// launchers
+// launchers (launch_fused: mlp_device.h)
+// one of the four walks at W = 64 / 256: the tile rule of `variant` (field_tiles), `lds_extra` bytes of staged inputs behind mlp_lds_bytes
 template <class Args>
-static hipError_t launch_fused_t(void (*kernel)(Args), int64_t n_tiles, int block, int lds_bytes, const Args& a, int n_cu, hipStream_t st) {
-    int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
-    if (grid < 1) grid = 1;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, st, a);
-    return hipGetLastError();
-}
-hipError_t launch_fused(void (*kernel)(MlpArgs), int64_t n_tiles, int block, int lds_bytes, const MlpArgs& a, int n_cu, hipStream_t st) {
-    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
-}
-hipError_t launch_fused(void (*kernel)(SunWalkArgs), int64_t n_tiles, int block, int lds_bytes, const SunWalkArgs& a, int n_cu, hipStream_t st) {
-    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
+static hipError_t launch_walk(int W, void (*k64)(Args), void (*k256)(Args), int variant, int lds_extra, const Args& a, int n_cu, hipStream_t st) {
+    if (W != 64 && W != 256) return hipErrorInvalidValue;
+    return launch_fused(W == 64 ? k64 : k256, field_tiles(a.m.n, variant, TILE_PTS, 4), 256, mlp_lds_bytes(a.m.bias_floats) + lds_extra, a, n_cu, st);
 }
 
 hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st) {
     if (a.n_suns < 1 || a.n_suns > kMaxWalkSuns) return hipErrorInvalidValue;      // the kernels stage 3 * kMaxWalkSuns floats in LDS
     if (W == 512) return launch_sun_walk_ks(W, a, n_cu, st);
-    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats) + sun_walk_lds_extra();
-    const int64_t tiles = field_tiles(a.m.n, 0, TILE_PTS, 4);
-    if (W == 64) return launch_fused(sun_walk_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
-    if (W == 256) return launch_fused(sun_walk_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
-    return hipErrorInvalidValue;
+    return launch_walk(W, sun_walk_kernel<64>, sun_walk_kernel<256>, 0, sun_walk_lds_extra(), a, n_cu, st);
 }
 
 int mlp_lds_bytes(int bias_floats) { return RING_BYTES + bias_floats * 4 + kVoteBytes; }
@@ -931,26 +903,14 @@ hipError_t launch_composite(const CompArgs& a, hipStream_t st) {
 
 
 // =====================================================================================================
-// Ray surface: the VARIANT 3 walk of mlp_kernel (a wave owns a ray, 32 samples per pass, the density-only stream) with the compositing scan in the pass
-// end (mlp_device.h RaySurf): four floats out per ray, from which the height map (Quick_Run.py:37-40), eval_HM's columns (Eval_funcs.py:299-319) and the
+// Ray surface: the VARIANT 3 walk of mlp_kernel (a wave owns a ray, 32 samples per pass, the density-only stream: FIELD_TRUNK alone) with the compositing
+// scan in the pass end (mlp_device.h RaySurf): four floats out per ray, from which the height map (Quick_Run.py:37-40), eval_HM's columns (Eval_funcs.py:299-319) and the
 // surface location / distance (mg_run_NeRF.py:188-189) follow.  No per-sample array, no compositing launch.
 template <int W>
 __global__ __launch_bounds__(256, 1) void ray_surface_kernel(const RaySurfaceArgs RA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = RA.m;
-    constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
-
-    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
-
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    FIELD_PROLOGUE(A)
 
     const int64_t n_tiles = field_tiles(A.n, 3, TILE_PTS, 4);      // a tile is a group of 4 rays, one per wave
     const int passes = (A.n_samples + 31) / 32;
@@ -963,62 +923,29 @@ __global__ __launch_bounds__(256, 1) void ray_surface_kernel(const RaySurfaceArg
         make_pe_pos(x0, x1, x2, h, pe);
 
         constexpr int KW = W / 16, KW2 = W2 / 16;
-        Frag hA[KW], hB[KW];
+        Frag hA[KW], hB[KW], x1f[KW2];
         f32x16 raw;
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
-    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
-        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        Frag x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
-#undef LAYER
+        FIELD_TRUNK(FIELD_LAYER, pe, hA, hB, x1f, raw);
         const float rho_raw = raw[3];       // lane-half 0 holds the density row
         RAYSURF_PASS_END(rs, A, RA.out, tile, pass, passes, 4, wave, wave, 4, true, lane, rho_raw, bias_lds + A.bias_floats);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
 }
 
-hipError_t launch_fused(void (*kernel)(RaySurfaceArgs), int64_t n_tiles, int block, int lds_bytes, const RaySurfaceArgs& a, int n_cu, hipStream_t st) {
-    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
-}
-
 hipError_t launch_ray_surface(int W, const RaySurfaceArgs& a, int n_cu, hipStream_t st) {
     if (W == 512) return launch_ray_surface_ks(W, a, n_cu, st);
-    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats);
-    const int64_t tiles = field_tiles(a.m.n, 3, TILE_PTS, 4);
-    if (W == 64) return launch_fused(ray_surface_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
-    if (W == 256) return launch_fused(ray_surface_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
-    return hipErrorInvalidValue;
+    return launch_walk(W, ray_surface_kernel<64>, ray_surface_kernel<256>, 3, 0, a, n_cu, st);
 }
 
 // =====================================================================================================
-// Shadow walk: the ray surface's walk (a wave owns a ray, 32 samples per pass from t = 0 downwards) through the layers of VARIANT 1 - trunk, density head,
-// fc_solar_1..4 with the ray's own sun direction - and the reference's shadow test in the pass end (mlp_device.h RayShadow; mg_Shadow_Eval.py:72-104,
-// 134-163): eight sums out per ray, no per-sample array, no transmittance launch.  Every pass of every ray runs.
+// Shadow walk: the ray surface's walk (a wave owns a ray, 32 samples per pass from t = 0 downwards) through the layers of VARIANT 1 - FIELD_TRUNK
+// (trunk, density head), FIELD_SOLAR (fc_solar_1..4) with the ray's own sun direction - and the reference's shadow test in the pass end (mlp_device.h RayShadow;
+// mg_Shadow_Eval.py:72-104, 134-163): eight sums out per ray, no per-sample array, no transmittance launch.  Every pass of every ray runs.
 template <int W>
 __global__ __launch_bounds__(256, 1) void shadow_walk_kernel(const ShadowWalkArgs SA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = SA.m;
-    constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
-
-    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
-
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    FIELD_PROLOGUE(A)
 
     const int64_t n_tiles = field_tiles(A.n, 3, TILE_PTS, 4);      // a tile is a group of 4 rays, one per wave
     const int passes = (A.n_samples + 31) / 32;
@@ -1031,73 +958,39 @@ __global__ __launch_bounds__(256, 1) void shadow_walk_kernel(const ShadowWalkArg
         make_pe_pos(x0, x1, x2, h, pe);
 
         constexpr int KW = W / 16, KW2 = W2 / 16;
-        Frag hA[KW], hB[KW];
+        Frag hA[KW], hB[KW], x1f[KW2];
         f32x16 raw;
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
-    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
-        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        Frag x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+        FIELD_TRUNK(FIELD_LAYER, pe, hA, hB, x1f, raw);
         const float rho_raw = raw[3];       // lane-half 0 holds the density row
         Frag ps[PESUN_KS];
         make_pe_sun(s0, s1, s2, h, ps);
         Frag sA[KW2], sB[KW2];
-        LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
-        LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
-        LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
-        LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
-#undef LAYER
+        FIELD_SOLAR(FIELD_LAYER, x1f, ps, sA, sB, raw);
         const float sv_raw = raw[0];
         RAYSHADOW_PASS_END(rs, A, SA.out, tile, pass, passes, 4, wave, true, lane, rho_raw, sv_raw);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
 }
 
-hipError_t launch_fused(void (*kernel)(ShadowWalkArgs), int64_t n_tiles, int block, int lds_bytes, const ShadowWalkArgs& a, int n_cu, hipStream_t st) {
-    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
-}
-
 hipError_t launch_shadow_walk(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st) {
     if (W == 512) return launch_shadow_walk_ks(W, a, n_cu, st);
-    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats);
-    const int64_t tiles = field_tiles(a.m.n, 3, TILE_PTS, 4);
-    if (W == 64) return launch_fused(shadow_walk_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
-    if (W == 256) return launch_fused(shadow_walk_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
-    return hipErrorInvalidValue;
+    return launch_walk(W, shadow_walk_kernel<64>, shadow_walk_kernel<256>, 3, 0, a, n_cu, st);
 }
 
 // =====================================================================================================
-// Film frame: the ray surface's walk (a wave owns a ray, 32 samples per pass from t = 0 downwards, the early-out vote) through the layer list of
-// mlp_kernel<PROG_FIELD, W, 0> on its unchanged stream and bias table, and the shading and compositing of the reference's film frames in the pass end
-// (mlp_device.h RayFrame; mg_movie_maker.py:108-187): sixteen floats out per ray, up to kMaxFrameTimes seasons from one field pass, no per-sample array.
-// The launch's sun direction, sky colour and class vectors are staged in LDS behind the vote words (sun_walk_kernel does the same with its suns).
+// Film frame: the ray surface's walk (a wave owns a ray, 32 samples per pass from t = 0 downwards, the early-out vote) through the layer lists of
+// mlp_kernel<PROG_FIELD, W, 0> (FIELD_TRUNK, FIELD_SOLAR, FIELD_ADJUST) on its unchanged stream and bias table, and the shading and compositing of the
+// reference's film frames in the pass end (mlp_device.h RayFrame; mg_movie_maker.py:108-187): sixteen floats out per ray, up to kMaxFrameTimes seasons from one
+// field pass, no per-sample array.  The launch's sun direction, sky colour and class vectors are staged in LDS behind the vote words (sun_walk_kernel does the
+// same with its suns).
 template <int W>
 __global__ __launch_bounds__(256, 1) void frame_walk_kernel(const FrameWalkArgs FA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = FA.m;
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-    __attribute__((address_space(3))) float* fin = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + A.bias_floats * 4 + kVoteBytes);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
-
-    for (int i = threadIdx.x; i < A.bias_floats; i += 256) bias_lds[i] = A.bias[i];
-    frame_stage_inputs(FA, fin);
-
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    FIELD_PROLOGUE(A,
+        __attribute__((address_space(3))) float* fin = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + A.bias_floats * 4 + kVoteBytes);
+        frame_stage_inputs(FA, fin);)
 
     const int64_t n_tiles = field_tiles(A.n, 3, TILE_PTS, 4);      // a tile is a group of 4 rays, one per wave
     const int passes = (A.n_samples + 31) / 32;
@@ -1110,21 +1003,9 @@ __global__ __launch_bounds__(256, 1) void frame_walk_kernel(const FrameWalkArgs 
         make_pe_pos(x0, x1, x2, h, pe);
 
         constexpr int KW = W / 16, KW2 = W2 / 16;
-        Frag hA[KW], hB[KW];
+        Frag hA[KW], hB[KW], x1f[KW2];
         f32x16 raw;
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW)                                                              \
-    run_layer<NBv, K0, K1, SINv>(rg, A.stream, A.stream_bytes, lds, bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
-        LAYER(F_FC1, W / 32, PEPOS_KS, 0, true, pe, nullptr, hA, nullptr);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC5, W / 32, KW, PEPOS_KS, true, hB, pe, hA, nullptr);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        Frag x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr);
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw);
+        FIELD_TRUNK(FIELD_LAYER, pe, hA, hB, x1f, raw);
         const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         float sv_raw;
         {
@@ -1132,37 +1013,22 @@ __global__ __launch_bounds__(256, 1) void frame_walk_kernel(const FrameWalkArgs 
             Frag ps[PESUN_KS];
             make_pe_sun(s0, s1, s2, h, ps);
             Frag sA[KW2], sB[KW2];
-            LAYER(F_S1, W2 / 32, KW2, PESUN_KS, true, x1f, ps, sA, nullptr);
-            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr);
-            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr);
-            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw);
+            FIELD_SOLAR(FIELD_LAYER, x1f, ps, sA, sB, raw);
             sv_raw = raw[0];
         }
-        LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr);
-        LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr);
-        LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr);
-        LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw);
+        FIELD_ADJUST(FIELD_LAYER, x1f, hA, hB, raw);
         float adj[3 * C_MAX];
 #pragma unroll
         for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
-#undef LAYER
         RAYFRAME_PASS_END(rf, A, FA, fin, tile, pass, passes, 4, wave, wave, 4, true, lane, col_r, col_g, col_b, rho_raw, sv_raw, adj, bias_lds + A.bias_floats);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
 }
 
-hipError_t launch_fused(void (*kernel)(FrameWalkArgs), int64_t n_tiles, int block, int lds_bytes, const FrameWalkArgs& a, int n_cu, hipStream_t st) {
-    return launch_fused_t(kernel, n_tiles, block, lds_bytes, a, n_cu, st);
-}
-
 hipError_t launch_frame_walk(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st) {
     if (a.n_times < 1 || a.n_times > kMaxFrameTimes || a.m.n_classes > kMaxClasses) return hipErrorInvalidValue;      // the kernels stage kFrameLdsFloats floats in LDS
     if (W == 512) return launch_frame_walk_ks(W, a, n_cu, st);
-    const int lds_bytes = mlp_lds_bytes(a.m.bias_floats) + kFrameLdsFloats * 4;
-    const int64_t tiles = field_tiles(a.m.n, 3, TILE_PTS, 4);
-    if (W == 64) return launch_fused(frame_walk_kernel<64>, tiles, 256, lds_bytes, a, n_cu, st);
-    if (W == 256) return launch_fused(frame_walk_kernel<256>, tiles, 256, lds_bytes, a, n_cu, st);
-    return hipErrorInvalidValue;
+    return launch_walk(W, frame_walk_kernel<64>, frame_walk_kernel<256>, 3, kFrameLdsFloats * 4, a, n_cu, st);
 }
 
 }  // namespace snerf

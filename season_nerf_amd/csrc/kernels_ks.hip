@@ -168,32 +168,32 @@ __device__ __forceinline__ void run_layer_ks(Ring& rg, Pend& pd, const uint8_t* 
 #if defined(SNERF_ABLATE) && (ABL & 2)        // timing-only: the A fragments stay in registers, no LDS reads
 #define KS_FRAG_READ(q) asm volatile("" : "+v"(fh[(q) % PF]), "+v"(fl[(q) % PF]));
 #else
-#define KS_FRAG_READ(q)                                                                                                 \
-    {                                                                                                                   \
-        lds_char* ap = cx.lds + rg.cur + cx.par_off + (((q) + PF) % KS_PAR_PAIRS) * kPairBytes + lane * 16;             \
-        fh[(q) % PF] = *(lds_cu32x4*)ap;                                                                                \
-        fl[(q) % PF] = *(lds_cu32x4*)(ap + kFragBytes);                                                                 \
+#define KS_FRAG_READ(q)                                                                                                                             \
+    {                                                                                                                                               \
+        lds_char* ap = cx.lds + rg.cur + cx.par_off + (((q) + PF) % KS_PAR_PAIRS) * kPairBytes + lane * 16;                                         \
+        fh[(q) % PF] = *(lds_cu32x4*)ap;                                                                                                            \
+        fl[(q) % PF] = *(lds_cu32x4*)(ap + kFragBytes);                                                                                             \
     }
 #endif
-#define KS_STEP(q, ACC, BFRAG)                                                                                          \
-    {                                                                                                                   \
-        const u32x4 a_hi = fh[(q) % PF], a_lo = fl[(q) % PF];                                                           \
-        ks_ring<NP>(rg, pd, stream, stream_bytes, cx.lds, wave, lane, (q));                                             \
-        if ((q) + PF < NP) KS_FRAG_READ(q)                                                                              \
-        ACC = mfma3(a_hi, a_lo, BFRAG, ACC);                                                                            \
+#define KS_STEP(q, ACC, BFRAG)                                                                                                                      \
+    {                                                                                                                                               \
+        const u32x4 a_hi = fh[(q) % PF], a_lo = fl[(q) % PF];                                                                                       \
+        ks_ring<NP>(rg, pd, stream, stream_bytes, cx.lds, wave, lane, (q));                                                                         \
+        if ((q) + PF < NP) KS_FRAG_READ(q)                                                                                                          \
+        ACC = mfma3(a_hi, a_lo, BFRAG, ACC);                                                                                                        \
     }
 #ifdef KS_NO_SCHED
 #define KS_SCHED() __builtin_amdgcn_sched_barrier(0);
 #else
-#define KS_SCHED()                                                                                                      \
-    {                                                                                                                   \
-        _Pragma("unroll") for (int m = 0; m < 3; ++m) {                                                                 \
-            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);                                                        \
-            __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 1, 0);                                                      \
-            __builtin_amdgcn_sched_group_barrier(SG_TRANS, 1, 0);                                                       \
-            __builtin_amdgcn_sched_group_barrier(SG_VALU, 3, 0);                                                        \
-        }                                                                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                              \
+#define KS_SCHED()                                                                                                                                  \
+    {                                                                                                                                               \
+        _Pragma("unroll") for (int m = 0; m < 3; ++m) {                                                                                             \
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);                                                                                    \
+            __builtin_amdgcn_sched_group_barrier(SG_DSREAD, 1, 0);                                                                                  \
+            __builtin_amdgcn_sched_group_barrier(SG_TRANS, 1, 0);                                                                                   \
+            __builtin_amdgcn_sched_group_barrier(SG_VALU, 3, 0);                                                                                    \
+        }                                                                                                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                                                                          \
     }
 #endif
 #pragma unroll
@@ -297,37 +297,87 @@ __device__ __forceinline__ f32x16 run_head_ks(Ring& rg, Pend& pd, const uint8_t*
 #undef KS_SCHED
 #undef KS_FRAG_READ
 
+// ---- What the kernels of this file share, written once.  Macros, not functions, for the reason RING_PROLOGUE is one: their expansion is what
+// each kernel held as a copy, and a function form changed the kernels' instructions.
+//
+// Kernel prologue.  Declares `lds` (the ring), `bias_lds`, `lane`, `wave`, `pair` / `par` (the wave pair and this wave's parity in it), `h`, `zero_bias` (the
+// 32 zero rows behind the bias table: the bias of parity 1's half of a raw head), the wave's context `cx` with its exchange buffers, `vote_lds` (the words of
+// the early-out vote, ks_lds_bytes), the pending chunk `pd` and the ring `rg`.  Copies the bias table of `A` and the zero rows to LDS, runs the statements
+// given after `A` (a kernel's own declarations and LDS staging, which need `lds` and must be in front of the barrier), issues the ring's prologue and ends
+// in the barrier that makes the LDS writes visible.
+#define KS_PROLOGUE(A, ...)                                                                                                                         \
+    extern __shared__ __attribute__((aligned(16))) char smem[];                                                                                     \
+    lds_char* lds = (lds_char*)smem;                                                                                                                \
+    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);                               \
+    const int lane = threadIdx.x & 63;                                                                                                              \
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                                              \
+    const int pair = wave >> 1, par = wave & 1;                                                                                                     \
+    const int h = lane >> 5;                                                                                                                        \
+    for (int i = threadIdx.x; i < (A).bias_floats + 32; i += 256) bias_lds[i] = i < (A).bias_floats ? (A).bias[i] : 0.f;                            \
+    __VA_ARGS__                                                                                                                                     \
+    lds_cfloat* zero_bias = bias_lds + (A).bias_floats;                                                                                             \
+    KsCtx cx;                                                                                                                                       \
+    cx.lds = lds;                                                                                                                                   \
+    cx.par_off = par * KS_PAR_BYTES;                                                                                                                \
+    {                                                                                                                                               \
+        lds_char* xb = lds + RING_BYTES + ((A).bias_floats + 32) * 4;                                                                               \
+        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;                                                                                              \
+        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;                                                                                        \
+    }                                                                                                                                               \
+    __attribute__((address_space(3))) float* vote_lds =                                                                                             \
+        (__attribute__((address_space(3))) float*)(lds + RING_BYTES + ((A).bias_floats + 32) * 4 + 4 * KS_XBUF_BYTES);                              \
+    Pend pd;                                                                                                                                        \
+    pd.goff = 0;                                                                                                                                    \
+    pd.wr = 0;                                                                                                                                      \
+    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)                                                                                                   \
+    __syncthreads();
+
+// A layer / a raw head of program PROG (the kernel's: PROG_FIELD or PROG_GROUP) at width W on the names of KS_PROLOGUE.  OWNB: the bias rows of this wave's
+// own blocks of layer L (n_out = 64 NBH).
+#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG, W, kMaxClasses, L) + par * (NBH) * 32)
+#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
+#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG, W, kMaxClasses, L), IN0, wave, lane)
+
+// The field network's layer lists (kernels.hip FIELD_TRUNK / FIELD_SOLAR / FIELD_ADJUST at this width).  The kernel's: KH = W / 32 and KH2 = W2 / 32, the k-steps
+// of this wave's K-half of a W- / W/2-wide activation; NBW = W / 64 and NBW2 = W2 / 64, the own blocks of a W- / W/2-wide layer.  The static_assert ties
+// the k-step counts of the lists to the packer for every kernel that walks the trunk.
+//   trunk and sigma / colour head: pe -> x1f and raw (regs 0..2 colour, 3 density, lane-half 0); hA, hB are scratch
+#define KS_TRUNK(pe, hA, hB, x1f, raw)                                                                                                              \
+    static_assert(ks_layer_pairs(field_layer(W, kMaxClasses, F_FC1)) == NBW * PEPOS_KS && ks_layer_pairs(field_layer(W, kMaxClasses, F_FC2)) == NBW * 2 * KH && \
+                  ks_layer_pairs(field_layer(W, kMaxClasses, F_FC5)) == NBW * (2 * KH + PEPOS_KS) && ks_layer_pairs(field_layer(W, kMaxClasses, F_FC9)) == NBW2 * 2 * KH && \
+                  ks_layer_pairs(field_layer(W, kMaxClasses, F_HEAD)) == KH2 && ks_layer_pairs(field_layer(W, kMaxClasses, F_S1)) == NBW2 * (2 * KH2 + PESUN_KS) && \
+                  ks_layer_pairs(field_layer(W, kMaxClasses, F_S2)) == NBW2 * 2 * KH2 && ks_layer_pairs(field_layer(W, kMaxClasses, F_A1)) == NBW * 2 * KH2 && \
+                  ks_layer_pairs(field_layer(W, kMaxClasses, F_AC)) == KH, "kernel and packer (program.h ks_*) disagree about the stream");         \
+    LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);                                                                                                \
+    LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);                                                                                                      \
+    LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);                                                                                                      \
+    LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);                                                                                                      \
+    LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);                                                                                                    \
+    LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);                                                                                                      \
+    LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);                                                                                                      \
+    LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);                                                                                                      \
+    LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);                                                                                                    \
+    raw = HEADL(F_HEAD, KH2, x1f)
+//   solar visibility branch: x1f, ps = PE(sun) -> raw[0]; sA, sB are scratch
+#define KS_SOLAR(x1f, ps, sA, sB, raw)                                                                                                              \
+    LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);                                                                                                  \
+    LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);                                                                                                     \
+    LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);                                                                                                     \
+    raw = HEADL(F_S4, KH2, sA)
+//   seasonal colour-adjust branch: x1f -> raw[0 .. 3 C_MAX); hA, hB are scratch
+#define KS_ADJUST(x1f, hA, hB, raw)                                                                                                                 \
+    LAYER(F_A1, NBW, KH2, 0, x1f, nullptr, hA);                                                                                                     \
+    LAYER(F_A2, NBW, KH, 0, hA, nullptr, hB);                                                                                                       \
+    LAYER(F_A3, NBW, KH, 0, hB, nullptr, hA);                                                                                                       \
+    raw = HEADL(F_AC, KH, hA)
+
 template <int W, int VARIANT>
 __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = wave >> 1, par = wave & 1;
-    const int h = lane >> 5;
+    constexpr int PROG = PROG_FIELD;
     const int C = A.n_classes;
-
-    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
-    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
-    KsCtx cx;
-    cx.lds = lds;
-    cx.par_off = par * KS_PAR_BYTES;
-    {
-        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
-        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
-        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
-    }
-    __attribute__((address_space(3))) float* vote_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + (A.bias_floats + 32) * 4 + 4 * KS_XBUF_BYTES);
-
-    Pend pd;
-    pd.goff = 0;
-    pd.wr = 0;
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    KS_PROLOGUE(A)
 
     // VARIANT 3 (ray visibility, mlp_device.h RaySum): a "tile" is a group of 2 rays (one per wave pair), walked in passes of 32 samples
     const int64_t n_tiles = field_tiles(A.n, VARIANT, KS_TILE_PTS, 2);
@@ -350,27 +400,9 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
 
         constexpr int KH = W / 32, KH2 = W2 / 32;        // k-steps of this wave's K-half of a W- / W/2-wide activation
         constexpr int NBW = W / 64, NBW2 = W2 / 64;      // own blocks of a W- / W/2-wide layer
-        static_assert(ks_layer_pairs(field_layer(W, C_MAX, F_FC1)) == NBW * PEPOS_KS && ks_layer_pairs(field_layer(W, C_MAX, F_FC2)) == NBW * 2 * KH &&
-                      ks_layer_pairs(field_layer(W, C_MAX, F_FC5)) == NBW * (2 * KH + PEPOS_KS) && ks_layer_pairs(field_layer(W, C_MAX, F_FC9)) == NBW2 * 2 * KH &&
-                      ks_layer_pairs(field_layer(W, C_MAX, F_HEAD)) == KH2 && ks_layer_pairs(field_layer(W, C_MAX, F_S1)) == NBW2 * (2 * KH2 + PESUN_KS) &&
-                      ks_layer_pairs(field_layer(W, C_MAX, F_S2)) == NBW2 * 2 * KH2 && ks_layer_pairs(field_layer(W, C_MAX, F_A1)) == NBW * 2 * KH2 &&
-                      ks_layer_pairs(field_layer(W, C_MAX, F_AC)) == KH, "kernel and packer (program.h ks_*) disagree about the stream");
-        Frag hA[KH], hB[KH];
-        // bias rows of this wave's own blocks of layer L (n_out = 64 NBH)
-#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
-#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
-#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
-        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
-        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
-        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
-        Frag x1f[KH2];
-        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
-        f32x16 raw = HEADL(F_HEAD, KH2, x1f);
+        Frag hA[KH], hB[KH], x1f[KH2];
+        f32x16 raw;
+        KS_TRUNK(pe, hA, hB, x1f, raw);
         const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         float sv_raw = 0.f;
         float adj[3 * C_MAX];
@@ -380,23 +412,14 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
             Frag ps[PESUN_KS];
             make_pe_sun(s0, s1, s2, h, ps);
             Frag sA[KH2], sB[KH2];
-            LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);
-            LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);
-            LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);
-            raw = HEADL(F_S4, KH2, sA);
+            KS_SOLAR(x1f, ps, sA, sB, raw);
             sv_raw = raw[0];
         }
         if constexpr (VARIANT == 0) {
-            LAYER(F_A1, NBW, KH2, 0, x1f, nullptr, hA);
-            LAYER(F_A2, NBW, KH, 0, hA, nullptr, hB);
-            LAYER(F_A3, NBW, KH, 0, hB, nullptr, hA);
-            raw = HEADL(F_AC, KH, hA);
+            KS_ADJUST(x1f, hA, hB, raw);
 #pragma unroll
             for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
         }
-#undef LAYER
-#undef HEADL
-#undef OWNB
         if constexpr (VARIANT == 3) {      // both waves of a pair hold the same sum and vote alike; wave 0 of the pair stores
             RAYSUM_PASS_END(rs, A, tile, pass, passes, 2, pair, wave, 4, par == 0, lane, rho_raw, x0, x1, x2, vote_lds);
         } else {
@@ -407,42 +430,19 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_kernel(const MlpArgs A) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
 }
 
-// Sun walk at this width: the VARIANT 0 walk of mlp_ks_kernel with fc_solar_1..4 run for n_suns sun directions from the walk stream (kernels.hip
-// sun_walk_kernel; the new layer adjacency is argued in the head comment).  The sun directions wait in LDS behind the vote words.
+// Sun walk at this width: the VARIANT 0 walk of mlp_ks_kernel (KS_TRUNK, KS_SOLAR, KS_ADJUST) with KS_SOLAR, fc_solar_1..4, run for n_suns sun
+// directions from the walk stream (kernels.hip sun_walk_kernel; the new layer adjacency is argued in the head comment).  The sun directions wait in LDS behind the vote words.
 template <int W>
 __global__ __launch_bounds__(256, 1) void sun_walk_ks_kernel(const SunWalkArgs SA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = SA.m;
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-    __attribute__((address_space(3))) float* sun_lds = (__attribute__((address_space(3))) float*)(lds + ks_lds_bytes(A.bias_floats));
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = wave >> 1, par = wave & 1;
-    const int h = lane >> 5;
+    constexpr int PROG = PROG_FIELD;
     const int C = A.n_classes;
     const int n_suns = SA.n_suns;
-
-    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
-    for (int i = threadIdx.x; i < 3 * n_suns; i += 256) sun_lds[i] = A.sun[i];
-    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
-    KsCtx cx;
-    cx.lds = lds;
-    cx.par_off = par * KS_PAR_BYTES;
-    {
-        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
-        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
-        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
-    }
-
-    Pend pd;
-    pd.goff = 0;
-    pd.wr = 0;
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    KS_PROLOGUE(A,
+        __attribute__((address_space(3))) float* sun_lds = (__attribute__((address_space(3))) float*)(lds + ks_lds_bytes(A.bias_floats));
+        for (int i = threadIdx.x; i < 3 * n_suns; i += 256) sun_lds[i] = A.sun[i];)
 
     const int64_t n_tiles = field_tiles(A.n, 0, KS_TILE_PTS, 2);
     snerf_field_out_dev once = A.out;      // what is stored once per point
@@ -460,43 +460,22 @@ __global__ __launch_bounds__(256, 1) void sun_walk_ks_kernel(const SunWalkArgs S
 
         constexpr int KH = W / 32, KH2 = W2 / 32;
         constexpr int NBW = W / 64, NBW2 = W2 / 64;
-        Frag hA[KH], hB[KH];
-#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
-#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
-#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
-        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
-        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
-        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
-        Frag x1f[KH2];
-        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
-        f32x16 raw = HEADL(F_HEAD, KH2, x1f);
+        Frag hA[KH], hB[KH], x1f[KH2];
+        f32x16 raw;
+        KS_TRUNK(pe, hA, hB, x1f, raw);
         const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         for (int j = 0; j < n_suns; ++j) {
             const float s0 = sun_lds[3 * j], s1 = sun_lds[3 * j + 1], s2 = sun_lds[3 * j + 2];      // wave-uniform
             Frag ps[PESUN_KS];
             make_pe_sun(s0, s1, s2, h, ps);
             Frag sA[KH2], sB[KH2];
-            LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);
-            LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);
-            LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);
-            raw = HEADL(F_S4, KH2, sA);
+            KS_SOLAR(x1f, ps, sA, sB, raw);
             if (par == 0 && h == 0 && valid && A.out.solar_vis) A.out.solar_vis[(int64_t)j * A.n + n] = sigmoid_f(raw[0]);
         }
-        LAYER(F_A1, NBW, KH2, 0, x1f, nullptr, hA);
-        LAYER(F_A2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_A3, NBW, KH, 0, hB, nullptr, hA);
-        raw = HEADL(F_AC, KH, hA);
+        KS_ADJUST(x1f, hA, hB, raw);
         float adj[3 * C_MAX];
 #pragma unroll
         for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
-#undef LAYER
-#undef HEADL
-#undef OWNB
         if (par == 0 && h == 0 && valid) store_field_outputs<0>(once, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, 0.f, adj, pcls);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
@@ -509,39 +488,14 @@ hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t
     return launch_fused(sun_walk_ks_kernel<512>, field_tiles(a.m.n, 0, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
 }
 
-// Ray surface at this width: the VARIANT 3 walk of mlp_ks_kernel (a wave pair owns a ray) with the compositing scan in the pass end (kernels.hip
+// Ray surface at this width: the VARIANT 3 walk of mlp_ks_kernel (a wave pair owns a ray; KS_TRUNK alone) with the compositing scan in the pass end (kernels.hip
 // ray_surface_kernel, mlp_device.h RaySurf).  Both waves of a pair hold the same density and the same sums and vote alike; wave 0 of the pair stores.
 template <int W>
 __global__ __launch_bounds__(256, 1) void ray_surface_ks_kernel(const RaySurfaceArgs RA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = RA.m;
-    constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = wave >> 1, par = wave & 1;
-    const int h = lane >> 5;
-
-    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
-    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
-    KsCtx cx;
-    cx.lds = lds;
-    cx.par_off = par * KS_PAR_BYTES;
-    {
-        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
-        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
-        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
-    }
-    __attribute__((address_space(3))) float* vote_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + (A.bias_floats + 32) * 4 + 4 * KS_XBUF_BYTES);
-
-    Pend pd;
-    pd.goff = 0;
-    pd.wr = 0;
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    constexpr int PROG = PROG_FIELD;
+    KS_PROLOGUE(A)
 
     const int64_t n_tiles = field_tiles(A.n, 3, KS_TILE_PTS, 2);      // a tile is a group of 2 rays, one per wave pair
     const int passes = (A.n_samples + 31) / 32;
@@ -555,24 +509,9 @@ __global__ __launch_bounds__(256, 1) void ray_surface_ks_kernel(const RaySurface
 
         constexpr int KH = W / 32, KH2 = W2 / 32;
         constexpr int NBW = W / 64, NBW2 = W2 / 64;
-        Frag hA[KH], hB[KH];
-#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
-#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
-#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
-        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
-        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
-        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
-        Frag x1f[KH2];
-        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
-        const f32x16 raw = HEADL(F_HEAD, KH2, x1f);
-#undef LAYER
-#undef HEADL
-#undef OWNB
+        Frag hA[KH], hB[KH], x1f[KH2];
+        f32x16 raw;
+        KS_TRUNK(pe, hA, hB, x1f, raw);
         const float rho_raw = raw[3];
         RAYSURF_PASS_END(rs, A, RA.out, tile, pass, passes, 2, pair, wave, 4, par == 0, lane, rho_raw, vote_lds);
     }
@@ -586,39 +525,15 @@ hipError_t launch_ray_surface_ks(int W, const RaySurfaceArgs& a, int n_cu, hipSt
     return launch_fused(ray_surface_ks_kernel<512>, field_tiles(a.m.n, 3, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
 }
 
-// Shadow walk at this width: the ray surface's walk (a wave pair owns a ray) through the layers of VARIANT 1 of mlp_ks_kernel with the shadow test in the
+// Shadow walk at this width: the ray surface's walk (a wave pair owns a ray) through the layers of VARIANT 1 of mlp_ks_kernel (KS_TRUNK, KS_SOLAR) with the shadow test in the
 // pass end (kernels.hip shadow_walk_kernel, mlp_device.h RayShadow).  Both waves of a pair hold the same density, visibility and sums; wave 0 of the pair
 // stores.  F_S4 is followed by the next pass's F_FC1, as in mlp_ks_kernel's VARIANT 1.
 template <int W>
 __global__ __launch_bounds__(256, 1) void shadow_walk_ks_kernel(const ShadowWalkArgs SA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = SA.m;
-    constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = wave >> 1, par = wave & 1;
-    const int h = lane >> 5;
-
-    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
-    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
-    KsCtx cx;
-    cx.lds = lds;
-    cx.par_off = par * KS_PAR_BYTES;
-    {
-        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
-        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
-        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
-    }
-
-    Pend pd;
-    pd.goff = 0;
-    pd.wr = 0;
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    constexpr int PROG = PROG_FIELD;
+    KS_PROLOGUE(A)
 
     const int64_t n_tiles = field_tiles(A.n, 3, KS_TILE_PTS, 2);      // a tile is a group of 2 rays, one per wave pair
     const int passes = (A.n_samples + 31) / 32;
@@ -632,32 +547,14 @@ __global__ __launch_bounds__(256, 1) void shadow_walk_ks_kernel(const ShadowWalk
 
         constexpr int KH = W / 32, KH2 = W2 / 32;
         constexpr int NBW = W / 64, NBW2 = W2 / 64;
-        Frag hA[KH], hB[KH];
-#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
-#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
-#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
-        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
-        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
-        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
-        Frag x1f[KH2];
-        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
-        f32x16 raw = HEADL(F_HEAD, KH2, x1f);
+        Frag hA[KH], hB[KH], x1f[KH2];
+        f32x16 raw;
+        KS_TRUNK(pe, hA, hB, x1f, raw);
         const float rho_raw = raw[3];
         Frag ps[PESUN_KS];
         make_pe_sun(s0, s1, s2, h, ps);
         Frag sA[KH2], sB[KH2];
-        LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);
-        LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);
-        LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);
-        raw = HEADL(F_S4, KH2, sA);
-#undef LAYER
-#undef HEADL
-#undef OWNB
+        KS_SOLAR(x1f, ps, sA, sB, raw);
         const float sv_raw = raw[0];
         RAYSHADOW_PASS_END(rs, A, SA.out, tile, pass, passes, 2, pair, par == 0, lane, rho_raw, sv_raw);
     }
@@ -677,30 +574,10 @@ hipError_t launch_shadow_walk_ks(int W, const ShadowWalkArgs& a, int n_cu, hipSt
 // per ray, not averaged over a ray's samples).
 template <int W>
 __global__ __launch_bounds__(256, 1) void mlp_ks_group_kernel(const MlpArgs A) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int C_MAX = kMaxClasses;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = wave >> 1, par = wave & 1;
-    const int h = lane >> 5;
+    constexpr int PROG = PROG_GROUP;
     const int C = A.n_classes;
-    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
-    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
-    KsCtx cx;
-    cx.lds = lds;
-    cx.par_off = par * KS_PAR_BYTES;
-    {
-        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
-        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
-        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
-    }
-    Pend pd;
-    pd.goff = 0;
-    pd.wr = 0;
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    KS_PROLOGUE(A)
     const int64_t n_tiles = (A.n + KS_TILE_PTS - 1) / KS_TILE_PTS;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t n = tile * KS_TILE_PTS + pair * 32 + (lane & 31);
@@ -712,9 +589,6 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_group_kernel(const MlpArgs A) {
         static_assert(ks_layer_pairs(group_layer(W, C_MAX, G_T1)) == NBW * PETIME_KS && ks_layer_pairs(group_layer(W, C_MAX, G_T2)) == NBW * 2 * KH &&
                       ks_layer_pairs(group_layer(W, C_MAX, G_CL)) == KH && ks_layer_pairs(group_layer(W, C_MAX, G_K1)) == NB4 * PESUN_KS &&
                       ks_layer_pairs(group_layer(W, C_MAX, G_K2)) == KH4, "kernel and packer (program.h ks_*) disagree about the stream");
-#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_GROUP, W, C_MAX, L) + par * (NBH) * 32)
-#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
-#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_GROUP, W, C_MAX, L), IN0, wave, lane)
         Frag pt[PETIME_KS];
         make_pe_time(t0, t1, h, pt);
         Frag hA[KH], hB[KH];
@@ -729,9 +603,6 @@ __global__ __launch_bounds__(256, 1) void mlp_ks_group_kernel(const MlpArgs A) {
         Frag kA[KH4];
         LAYER(G_K1, NB4, 0, PESUN_KS, nullptr, ps, kA);
         raw = HEADL(G_K2, KH4, kA);
-#undef LAYER
-#undef HEADL
-#undef OWNB
         if (par == 0 && h == 0 && valid) {
             float m = -3.0e38f;
 #pragma unroll
@@ -782,43 +653,19 @@ int field_variant_chunks_ks(int W, int C, int variant) {
 int mlp_ks_lds_bytes(int bias_floats) { return ks_lds_bytes(bias_floats); }
 int mlp_ks_tile_points() { return KS_TILE_PTS; }
 
-// Film frame at this width: the ray surface's walk (a wave pair owns a ray, the early-out vote) through the layer list of mlp_ks_kernel's VARIANT 0 on its
-// unchanged stream, with the film frame's shading and compositing in the pass end (kernels.hip frame_walk_kernel, mlp_device.h RayFrame).  Both waves of a
-// pair hold the same head rows and the same sums and vote alike; wave 0 of the pair stores.  F_AC is followed by the next pass's F_FC1, as in VARIANT 0.
-// The launch's inputs wait in LDS behind the vote words, as sun_walk_ks_kernel's suns do.
+// Film frame at this width: the ray surface's walk (a wave pair owns a ray, the early-out vote) through the layer lists of mlp_ks_kernel's VARIANT 0 (KS_TRUNK,
+// KS_SOLAR, KS_ADJUST) on its unchanged stream, with the film frame's shading and compositing in the pass end (kernels.hip frame_walk_kernel, mlp_device.h
+// RayFrame).  Both waves of a pair hold the same head rows and the same sums and vote alike; wave 0 of the pair stores.  F_AC is followed by the next pass's
+// F_FC1, as in VARIANT 0. The launch's inputs wait in LDS behind the vote words, as sun_walk_ks_kernel's suns do.
 template <int W>
 __global__ __launch_bounds__(256, 1) void frame_walk_ks_kernel(const FrameWalkArgs FA) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const MlpArgs& A = FA.m;
     constexpr int C_MAX = kMaxClasses;
     constexpr int W2 = W / 2;
-    lds_char* lds = (lds_char*)smem;
-    __attribute__((address_space(3))) float* bias_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES);
-    __attribute__((address_space(3))) float* fin = (__attribute__((address_space(3))) float*)(lds + ks_lds_bytes(A.bias_floats));
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = wave >> 1, par = wave & 1;
-    const int h = lane >> 5;
-
-    for (int i = threadIdx.x; i < A.bias_floats + 32; i += 256) bias_lds[i] = i < A.bias_floats ? A.bias[i] : 0.f;
-    frame_stage_inputs(FA, fin);
-    lds_cfloat* zero_bias = bias_lds + A.bias_floats;
-    KsCtx cx;
-    cx.lds = lds;
-    cx.par_off = par * KS_PAR_BYTES;
-    {
-        lds_char* xb = lds + RING_BYTES + (A.bias_floats + 32) * 4;
-        cx.xw = xb + (pair * 2 + par) * KS_XBUF_BYTES;
-        cx.xr = xb + (pair * 2 + (par ^ 1)) * KS_XBUF_BYTES;
-    }
-    __attribute__((address_space(3))) float* vote_lds = (__attribute__((address_space(3))) float*)(lds + RING_BYTES + (A.bias_floats + 32) * 4 + 4 * KS_XBUF_BYTES);
-
-    Pend pd;
-    pd.goff = 0;
-    pd.wr = 0;
-    RING_PROLOGUE(rg, RING_D, A, lds, wave, lane)
-    __syncthreads();
+    constexpr int PROG = PROG_FIELD;
+    KS_PROLOGUE(A,
+        __attribute__((address_space(3))) float* fin = (__attribute__((address_space(3))) float*)(lds + ks_lds_bytes(A.bias_floats));
+        frame_stage_inputs(FA, fin);)
 
     const int64_t n_tiles = field_tiles(A.n, 3, KS_TILE_PTS, 2);      // a tile is a group of 2 rays, one per wave pair
     const int passes = (A.n_samples + 31) / 32;
@@ -832,21 +679,9 @@ __global__ __launch_bounds__(256, 1) void frame_walk_ks_kernel(const FrameWalkAr
 
         constexpr int KH = W / 32, KH2 = W2 / 32;
         constexpr int NBW = W / 64, NBW2 = W2 / 64;
-        Frag hA[KH], hB[KH];
-#define OWNB(L, NBH) (bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L) + par * (NBH) * 32)
-#define LAYER(L, NBH, KSHv, KSXv, IN0, IN1, OUT) run_layer_ks<NBH, KSHv, KSXv>(rg, pd, A.stream, A.stream_bytes, cx, OWNB(L, NBH), IN0, IN1, OUT, wave, lane)
-#define HEADL(L, KSHv, IN0) run_head_ks<KSHv>(rg, pd, A.stream, A.stream_bytes, cx, par ? zero_bias : bias_lds + prog_bias_start(PROG_FIELD, W, C_MAX, L), IN0, wave, lane)
-        LAYER(F_FC1, NBW, 0, PEPOS_KS, nullptr, pe, hA);
-        LAYER(F_FC2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC3, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC4, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC5, NBW, KH, PEPOS_KS, hB, pe, hA);
-        LAYER(F_FC6, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_FC7, NBW, KH, 0, hB, nullptr, hA);
-        LAYER(F_FC8, NBW, KH, 0, hA, nullptr, hB);
-        Frag x1f[KH2];
-        LAYER(F_FC9, NBW2, KH, 0, hB, nullptr, x1f);
-        f32x16 raw = HEADL(F_HEAD, KH2, x1f);
+        Frag hA[KH], hB[KH], x1f[KH2];
+        f32x16 raw;
+        KS_TRUNK(pe, hA, hB, x1f, raw);
         const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         float sv_raw;
         {
@@ -854,22 +689,13 @@ __global__ __launch_bounds__(256, 1) void frame_walk_ks_kernel(const FrameWalkAr
             Frag ps[PESUN_KS];
             make_pe_sun(s0, s1, s2, h, ps);
             Frag sA[KH2], sB[KH2];
-            LAYER(F_S1, NBW2, KH2, PESUN_KS, x1f, ps, sA);
-            LAYER(F_S2, NBW2, KH2, 0, sA, nullptr, sB);
-            LAYER(F_S3, NBW2, KH2, 0, sB, nullptr, sA);
-            raw = HEADL(F_S4, KH2, sA);
+            KS_SOLAR(x1f, ps, sA, sB, raw);
             sv_raw = raw[0];
         }
-        LAYER(F_A1, NBW, KH2, 0, x1f, nullptr, hA);
-        LAYER(F_A2, NBW, KH, 0, hA, nullptr, hB);
-        LAYER(F_A3, NBW, KH, 0, hB, nullptr, hA);
-        raw = HEADL(F_AC, KH, hA);
+        KS_ADJUST(x1f, hA, hB, raw);
         float adj[3 * C_MAX];
 #pragma unroll
         for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
-#undef LAYER
-#undef HEADL
-#undef OWNB
         RAYFRAME_PASS_END(rf, A, FA, fin, tile, pass, passes, 2, pair, wave, 4, par == 0, lane, col_r, col_g, col_b, rho_raw, sv_raw, adj, vote_lds);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
@@ -881,5 +707,9 @@ hipError_t launch_frame_walk_ks(int W, const FrameWalkArgs& a, int n_cu, hipStre
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     return launch_fused(frame_walk_ks_kernel<512>, field_tiles(a.m.n, 3, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
 }
+
+#undef OWNB
+#undef LAYER
+#undef HEADL
 
 }  // namespace snerf

@@ -133,6 +133,17 @@ __device__ __forceinline__ void ring_step(Ring& rg, const uint8_t* stream, uint3
     rg.wr = ring_next<D>(rg.wr);
 }
 
+// Persistent launch of a fused kernel of any family: min(n_tiles, n_cu) workgroups (at least one) of `block` threads with `lds_bytes` of dynamic LDS.
+template <class Args>
+hipError_t launch_fused(void (*kernel)(Args), int64_t n_tiles, int block, int lds_bytes, const Args& a, int n_cu, hipStream_t st) {
+    int grid = (int)(n_tiles < n_cu ? n_tiles : n_cu);
+    if (grid < 1) grid = 1;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, st, a);
+    return hipGetLastError();
+}
+
 // sin/cos of k_j * x exactly as the reference evaluates them (misc.py:109,127-131): the fp32 argument is
 // 2^j * fl32(fl32(pi/2) * x); it is reduced in fp64 (exact power-of-two scaling, exact fract) before v_sin/v_cos.
 struct PeArg {
