@@ -530,6 +530,58 @@ int snerf_image_error(int64_t n_pixels, const float* d_image, const float* d_gt,
  * [n_rays, n_samples] arrays with arbitrary per-sample deltas (snerf_composite_rays fuses the same scan with the shading). */
 int snerf_transmittance(int64_t n_rays, int n_samples, const float* d_rho, const float* d_delta, float* d_pv, void* stream);
 
+/* ---- device ray loader: the reference's per-step data path - two DataLoader(shuffle=True, num_workers=4) collating batch_size single-row
+ * __getitem__ calls (mg_run_NeRF.py:74-84, NN_loaders/mg_Color_Loader.py:94-102), Net_tool.get_data / data_to_dict (mg_run_NeRF.py:229-264, :122-133)
+ * and SC_loader.__getitem__'s t.rand(4) per sun-check ray (NN_loaders/mg_SC_loader.py:17-21) - over a ray table that already lives on the device
+ * (d_table [n_rows, 22] fp32: Img_Pt 2 | Top 3 | Bot 3 | View_Angle 3 | Sun_Angle 3 | Time_Encoded 4 | Sample_Weight 1 | GT_Color 3; owned by the
+ * caller, alive as long as the loader).
+ *   Shuffle without replacement: row i of a batch is table[perm_epoch(((batch_in_epoch * world) + rank) * batch + i)]; perm is a keyed bijection of
+ *   [0, n_rows) - a balanced Feistel network over 2^k >= n_rows (k even), six rounds of murmur3's 32-bit finaliser, round keys from (seed, epoch),
+ *   cycle-walking while the value is >= n_rows.  Exact integer arithmetic: snerf_loader_indices_host gives the same indices without a GPU.
+ *   Epochs as DataLoader(shuffle=True): drop_last = 0 (the reference's default) ceil(n_rows / batch) batches, the last one short; drop_last = 1
+ *   floor(n_rows / batch); world > 1 (data parallel) needs drop_last - floor(n_rows / (batch * world)) batches per epoch, the ranks taking disjoint
+ *   consecutive batch-sized blocks of the ONE permutation.
+ *   Sun-check rays: Philox4x32-10, key = the seed's (low, high) halves, counter = (i, draws low, draws high, rank), u = (word >> 8) * 2^-24;
+ *   top = (u0 * dx + x0, u1 * dy + y0, z_hi), bot = (u2 * dx + x0, u3 * dy + y0, z_lo), product and sum rounded separately as torch's fp32 ops do;
+ *   bounds6 (HOST, optional) = x0, x1, y0, y1, z_lo, z_hi (NULL: the cube [-1, 1]^3, setup_SC_loader's default), dx = x1 - x0 in fp32.
+ *   State: four int64 in DEVICE memory {epoch, batch_in_epoch, draws, reserved}.  The kernels read the position from there, never from a launch
+ *   argument, and a one-thread kernel behind the draw advances it: captured in a hipGraph (two kernel nodes), snerf_loader_next draws a new batch at
+ *   every replay.  The handle keeps a host shadow, advanced by the same rule per (uncaptured) launch and used only to size a short last batch; a
+ *   capture is refused (SNERF_E_STATE) unless every batch of an epoch has `batch` rows.  After replays the device copy is the truth
+ *   (snerf_loader_get_state).
+ * snerf_loader_create: SNERF_E_INVALID - before anything touches the GPU - for a NULL table, row_width != 22, n_rows < 1, batch < 1 (or >= 2^31),
+ *   rank outside [0, world), world > 1 without drop_last, batch * world > n_rows with drop_last.
+ * snerf_loader_next: every output is optional (NULL = skip); returns the row count of this batch (>= 1) or a negative SNERF_E_* code.
+ * snerf_loader_set_state / _get_state: state4 is a HOST array; set writes both copies; both synchronise `stream` and are refused while it captures. */
+typedef struct snerf_loader snerf_loader;
+typedef struct snerf_loader_out {
+    float* d_img_pt;        /* [B,2] */
+    float* d_top;           /* [B,3] */
+    float* d_bot;           /* [B,3] */
+    float* d_view_angle;    /* [B,3] */
+    float* d_sun_angle;     /* [B,3] */
+    float* d_time_encoded;  /* [B,4] */
+    float* d_sample_weight; /* [B,1] */
+    float* d_gt_color;      /* [B,3] */
+    int64_t* d_row_index;   /* [B] */
+    float* d_sc_top;        /* [B,3] */
+    float* d_sc_bot;        /* [B,3] */
+} snerf_loader_out;
+int snerf_loader_create(const float* d_table, int64_t n_rows, int row_width, int64_t batch, uint64_t seed, int drop_last, int rank, int world,
+                        const float* bounds6, snerf_loader** out);
+void snerf_loader_destroy(snerf_loader* l);
+int64_t snerf_loader_batches_per_epoch(const snerf_loader* l);
+int64_t snerf_loader_batch(const snerf_loader* l);       /* rows of a full batch: what every output buffer must hold */
+int64_t snerf_loader_next(snerf_loader* l, const snerf_loader_out* out, void* stream);
+int snerf_loader_get_state(snerf_loader* l, int64_t* state4, void* stream);
+int snerf_loader_set_state(snerf_loader* l, const int64_t* state4, void* stream);
+/* Host-only mirrors (no GPU): positions first .. first + count - 1 of epoch `epoch`'s permutation of [0, n_rows); the sun-check rays
+ * first .. first + count - 1 of draw `draws` on `rank` (top / bot: [count, 3]).  snerf_loader_philox_host is the generator itself (counter 4 words,
+ * key 2 words -> 4 words), for its known-answer vectors. */
+int snerf_loader_indices_host(int64_t n_rows, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int64_t* out);
+int snerf_loader_sc_rays_host(uint64_t seed, int64_t draws, int rank, int64_t first, int64_t count, const float* bounds6, float* top, float* bot);
+int snerf_loader_philox_host(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
+
 /* Name and launch geometry of the dominant kernel (for profiling scripts): fills grid/block/lds bytes. */
 int snerf_field_kernel_info(const snerf_model* m, int64_t n_points, int* grid, int* block, int* lds_bytes);
 

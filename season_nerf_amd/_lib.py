@@ -27,6 +27,12 @@ class SunWalkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("d_shaded", "d_season", "d_base", "d_raw_shadow", "d_shadow_adjust")]
 
 
+class LoaderOut(C.Structure):
+    """snerf_loader_out: the optional outputs of snerf_loader_next (NULL = skip)."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_img_pt", "d_top", "d_bot", "d_view_angle", "d_sun_angle", "d_time_encoded", "d_sample_weight", "d_gt_color",
+                                          "d_row_index", "d_sc_top", "d_sc_bot")]
+
+
 class I8Estimate(C.Structure):
     """snerf_i8_estimate: the pack-time error model of the int8-digit format (include/season_nerf_hip.h)."""
     _fields_ = [("head_rms", C.c_double * 4), ("hidden_rms", C.c_double), ("worst", C.c_double),
@@ -130,6 +136,21 @@ def lib():
     L.snerf_linear_dgrad.argtypes = [i64, i32, i32, vp, i64, vp, i32, C.c_float, i32, vp, i64, i32, vp, C.c_size_t, vp, i64, vp, vp, vp, vp, vp]
     L.snerf_linear_wgrad.argtypes = [i64, i32, i32, vp, i64, vp, i64, C.c_float, vp, i32, vp, i32, vp]
     L.snerf_field_kernel_info.argtypes = [vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    u64 = C.c_uint64
+    L.snerf_loader_create.argtypes = [vp, i64, i32, i64, u64, i32, i32, i32, vp, C.POINTER(vp)]
+    L.snerf_loader_destroy.argtypes = [vp]
+    L.snerf_loader_destroy.restype = None
+    L.snerf_loader_batches_per_epoch.restype = i64
+    L.snerf_loader_batches_per_epoch.argtypes = [vp]
+    L.snerf_loader_batch.restype = i64
+    L.snerf_loader_batch.argtypes = [vp]
+    L.snerf_loader_next.restype = i64
+    L.snerf_loader_next.argtypes = [vp, C.POINTER(LoaderOut), vp]
+    L.snerf_loader_get_state.argtypes = [vp, vp, vp]
+    L.snerf_loader_set_state.argtypes = [vp, vp, vp]
+    L.snerf_loader_indices_host.argtypes = [i64, u64, i64, i64, i64, vp]
+    L.snerf_loader_sc_rays_host.argtypes = [u64, i64, i32, i64, i64, vp, vp, vp]
+    L.snerf_loader_philox_host.argtypes = [vp, vp, vp]
     _lib = L
     return L
 
@@ -156,4 +177,6 @@ EXPORTS = ["snerf_last_error", "snerf_abi_version", "snerf_model_create", "snerf
            "snerf_trainer_forward_image", "snerf_trainer_backward_image", "snerf_trainer_backward_image_dt", "snerf_trainer_backward_points", "snerf_trainer_forward_solar",
            "snerf_trainer_backward_solar", "snerf_trainer_zero_grad", "snerf_trainer_set_allreduce", "snerf_trainer_adam_step", "snerf_trainer_adam_step_dev", "snerf_adam_step", "snerf_trainer_debug_read", "snerf_train_kernel_debug",
            "snerf_rows_debug_set", "snerf_rows_record_reset", "snerf_rows_record_read",
-           "snerf_loss_scratch_bytes", "snerf_loss_scratch_init", "snerf_loss_terms_forward", "snerf_loss_terms_backward"]
+           "snerf_loss_scratch_bytes", "snerf_loss_scratch_init", "snerf_loss_terms_forward", "snerf_loss_terms_backward",
+           "snerf_loader_create", "snerf_loader_destroy", "snerf_loader_batches_per_epoch", "snerf_loader_batch", "snerf_loader_next", "snerf_loader_get_state", "snerf_loader_set_state",
+           "snerf_loader_indices_host", "snerf_loader_sc_rays_host", "snerf_loader_philox_host"]

@@ -11,6 +11,7 @@
 #include <string>
 
 #include "kernels.h"
+#include "loader_common.h"
 #include "pack.h"
 #include "train.h"
 
@@ -63,6 +64,16 @@ struct snerf_model {
     mutable uint8_t* d_walk = nullptr;
     mutable int walk_suns = 0;
     int n_cu = 0;
+};
+
+struct snerf_loader {
+    const float* d_table = nullptr;
+    int64_t n = 0, batch = 0, bpe = 0;      // rows of the table, rows per batch, batches per epoch
+    uint64_t seed = 0;
+    int drop_last = 0, rank = 0, world = 1, bits = 2;
+    float b[6] = {0};                        // x0, dx, y0, dy, z_lo, z_hi of the sun-check rays
+    int64_t* d_state = nullptr;              // {epoch, batch_in_epoch, draws, reserved}: what the kernels read
+    int64_t shadow[4] = {0, 0, 0, 0};        // host copy, advanced per uncaptured launch: sizes a short last batch, nothing else
 };
 
 extern "C" {
@@ -901,6 +912,147 @@ int snerf_field_kernel_info(const snerf_model* m, int64_t n_points, int* grid, i
         else if (ks) *lds_bytes = mlp_ks_lds_bytes((int)m->host_ks.bias.size());
         else *lds_bytes = mlp_lds_bytes((int)m->host[PROG_FIELD].bias.size());
     }
+    return SNERF_OK;
+}
+
+// ---- device ray loader (csrc/loader.hip; arithmetic shared with the host mirrors: csrc/loader_common.h)
+static int64_t loader_batches_per_epoch(int64_t n, int64_t batch, int drop_last, int world) {
+    return drop_last ? n / (batch * world) : (n + batch - 1) / batch;
+}
+static void loader_advance_host(int64_t* s, int64_t bpe) {      // the rule of loader_advance_kernel
+    s[2] += 1;
+    if (++s[1] >= bpe) { s[1] = 0; s[0] += 1; }
+}
+static void loader_bounds(const float* bounds6, float* b) {     // SC_loader.__init__: x = bounds[0,0], dx = bounds[0,1] - bounds[0,0] (fp32), ...
+    static const float cube[6] = {-1.f, 1.f, -1.f, 1.f, -1.f, 1.f};
+    const float* s = bounds6 ? bounds6 : cube;
+    b[0] = s[0]; b[1] = s[1] - s[0]; b[2] = s[2]; b[3] = s[3] - s[2]; b[4] = s[4]; b[5] = s[5];
+}
+static bool stream_capturing(void* stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+int snerf_loader_create(const float* d_table, int64_t n_rows, int row_width, int64_t batch, uint64_t seed, int drop_last, int rank, int world,
+                        const float* bounds6, snerf_loader** out) {
+    if (!out) return fail(SNERF_E_INVALID, "snerf_loader_create: NULL result pointer");
+    *out = nullptr;
+    if (!d_table) return fail(SNERF_E_INVALID, "snerf_loader_create: NULL table");
+    if (row_width != kLoaderCols) return fail(SNERF_E_INVALID, "snerf_loader_create: the ray table has 22 columns, got " + std::to_string(row_width));
+    if (n_rows < 1) return fail(SNERF_E_INVALID, "snerf_loader_create: n_rows < 1");
+    if (batch < 1 || batch > 0x7fffffffLL) return fail(SNERF_E_INVALID, "snerf_loader_create: batch must be in [1, 2^31)");
+    if (world < 1 || rank < 0 || rank >= world) return fail(SNERF_E_INVALID, "snerf_loader_create: rank outside [0, world)");
+    if (world > 1 && !drop_last) return fail(SNERF_E_INVALID, "snerf_loader_create: world > 1 needs drop_last (every rank must see the same number of full batches)");
+    if (drop_last && batch * world > n_rows) return fail(SNERF_E_INVALID, "snerf_loader_create: batch * world > n_rows with drop_last - an epoch would be empty");
+    snerf_loader* l = new snerf_loader();
+    l->d_table = d_table; l->n = n_rows; l->batch = batch; l->seed = seed; l->drop_last = drop_last ? 1 : 0; l->rank = rank; l->world = world;
+    l->bits = loader_bits(n_rows);
+    l->bpe = loader_batches_per_epoch(n_rows, batch, l->drop_last, world);
+    loader_bounds(bounds6, l->b);
+    hipError_t e = hipMalloc((void**)&l->d_state, 4 * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMemcpy(l->d_state, l->shadow, 4 * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (l->d_state) (void)hipFree(l->d_state);
+        delete l;
+        return fail_hip(e, "snerf_loader_create: state allocation");
+    }
+    *out = l;
+    return SNERF_OK;
+}
+
+void snerf_loader_destroy(snerf_loader* l) {
+    if (!l) return;
+    if (l->d_state) (void)hipFree(l->d_state);
+    delete l;
+}
+
+int64_t snerf_loader_batches_per_epoch(const snerf_loader* l) {
+    if (!l) return fail(SNERF_E_INVALID, "NULL loader");
+    return l->bpe;
+}
+
+int64_t snerf_loader_batch(const snerf_loader* l) {
+    if (!l) return fail(SNERF_E_INVALID, "NULL loader");
+    return l->batch;
+}
+
+int64_t snerf_loader_next(snerf_loader* l, const snerf_loader_out* out, void* stream) {
+    if (!l || !out) return fail(SNERF_E_INVALID, "snerf_loader_next: NULL loader or outputs");
+    const bool uniform = l->bpe * l->batch * l->world <= l->n && (l->drop_last || l->n % l->batch == 0);
+    const bool capturing = stream_capturing(stream);
+    if (capturing && !uniform)
+        return fail(SNERF_E_STATE, "snerf_loader_next: a captured draw replays with a fixed row count - the epoch's last batch is short (use drop_last)");
+    const int64_t p0 = (l->shadow[1] * l->world + l->rank) * l->batch;
+    const int64_t rows = uniform ? l->batch : (l->n - p0 < l->batch ? l->n - p0 : l->batch);
+    if (rows < 1) return fail(SNERF_E_STATE, "snerf_loader_next: the host shadow of the position is past the epoch's end");
+    LoaderArgs a{};
+    a.table = l->d_table; a.n_rows = l->n; a.batch = l->batch; a.rows = rows; a.batches_per_epoch = l->bpe; a.state = l->d_state; a.seed = l->seed;
+    a.rank = l->rank; a.world = l->world; a.bits = l->bits;
+    a.img_pt = out->d_img_pt; a.top = out->d_top; a.bot = out->d_bot; a.view = out->d_view_angle; a.sun = out->d_sun_angle; a.time = out->d_time_encoded;
+    a.weight = out->d_sample_weight; a.gt = out->d_gt_color; a.index = out->d_row_index; a.sc_top = out->d_sc_top; a.sc_bot = out->d_sc_bot;
+    a.x0 = l->b[0]; a.dx = l->b[1]; a.y0 = l->b[2]; a.dy = l->b[3]; a.z_lo = l->b[4]; a.z_hi = l->b[5];
+    hipError_t e = launch_loader_draw(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "loader draw kernel launch");
+    e = launch_loader_advance(l->d_state, l->bpe, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "loader advance kernel launch");
+    if (!capturing) loader_advance_host(l->shadow, l->bpe);      // (a capture executes nothing; its replays advance the device copy only)
+    return rows;
+}
+
+int snerf_loader_get_state(snerf_loader* l, int64_t* state4, void* stream) {
+    if (!l || !state4) return fail(SNERF_E_INVALID, "snerf_loader_get_state: NULL argument");
+    if (stream_capturing(stream)) return fail(SNERF_E_STATE, "snerf_loader_get_state: the stream is capturing");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);      // the draws queued so far have advanced the state; then a blocking copy (never a stream-ordered
+    if (e == hipSuccess) e = hipMemcpy(state4, l->d_state, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);      // runtime copy in this library: DESIGN 5.4c)
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "snerf_loader_get_state");
+}
+
+int snerf_loader_set_state(snerf_loader* l, const int64_t* state4, void* stream) {
+    if (!l || !state4) return fail(SNERF_E_INVALID, "snerf_loader_set_state: NULL argument");
+    if (state4[0] < 0 || state4[1] < 0 || state4[1] >= l->bpe || state4[2] < 0)
+        return fail(SNERF_E_INVALID, "snerf_loader_set_state: epoch / draws negative or batch_in_epoch outside [0, batches per epoch)");
+    if (stream_capturing(stream)) return fail(SNERF_E_STATE, "snerf_loader_set_state: the stream is capturing");
+    for (int i = 0; i < 4; ++i) l->shadow[i] = state4[i];
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);      // no draw in flight reads the state while the blocking copy replaces it
+    if (e == hipSuccess) e = hipMemcpy(l->d_state, l->shadow, 4 * sizeof(int64_t), hipMemcpyHostToDevice);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "snerf_loader_set_state");
+}
+
+int snerf_loader_indices_host(int64_t n_rows, uint64_t seed, int64_t epoch, int64_t first, int64_t count, int64_t* out) {
+    if (n_rows < 1 || epoch < 0 || first < 0 || count < 0 || first > n_rows - count || (count > 0 && !out))
+        return fail(SNERF_E_INVALID, "snerf_loader_indices_host: need n_rows >= 1, epoch >= 0 and [first, first + count) inside [0, n_rows)");
+    const int bits = loader_bits(n_rows);
+    const LoaderKeys K = loader_keys(seed, (uint64_t)epoch);
+    for (int64_t j = 0; j < count; ++j) out[j] = loader_perm(first + j, n_rows, bits, K);
+    return SNERF_OK;
+}
+
+int snerf_loader_sc_rays_host(uint64_t seed, int64_t draws, int rank, int64_t first, int64_t count, const float* bounds6, float* top, float* bot) {
+    if (first < 0 || count < 0 || (count > 0 && (!top || !bot))) return fail(SNERF_E_INVALID, "snerf_loader_sc_rays_host: bad argument");
+    float b[6];
+    loader_bounds(bounds6, b);
+    for (int64_t j = 0; j < count; ++j) {
+        uint32_t w[4];
+        loader_sc_words(seed, (uint64_t)draws, (uint32_t)rank, (uint32_t)(first + j), w);
+        float u[4], v[4];
+        for (int q = 0; q < 4; ++q) u[q] = loader_uniform(w[q]);
+        for (int q = 0; q < 4; ++q) {
+            const float prod = u[q] * ((q & 1) ? b[3] : b[1]);    // two roundings (this file is built with -ffp-contract=off), as __fmul_rn / __fadd_rn in the kernel
+            v[q] = prod + ((q & 1) ? b[2] : b[0]);
+        }
+        top[j * 3] = v[0]; top[j * 3 + 1] = v[1]; top[j * 3 + 2] = b[5];
+        bot[j * 3] = v[2]; bot[j * 3 + 1] = v[3]; bot[j * 3 + 2] = b[4];
+    }
+    return SNERF_OK;
+}
+
+int snerf_loader_philox_host(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4) {
+    if (!counter4 || !key2 || !out4) return fail(SNERF_E_INVALID, "snerf_loader_philox_host: NULL argument");
+    philox4x32_10(counter4, key2, out4);
     return SNERF_OK;
 }
 

@@ -191,6 +191,22 @@ hipError_t launch_surface_distance(int64_t n_rays, int S, const float* top, cons
                                    int dy, const double* levels, double* dist, hipStream_t st);
 hipError_t launch_image_error(int64_t n_pix, const float* img, const float* gt, double* sums, hipStream_t st);
 hipError_t launch_transmittance(int64_t n_rays, int S, const float* rho, const float* delta, float* pv, hipStream_t st);
+// loader.hip: one training batch drawn from the device-resident ray table; the position (epoch, batch) is read from d_state, not from an argument
+struct LoaderArgs {
+    const float* table;        // [n_rows, 22]
+    int64_t n_rows, batch;     // batch = B of the position formula p = ((batch_in_epoch * world) + rank) * B + i
+    int64_t rows;              // rows this launch writes (< batch only in a short last batch)
+    int64_t batches_per_epoch;
+    const int64_t* state;      // {epoch, batch_in_epoch, draws, reserved}
+    uint64_t seed;
+    int rank, world, bits;
+    float *img_pt, *top, *bot, *view, *sun, *time, *weight, *gt;     // each optional
+    int64_t* index;            // optional [rows]
+    float *sc_top, *sc_bot;    // optional [rows, 3]
+    float x0, dx, y0, dy, z_lo, z_hi;
+};
+hipError_t launch_loader_draw(const LoaderArgs& a, hipStream_t st);
+hipError_t launch_loader_advance(int64_t* state, int64_t batches_per_epoch, hipStream_t st);
 int mlp_lds_bytes(int bias_floats);
 int mlp_tile_points();
 int field_variant_chunks(int W, int C, int variant);

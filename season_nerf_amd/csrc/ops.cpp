@@ -36,6 +36,10 @@
 //   season_nerf::train_fwd_solar(trainer, top, bot, tvals, sun, train_bn, params[]) -> [solar_vis, pv, pe, sky_raw, rho, pts, delta]      eval_Rho_Only / forward_Solar
 //   season_nerf::train_bwd_solar(trainer, grads!, g_solar_vis) -> ()
 //   season_nerf::prior_density(pts[N,3], delta[N], height_map[h,w] f64, outside[N]?) -> rho_prior[N,1]                                    T_NeRF.Supervised_Sample
+// Device ray loader (csrc/loader.hip; `loader` = the snerf_loader handle a season_nerf_amd.loader.DeviceRayLoader owns):
+//   season_nerf::loader_next(loader, table[N,22], img_pt!?, top!?, bot!?, view_angle!?, sun_angle!?, time_encoded!?, sample_weight!?, gt_color!?, row_index!?,
+//        sc_top!?, sc_bot!?) -> ()        the next shuffled batch written into the given buffers ([>= batch, w] each, None = skip); the position lives in
+//        device memory behind the handle and advances per call - and per replay of a graph that captured the call            get_data, mg_run_NeRF.py:229-264
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm presents HIP devices under the "cuda" device type
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -626,6 +630,34 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> loss_terms_bwd(const Tensor& g_vals, 
     return {d_rgb, d_alb, d_sky, d_sv};
 }
 
+// ---- device ray loader: DataLoader(shuffle=True) + data_to_dict + SC_loader of mg_run_NeRF.py:74-84,122-133,229-264 as two kernel launches -----------
+void loader_next(int64_t loader, const Tensor& table, const c10::optional<Tensor>& img_pt, const c10::optional<Tensor>& top, const c10::optional<Tensor>& bot,
+                 const c10::optional<Tensor>& view, const c10::optional<Tensor>& sun, const c10::optional<Tensor>& time, const c10::optional<Tensor>& weight,
+                 const c10::optional<Tensor>& gt, const c10::optional<Tensor>& index, const c10::optional<Tensor>& sc_top, const c10::optional<Tensor>& sc_bot) {
+    snerf_loader* l = (snerf_loader*)loader;
+    TORCH_CHECK(l, "loader_next: NULL loader handle");
+    check_shape(table, "table", -1, 22);
+    const int64_t B = snerf_loader_batch(l);
+    auto out = [&](const c10::optional<Tensor>& t, const char* name, int64_t w) -> float* {
+        if (!t.has_value()) return nullptr;
+        check_dev_f32(*t, name);
+        TORCH_CHECK(t->device() == table.device() && t->dim() == 2 && t->size(0) >= B && t->size(1) == w, name, " must be [>= ", B, ", ", w, "] on the table's device, got ", t->sizes());
+        return t->data_ptr<float>();
+    };
+    snerf_loader_out o{};
+    o.d_img_pt = out(img_pt, "img_pt", 2); o.d_top = out(top, "top", 3); o.d_bot = out(bot, "bot", 3); o.d_view_angle = out(view, "view_angle", 3);
+    o.d_sun_angle = out(sun, "sun_angle", 3); o.d_time_encoded = out(time, "time_encoded", 4); o.d_sample_weight = out(weight, "sample_weight", 1);
+    o.d_gt_color = out(gt, "gt_color", 3); o.d_sc_top = out(sc_top, "sc_top", 3); o.d_sc_bot = out(sc_bot, "sc_bot", 3);
+    if (index.has_value()) {
+        TORCH_CHECK(index->is_cuda() && index->device() == table.device() && index->scalar_type() == at::kLong && index->is_contiguous() && index->dim() == 1 && index->size(0) >= B,
+                    "row_index must be a contiguous int64 [>= ", B, "] tensor on the table's device");
+        o.d_row_index = index->data_ptr<int64_t>();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA g(table.device());
+    const int64_t rows = snerf_loader_next(l, &o, cur_stream(table));
+    TORCH_CHECK(rows > 0, "season_nerf::loader_next failed (code ", rows, "): ", snerf_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(season_nerf, m) {
@@ -661,6 +693,8 @@ TORCH_LIBRARY(season_nerf, m) {
     m.def("trainer_adam_step_dev_(int trainer, Tensor(a!) params, Tensor grads, Tensor hyper) -> ()");
     m.def("trainer_zero_grad_(int trainer, Tensor(a!) grads) -> ()");
     m.def("loss_scratch_prepare(Tensor like) -> ()");
+    m.def("loader_next(int loader, Tensor table, Tensor(a!)? img_pt, Tensor(b!)? top, Tensor(c!)? bot, Tensor(d!)? view_angle, Tensor(e!)? sun_angle, "
+          "Tensor(f!)? time_encoded, Tensor(g!)? sample_weight, Tensor(h!)? gt_color, Tensor(i!)? row_index, Tensor(j!)? sc_top, Tensor(k!)? sc_bot) -> ()");
     m.def("loss_terms(Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor pe, Tensor? albedo_min_global, int world) "
           "-> (Tensor, Tensor)");
     m.def("loss_terms_bwd(Tensor g_vals, Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor min, int world) "
@@ -692,6 +726,7 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("trainer_adam_step_dev_", trainer_adam_step_dev_);
     m.impl("trainer_zero_grad_", trainer_zero_grad_);
     m.impl("loss_scratch_prepare", loss_scratch_prepare);
+    m.impl("loader_next", loader_next);
     m.impl("loss_terms", loss_terms);
     m.impl("loss_terms_bwd", loss_terms_bwd);
     m.impl("fused_adam_", fused_adam_);

@@ -7,8 +7,9 @@
                           schedule `ps = [0.2, 0, 0, 0.8]` (phase 1 = DSM-prior "jump start", phase 4 = free learning),
                           `reset_eval()` building a fresh evaluator / Adam x2 / OneCycle x2 at every phase entry, `step()`.
 
-What stays with the caller (out of scope): the DataLoaders of `Net_tool.__init__` (mg_run_NeRF.py:75-84 - pass
-`get_data`), TensorBoard (`writer` is anything with `add_scalar(tag, value, step)` or None), checkpoint files.
+The DataLoaders of `Net_tool.__init__` (mg_run_NeRF.py:75-84) are either the caller's (`get_data`) or `loader.DeviceRayLoader`s over device-resident ray
+tables (`train_loader` / `val_loader`).  What stays with the caller (out of scope): reading the reference's pickled loaders, TensorBoard
+(`writer` is anything with `add_scalar(tag, value, step)` or None), checkpoint files.
 Differences from the reference, all about not stalling the GPU: the network optimiser is `FusedAdam` by default (one kernel
 over the flat arena, one RCCL all-reduce when torch.distributed is initialised; the adaptive-loss gradients travel in a second
 small all-reduce), and the loss scalars are read back (`.item()`, a device sync per term in the reference) only every
@@ -160,14 +161,21 @@ class GraphedTrainStep:
         step = GraphedTrainStep(tool, example_batch)
         for k in range(n): loss = step(batch_k, k)          # loss: the step's LossDict (device tensors, not read back)
 
+    With `loader=` (a loader.DeviceRayLoader whose batches all have one size) the batch is drawn INSIDE the graph: the captured body begins with the loader's
+    two kernels, which read the position from device memory and advance it, so every replay trains on the next shuffled batch and the five per-step copies
+    into the fixed buffers disappear (the warm-up steps draw from the same loader, eagerly: the sequence of batches is the loader's, captured or not).
+
+        step = GraphedTrainStep(tool, loader=train_loader)
+        for k in range(n): loss = step(None, k)
+
     The LossDict a replayed step returns (and `tool.last_loss`) ALIASES the graph's static output: its tensors live in the graph's private
     pool and are overwritten by the next replay.  A caller that keeps losses across steps passes `keep=True` (one 5-float device copy per
     step, stream-ordered, no sync) or reads the value before the next call.
     """
 
     @staticmethod
-    def eligible(tool):
-        """None if `tool`'s current phase can run captured, else the reason it cannot."""
+    def eligible(tool, loader=None):
+        """None if `tool`'s current phase (drawing its batches from `loader` inside the graph, if given) can run captured, else the reason it cannot."""
         from . import parallel
         ev = tool.eval_tool
         a = ev.args
@@ -177,9 +185,11 @@ class GraphedTrainStep:
             return "the adaptive loss needs its parameters on the GPU and their optimiser (Net_tool.optim2)"
         if parallel.data_parallel():
             return "not under torch.distributed (the data-parallel exchanges are issued from Python)"
+        if loader is not None and not loader.graph_safe:
+            return "the loader's last batch of an epoch is short (a replay cannot change its ray count): build it with drop_last=True"
         return None
 
-    def __init__(self, tool, data_dict, warmup=3, keep=False, check_every=64):
+    def __init__(self, tool, data_dict=None, warmup=3, keep=False, check_every=64, loader=None):
         from . import training
         # check_every: every that many replays the parameters, Adam's moments and (adaptive loss) the loss object's parameters and moments are tested for
         # non-finite values ON THE DEVICE (one reduction, its flag copied to pinned memory without a sync and read one period later).  A hit disables the graph:
@@ -192,14 +202,23 @@ class GraphedTrainStep:
         self.keep = bool(keep)
         ev, net = tool.eval_tool, tool.network
         a = ev.args
-        why = self.eligible(tool)
+        why = self.eligible(tool, loader)
         if why:
             raise ValueError("GraphedTrainStep: " + why)
-        self.tool, self.ev, self.net, self._training = tool, ev, net, training
+        if (data_dict is None) == (loader is None):
+            raise ValueError("GraphedTrainStep: pass exactly one of an example batch and loader=")
+        self.tool, self.ev, self.net, self._training, self.loader = tool, ev, net, training, loader
         self.dev = dev = ev.device
-        self.R, self.S = data_dict["Top"].shape[0], a.n_samples
         e = lambda *sh: torch.empty(*sh, device=dev)
-        self.data = {k: e(*data_dict[k].shape) for k in ("Top", "Bot", "Sun_Angle", "Time_Encoded", "GT_Color")}
+        if loader is not None:
+            from .loader import FIELDS
+            self.R, self.S = loader.batch_size, a.n_samples
+            self.data = {k: e(self.R, FIELDS[k][1]) for k in ("Top", "Bot", "Sun_Angle", "Time_Encoded", "GT_Color")}
+            # what the draw writes: the fields get_loss reads + the random sun-check rays of the reference's data_dict (mg_run_NeRF.py:250)
+            self.drawn = dict(self.data, SC_Top=e(self.R, 3), SC_Bot=e(self.R, 3))
+        else:
+            self.R, self.S = data_dict["Top"].shape[0], a.n_samples
+            self.data = {k: e(*data_dict[k].shape) for k in ("Top", "Bot", "Sun_Angle", "Time_Encoded", "GT_Color")}
         self.tv = {"tv_image": e(self.S), "tv_solar": e(self.S), "trust": e(1) if ev.use_prior else None}
         self.sol = (e(self.R, 3), e(self.R, 3), e(self.R, 3), e(self.R, 4))
         self._gen = ev.solar_creation_tool
@@ -211,8 +230,9 @@ class GraphedTrainStep:
         through the pinned ring and is dealt out to the fixed buffers by one multi-tensor copy kernel: eight uploads, each with a device-to-device copy behind
         it and each waiting for the one before it, cost the GPU ~0.4 ms between two replays (tools/graph_replay_probe.py)."""
         tr = self._training
-        for k, dst in self.data.items():
-            dst.copy_(tr._to_dev(data_dict[k], self.dev))
+        if self.loader is None:                          # (with a loader the graph's first two kernels fill self.data)
+            for k, dst in self.data.items():
+                dst.copy_(tr._to_dev(data_dict[k], self.dev))
         tvi = tr.sample_parameters(self.S, eval_mode=False)
         st, en, vec, stime, _ = self._gen(self.R, include_times=True)
         tvs = tr.sample_parameters(self.S, eval_mode=False, include_end_pt=True)
@@ -234,6 +254,8 @@ class GraphedTrainStep:
 
     def _body(self):
         tool, ev = self.tool, self.ev
+        if self.loader is not None:
+            self.loader.next_into(self.drawn)          # two kernel nodes: the position is read from, and advanced in, device memory
         tool.optim.zero_grad()
         if tool.optim2 is not None:
             # in place: the gradients of the loss object's parameters exist since the eager warm-up steps and keep their addresses - the capture allocates
@@ -345,6 +367,8 @@ class GraphedTrainStep:
 
     def __call__(self, data_dict, current_step=0):
         tool = self.tool
+        if self.loader is not None and (self.disabled or self.calls < self.warmup):
+            data_dict = self.loader.next()             # the eager steps take the loader's next batch, as a replay does
         if self.disabled:
             return tool.train_step(data_dict, current_step)
         if self.calls < self.warmup:                   # eager steps first: the engine, its scratch and every cached constant exist before the capture
@@ -357,7 +381,7 @@ class GraphedTrainStep:
                 # graph dies here and the captured backward creates its accumulators on the capture stream.
                 loss = tool.last_loss = {k: [v[0].detach() if torch.is_tensor(v[0]) else v[0], v[1]] for k, v in loss.items()}
             return loss
-        if data_dict["Top"].shape[0] != self.R:
+        if self.loader is None and data_dict["Top"].shape[0] != self.R:
             raise ValueError(f"GraphedTrainStep: captured for {self.R} rays, got {data_dict['Top'].shape[0]}")
         first = self.graph is None
         self._load(data_dict, current_step, with_hyper=not first)
@@ -399,11 +423,13 @@ class T_NeRF_Net_Tool(Net_tool):
     `args` fields read: max_train_steps, n_saves, fc_units, number_low_frequency_cases, lr, lr_alpha_scale, jump_start,
     Use_MSE_loss, batch_size, n_samples (+ what `All_in_One_Eval` reads).  Keyword-only extras replace what the reference's
     base class builds from files: `get_data(eval_mode) -> data_dict` (the DataLoader pair of mg_run_NeRF.py:75-84 and
-    `get_data`, :228-262), `solar_vecs` (`train_data["Color_Loader"].solar_vecs`), `writer`, `eval_img(step)`.
+    `get_data`, :228-262), `solar_vecs` (`train_data["Color_Loader"].solar_vecs`), `writer`, `eval_img(step)`.  Without a `get_data` callable the batches come from
+    `train_loader` / `val_loader` (loader.DeviceRayLoader: shuffled batches drawn on the device; `solar_vecs` then defaults to the training loader's), and with
+    `use_graph` the training draw happens inside the captured step (GraphedTrainStep(tool, loader=...)).
     """
 
     def __init__(self, args, training_DSM, GT_DSM, device, H, WC, *, get_data=None, solar_vecs=None, writer=None, eval_img=None,
-                 fused_adam=True, log_every=1, ada_factory=None, use_graph=False):
+                 fused_adam=True, log_every=1, ada_factory=None, use_graph=False, train_loader=None, val_loader=None):
         from .network import T_NeRF
         self.args, self.device = args, torch.device(device)
         self.writer, self.log_every, self.fused_adam = writer, max(int(log_every), 1), fused_adam
@@ -413,6 +439,9 @@ class T_NeRF_Net_Tool(Net_tool):
         self._step_count = 0
         self.use_graph, self._graphed = bool(use_graph), None      # use_graph: phases that allow it run as one hipGraph launch per step (GraphedTrainStep)
         self._get_data, self._eval_img, self.solar_vecs = get_data, eval_img, solar_vecs
+        self.train_loader, self.val_loader = train_loader, val_loader
+        if solar_vecs is None and train_loader is not None:
+            self.solar_vecs = train_loader.solar_vecs
         # Learning phases (Net_Tool_2.py:23-54): fractions of the run spent in phase 1 (DSM-prior "jump start"), 2, 3 and - the
         # remainder - 4 (free learning); phases 2 and 3 are empty in the reference's schedule.  Attribute names are the reference's
         # (step() and outside code read them).
@@ -472,10 +501,13 @@ class T_NeRF_Net_Tool(Net_tool):
         self._graphed = None                   # a new evaluator and new optimisers: a captured step of the previous phase is stale
 
     def get_data(self, eval_mode=False):
-        if self._get_data is None:
-            raise NotImplementedError("T_NeRF_Net_Tool: pass get_data=callable(eval_mode) -> data_dict; the reference's DataLoaders "
-                                      "(mg_run_NeRF.py:75-84) are outside the hot path (SURVEY 8)")
-        return self._get_data(eval_mode)
+        if self._get_data is not None:
+            return self._get_data(eval_mode)
+        loader = self.val_loader if eval_mode else self.train_loader
+        if loader is None:
+            raise NotImplementedError("T_NeRF_Net_Tool: pass get_data=callable(eval_mode) -> data_dict, or train_loader= / val_loader= (loader.DeviceRayLoader); "
+                                      "the reference's DataLoaders (mg_run_NeRF.py:75-84) are not rebuilt from its files (SURVEY 8)")
+        return loader.next()
 
     def step(self):
         """Net_Tool_2.py:134-145."""
@@ -484,13 +516,20 @@ class T_NeRF_Net_Tool(Net_tool):
             self.learning_mode = mode
             self.reset_eval()
         self.network.train()
-        data = self.get_data(eval_mode=False)
-        if self.use_graph and GraphedTrainStep.eligible(self) is None:
-            if self._graphed is None or self._graphed.R != data["Top"].shape[0]:
-                self._graphed = GraphedTrainStep(self, data, warmup=2)
-            self._graphed(data, self._step_count)
+        loader = self.train_loader if self._get_data is None else None
+        graph = self.use_graph and GraphedTrainStep.eligible(self, loader) is None
+        if graph and loader is not None:               # the batch is drawn inside the captured step: nothing to fetch here
+            if self._graphed is None:
+                self._graphed = GraphedTrainStep(self, loader=loader, warmup=2)
+            self._graphed(None, self._step_count)
         else:
-            self.train_step(data, self._step_count)
+            data = self.get_data(eval_mode=False)
+            if graph:
+                if self._graphed is None or self._graphed.R != data["Top"].shape[0]:
+                    self._graphed = GraphedTrainStep(self, data, warmup=2)
+                self._graphed(data, self._step_count)
+            else:
+                self.train_step(data, self._step_count)
         self._step_count += 1
         if self._step_count in self.sub_section_outputs[mode - 1]:
             self.eval_step(self.get_data(eval_mode=True), self._step_count - 1)
