@@ -32,28 +32,13 @@ namespace snerf {
 constexpr int AG_R0 = 0, AG_R1 = 128;      // two 128-register regions; who lives where: see the layer list of the kernel
 // register numbers are "i" operands: loop indices that are constants once the layer is unrolled (a number that did not fold
 // fails the build in the backend, it cannot reach the GPU)
-#ifdef SNERF_DBG_NOP_PARK
-#define DBG_PARK_PAD "\n\ts_nop 7"
-#else
-#define DBG_PARK_PAD ""
-#endif
-#ifdef SNERF_DBG_NOP_MFMA
-#define DBG_MFMA_PAD "\n\ts_nop 15\n\ts_nop 15"
-#else
-#define DBG_MFMA_PAD ""
-#endif
-#ifdef SNERF_DBG_EARLYCLOBBER
-#define DBG_EC "=&v"
-#else
-#define DBG_EC "=v"
-#endif
 static __device__ __forceinline__ void park(int v, int idx) {
-    asm volatile("v_accvgpr_write_b32 a[%1], %0" DBG_PARK_PAD ::"v"(v), "i"(idx));
+    asm volatile("v_accvgpr_write_b32 a[%1], %0" ::"v"(v), "i"(idx));
 }
 template <bool FIRST>
 __device__ __forceinline__ void mfma_asm(i32x16& acc, const i32x4& a, int base) {
-    if (FIRST) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, a[%2:%3], 0" DBG_MFMA_PAD : DBG_EC(acc) : "v"(a), "i"(base), "i"(base + 3));
-    else asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, a[%2:%3], %0" DBG_MFMA_PAD : "+v"(acc) : "v"(a), "i"(base), "i"(base + 3));
+    if (FIRST) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, a[%2:%3], 0" : "=v"(acc) : "v"(a), "i"(base), "i"(base + 3));
+    else asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, a[%2:%3], %0" : "+v"(acc) : "v"(a), "i"(base), "i"(base + 3));
 }
 template <bool FIRST>      // base: first register of the k-step (4 high-digit dwords, then 4 low-digit dwords)
 __device__ __forceinline__ void mfma_i8x3_agpr(const i32x4& aT, const i32x4& aL, Acc8& acc, int base) {
@@ -267,55 +252,36 @@ __global__ __launch_bounds__(256, 1) void mlp_i8_kernel(const MlpArgs A) {
         // of R1; the adjust branch starts from x1 (R0) into R1, so its ping-pong is R1 / R0 / R1.  The Frag8 arrays below
         // are the same buffers for the widths whose activations stay in compiler-allocated VGPRs.
         constexpr bool AG = W > 256;
-        constexpr int xA = AG_R0, xB = AG_R1, xX1 = AG_R0, xSA = AG_R1, xSB = AG_R1 + 64, NOAG = -1;
+        // A buffer's AGPR base by its name (-1: an encoding, or no digit output); the Frag8 array of that name is unused at W = 512.
+        constexpr int ag_hA = AG_R0, ag_hB = AG_R1, ag_x1f = AG_R0, ag_sA = AG_R1, ag_sB = AG_R1 + 64, ag_pe = -1, ag_ps = -1, ag_nullptr = -1;
         if constexpr (AG) reserve_agprs();
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN0AG, IN1, OUT, OUTAG, RAW)                                                      \
-    run_layer8<NBv, K0, K1, SINv, D, AG ? IN0AG : -1, AG ? OUTAG : -1, AG, false, VARIANT == 3>(rg, A.stream, A.stream_bytes, lds, \
-        tab_lds + prog_table_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane)
-#define LAYER_RAW(L, NBv, K0, K1, IN0, IN0AG, IN1, OUT, OUTAG, RX)                                                         \
-    run_layer8<NBv, K0, K1, true, D, AG ? IN0AG : -1, AG ? OUTAG : -1, AG, true, VARIANT == 3>(rg, A.stream, A.stream_bytes, lds, \
-        tab_lds + prog_table_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, nullptr, wave, lane, RX)
+        // the lists of mlp_i8_device.h; one wave per SIMD carries nothing across a layer boundary (PO, PR, PX unused)
+#define SHAPE(L) field_layer(W, C_MAX, L, FMT_I8)
+#define LAYER(L, IN0, IN1, OUT, RAW, RX, PO, PR, PX)                                                                                           \
+    run_layer8<SHAPE(L).nb(), SHAPE(L).ks0, SHAPE(L).ks1, layer_sine(SHAPE(L)), D, AG ? ag_##IN0 : -1, AG ? ag_##OUT : -1, AG, layer_reads_raw(SHAPE(L)),  \
+               VARIANT == 3>(rg, A.stream, A.stream_bytes, lds, tab_lds + prog_table_start(PROG_FIELD, W, C_MAX, L), IN0, IN1, OUT, RAW, wave, lane, RX)
         const float rx_p[3] = {x0, x1, x2}, rx_s[3] = {s0, s1, s2};      // raw coordinates: fp32, no digit range
-        // trunk (G_NeRF.py:80-91)
-        LAYER_RAW(F_FC1, W / 32, PEPOS_KS8, 0, pe, NOAG, nullptr, hA, xA, rx_p);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, xA, nullptr, hB, xB, nullptr);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, xB, nullptr, hA, xA, nullptr);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, xA, nullptr, hB, xB, nullptr);
-        LAYER_RAW(F_FC5, W / 32, KW, PEPOS_KS8, hB, xB, pe, hA, xA, rx_p);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, xA, nullptr, hB, xB, nullptr);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, xB, nullptr, hA, xA, nullptr);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, xA, nullptr, hB, xB, nullptr);
         Frag8 x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, xB, nullptr, x1f, xX1, nullptr);
-        // sigma / colour head (G_NeRF.py:93-98): regs 0..2 colour, 3 density (lane-half 0)
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, xX1, nullptr, nullptr, NOAG, &raw);
+        I8_TRUNK(LAYER, pe, hA, hB, x1f, &raw, rx_p);
         const float col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         float sv_raw = 0.f;
         float adj[3 * C_MAX];
 #pragma unroll
         for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = 0.f;
         if constexpr (VARIANT <= 1) {
-            // solar visibility branch (G_NeRF.py:100-108)
             Frag8 ps[PESUN_KS8];
             make_pe_sun8(s0, s1, s2, h, ps);
             Frag8 sA[KW2], sB[KW2];
-            LAYER_RAW(F_S1, W2 / 32, KW2, PESUN_KS8, x1f, xX1, ps, sA, xSA, rx_s);
-            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, xSA, nullptr, sB, xSB, nullptr);
-            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, xSB, nullptr, sA, xSA, nullptr);
-            LAYER(F_S4, 1, KW2, 0, false, sA, xSA, nullptr, nullptr, NOAG, &raw);
+            I8_SOLAR(LAYER, x1f, ps, sA, sB, &raw, rx_s);
             sv_raw = raw[0];
         }
         if constexpr (VARIANT == 0) {
-            // seasonal colour-adjust branch (T_NeRF_net_v2.py:83-87)
-            LAYER(F_A1, W / 32, KW2, 0, true, x1f, xX1, nullptr, hB, xB, nullptr);
-            LAYER(F_A2, W / 32, KW, 0, true, hB, xB, nullptr, hA, xA, nullptr);
-            LAYER(F_A3, W / 32, KW, 0, true, hA, xA, nullptr, hB, xB, nullptr);
-            LAYER(F_AC, 1, KW, 0, false, hB, xB, nullptr, nullptr, NOAG, &raw);
+            I8_ADJUST(LAYER, x1f, hB, hA, &raw);      // from x1 (R0) into R1: the ping-pong is hB, hA, hB
 #pragma unroll
             for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
         }
 #undef LAYER
-#undef LAYER_RAW
+#undef SHAPE
         if constexpr (VARIANT == 3) {
             RAYSUM_PASS_END(rs, A, tile, pass, passes, 4, wave, wave, 4, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
         } else {

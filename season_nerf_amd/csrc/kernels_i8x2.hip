@@ -8,14 +8,15 @@
 //     * no software-pipelined epilogue and no accumulator ping-pong (that is what the registers went to): a block is
 //       24 MFMAs with the next fragments prefetched, then its epilogue (sine + digit split) in two halves;
 //     * ring protocol as in the one-wave kernels (mlp_device.h): one counted vmcnt wait + one workgroup barrier per 16 KiB chunk,
-//       now shared by eight waves - each moves two of the chunk's sixteen 1 KiB pieces - so the L2 -> LDS weight traffic per
-//       point halves.
+//       now shared by eight waves, so the L2 -> LDS weight traffic per point halves.  Waves 0-3 (which reach every barrier early, see
+//       run_layer8x2) move the chunk's sixteen 1 KiB pieces, four each; waves 4-7 only take the barrier (all eight moving two pieces each measured
+//       slower: DESIGN 5.1b).
 //  Measured (profiles/r2): 0.74 ms against 0.82 ms for the one-wave kernel.  The matrix pipe is busy 59 % of the time: the two
 //  waves of a SIMD run in step (the per-chunk barrier re-aligns all eight every block), so the pipe saturates while both are
 //  in their MFMA phase and idles while both run epilogues.  Tried against that, each without gain: waves 4-7 taking every
 //  barrier half a chunk later in their own stream (a protocol in which barrier m publishes chunk m + 1), s_setprio 2 / 3 for
-//  the MFMA phase, fragment prefetch depth 1 / 3, MFMA / VALU interleave pinned inside a k-step (sched_group_barrier, the
-//  SNERF_X2_GROUPS switch below), waves 4-7 running their epilogue slices in the odd k-steps and waves 0-3 in the even ones.
+//  the MFMA phase, fragment prefetch depth 1 / 3, MFMA / VALU interleave pinned inside a k-step (sched_group_barrier),
+//  waves 4-7 running their epilogue slices in the odd k-steps and waves 0-3 in the even ones.
 //  So the two waves running in step is not what leaves the matrix pipe 40 % idle; the chip holds 1.8 GHz in this kernel.
 //  Weight stream, tables, digit formats, accuracy: exactly those of kernels_i8.hip (same packed model, bit-identical results).
 //  At W = 256 the kernel runs the same digits on v_mfma_i32_16x16x64_i8 from a stream of its own (run_layer16, field_tiles16 below; program.h "k64"):
@@ -29,25 +30,10 @@ namespace snerf {
 
 constexpr int NW2 = 8;                                      // waves per workgroup: two per SIMD
 constexpr int TILE2 = 32 * NW2;                             // 256 points per workgroup tile
-constexpr int PIECES2 = kChunkBytes / kFragBytes / NW2;     // 1 KiB DMA pieces per wave and chunk (2)
+constexpr int DMA_WAVES2 = 4, PIECES4 = kChunkBytes / kFragBytes / DMA_WAVES2;      // waves 0-3 move a chunk, four 1 KiB pieces each
 constexpr int RING2_D = 7;
-#ifndef SNERF_PFX
-#define SNERF_PFX 2
-#endif
-constexpr int PFX = SNERF_PFX;                                // weight-fragment pairs requested ahead of their MFMAs
-static_assert(PIECES2 == 2 && kChunkPairs == 8, "the DMA below moves two pieces per wave; barrier positions assume 8-pair chunks");
-
-#ifdef SNERF_STAMP
-// Diagnostic build only (tools/variants.py ... -DSNERF_STAMP): cycle stamps of workgroup 0, second tile: per layer the s_memtime
-// at entry, and per wave the cycles spent inside ring_step2 (vmcnt wait + barrier).  Read back with snerf_debug_stamps().
-__device__ unsigned long long g_stamps[8 * 64];
-__device__ __forceinline__ void stamp(int wave, int lane, int slot, bool on) {
-    if (on && lane == 0) g_stamps[wave * 64 + slot] = __builtin_amdgcn_s_memtime();
-}
-#define STAMP(slot) stamp(wave, lane, slot, stamp_on)
-#else
-#define STAMP(slot)
-#endif
+constexpr int PFX = 2;                                      // weight-fragment pairs requested ahead of their MFMAs
+static_assert(PIECES4 == 4 && kChunkPairs == 8, "dma_chunk4 moves four pieces per loading wave; barrier positions assume 8-pair chunks");
 
 struct Ring2 {
     uint32_t wr;       // LDS offset of the slot the next DMA fills
@@ -58,66 +44,7 @@ __device__ __forceinline__ uint32_t ring2_next(uint32_t off) {
     off += kChunkBytes;
     return off == RING2_D * kChunkBytes ? 0u : off;
 }
-__device__ __forceinline__ void dma_chunk2(const uint8_t* stream, uint32_t goff, lds_char* lds, uint32_t wr, int wave, int lane);
-__device__ __forceinline__ void dma_chunk4(const uint8_t* stream, uint32_t goff, lds_char* lds, uint32_t wr, int wave, int lane);
-#ifndef SNERF_X2_ALL_LOAD
-#define SNERF_X2_OLD_LOADS 1      // waves 0-3 (which reach every barrier early, see run_layer8x2) move all sixteen pieces of a chunk
-#endif
-// Hand the next chunk to the consumers and refill the slot released two chunks ago (ring_step of mlp_device.h for eight waves):
-// vmcnt((D-3)*2): all but the (D-3) youngest chunks this wave fetched have landed => the chunk about to be read is complete.
-template <int PHASE>
-__device__ __forceinline__ void ring_step2(Ring2& rg, const uint8_t* stream, uint32_t stream_bytes, lds_char* lds, int wave, int lane) {
-#if defined(SNERF_ABLATE) && (ABL & 4)     // timing-only: no ring at all
-    return;
-#endif
-#if defined(SNERF_X2_OLD_LOADS) && !defined(SNERF_STAMP)
-    if (PHASE == 0) {
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((RING2_D - 3) * 4) : "memory");
-        dma_chunk4(stream, rg.goff, lds, rg.wr, wave, lane);
-    } else {
-        asm volatile("s_barrier" ::: "memory");      // the loading waves waited for their pieces before they arrived here
-    }
-    rg.goff += kChunkBytes;
-    if (rg.goff >= stream_bytes) rg.goff = 0;
-    rg.wr = ring2_next(rg.wr);
-    return;
-#endif
-#ifdef SNERF_STAMP
-    const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RING2_D - 3) * PIECES2) : "memory");
-    const unsigned long long t1_ = __builtin_amdgcn_s_memtime();
-    asm volatile("s_barrier" ::: "memory");
-    const unsigned long long t2_ = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && lane == 0) { g_stamps[wave * 64 + 62] += t1_ - t0_; g_stamps[wave * 64 + 63] += t2_ - t1_; }
-#else
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((RING2_D - 3) * PIECES2) : "memory");
-#endif
-    dma_chunk2(stream, rg.goff, lds, rg.wr, wave, lane);
-    rg.goff += kChunkBytes;
-    if (rg.goff >= stream_bytes) rg.goff = 0;
-    rg.wr = ring2_next(rg.wr);
-}
-// wave w moves pieces 2w and 2w + 1 of the chunk (see dma_chunk in mlp_device.h for why this is inline asm)
-__device__ __forceinline__ void dma_chunk2(const uint8_t* stream, uint32_t goff, lds_char* lds, uint32_t wr, int wave, int lane) {
-    const uint8_t* b0 = stream + goff + wave * (PIECES2 * kFragBytes);
-    const uint32_t dst = (uint32_t)(uintptr_t)(lds + wr + wave * (PIECES2 * kFragBytes));
-    const uint32_t voff = lane * 16;
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %3\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %4\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(dst), "s"(b0), "s"(b0 + kFragBytes)
-        : "memory", "scc");
-}
-
-// wave w (0..3) moves pieces 4w .. 4w+3
+// wave w (0..3) moves pieces 4w .. 4w+3 of the chunk (see dma_chunk in mlp_device.h for why this is inline asm)
 __device__ __forceinline__ void dma_chunk4(const uint8_t* stream, uint32_t goff, lds_char* lds, uint32_t wr, int wave, int lane) {
     const uint8_t* b0 = stream + goff + wave * (4 * kFragBytes);
     const uint32_t dst = (uint32_t)(uintptr_t)(lds + wr + wave * (4 * kFragBytes));
@@ -141,6 +68,25 @@ __device__ __forceinline__ void dma_chunk4(const uint8_t* stream, uint32_t goff,
         : "=&s"(keep)
         : "v"(voff), "s"(dst), "s"(b0), "s"(b0 + kFragBytes), "s"(b0 + 2 * kFragBytes), "s"(b0 + 3 * kFragBytes)
         : "memory", "scc");
+}
+
+// Hand the next chunk to the consumers and refill the slot released two chunks ago (ring_step of mlp_device.h for eight waves).  PHASE 0, the loading
+// waves: vmcnt((D-3)*4): all but the (D-3) youngest chunks this wave fetched have landed, and so have the other loading waves' pieces once all have
+// passed the barrier => the chunk about to be read is complete.  PHASE 1 only takes the barrier.
+template <int PHASE>
+__device__ __forceinline__ void ring_step2(Ring2& rg, const uint8_t* stream, uint32_t stream_bytes, lds_char* lds, int wave, int lane) {
+#if defined(SNERF_ABLATE) && (ABL & 4)     // timing-only: no ring at all
+    return;
+#endif
+    if (PHASE == 0) {
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((RING2_D - 3) * PIECES4) : "memory");
+        dma_chunk4(stream, rg.goff, lds, rg.wr, wave, lane);
+    } else {
+        asm volatile("s_barrier" ::: "memory");      // the loading waves waited for their pieces before they arrived here
+    }
+    rg.goff += kChunkBytes;
+    if (rg.goff >= stream_bytes) rg.goff = 0;
+    rg.wr = ring2_next(rg.wr);
 }
 
 // per-row scale and bias of accumulator elements 4g .. 4g+3 of block b (table layout: [16 scales | 16 biases] per block and lane-half)
@@ -234,6 +180,8 @@ __device__ __forceinline__ void epi_quad(const int* m, int g, const TabQ& t, con
 // The field chain's boundaries (field_tiles2).  A layer's output is its successor's first input everywhere but behind the two one-block
 // raw heads: fc_solar_1 reads x1f, not the colour / density head, and adjust_layer_1 reads x1f, not fc_solar_4.
 __host__ __device__ constexpr bool field_feeds_next(int l) { return l != F_HEAD && l != F_S4; }
+// every variant runs a prefix of the enum order (program.h field_variant_layers): the layer in front of L in the chain is L - 1, also across the two heads
+static_assert(F_S1 == F_HEAD + 1 && F_A1 == F_S4 + 1 && F_FC1 == 0, "the kernels' LAYER macros build the carry of layer L from layer L - 1");
 // the last layer of a variant's chain: the tile's outputs are read right behind it
 __host__ __device__ constexpr int field_last(int variant) { return variant == 0 ? F_AC : variant == 1 ? F_S4 : F_HEAD; }
 // One flag per boundary and instantiation: does layer l hand its last block to the next layer?  Not the last layer of a variant (the tile's
@@ -241,11 +189,46 @@ __host__ __device__ constexpr int field_last(int variant) { return variant == 0 
 // (256 registers, no scratch: tests/test_isa_guards.py): a boundary that costs an instantiation a register is switched off HERE and
 // stays exposed as before.
 __host__ __device__ constexpr bool field_carries(int W, int variant, int C, int l) {
-#ifdef SNERF_X2_NO_CARRY      // A/B: every boundary exposed (the kernel before the carry)
-    return false;
-#endif
     return l != field_last(variant) && carry_fits(prog_layer(PROG_FIELD, W, C, l, FMT_I8).n_out / 32, field_feeds_next(l));
 }
+
+// The weight pipeline of a layer (run_layer8x2, run_layer16), in terms of the layer's rg, stream, stream_bytes, lds, wave, lane, PHASE and its fragment
+// slots fT, fL.  REQUEST: pair QN of the layer into slot SLOT; the first pair of a chunk takes the ring step.
+#if defined(SNERF_ABLATE) && (ABL & 2)     // timing-only: weight fragments stay in registers, no LDS reads
+constexpr bool kNoFragReads = true;
+#else
+constexpr bool kNoFragReads = false;
+#endif
+#define REQUEST(QN, SLOT)                                                                              \
+    do {                                                                                               \
+        if ((QN) % kChunkPairs == 0) {                                                                 \
+            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                              \
+            if ((QN) > 0) rg.cur = ring2_next(rg.cur);                                                 \
+        }                                                                                              \
+        lds_char* ap_ = lds + rg.cur + ((QN) % kChunkPairs) * kPairBytes + lane * 16;                  \
+        if (!kNoFragReads) {                                                                           \
+            fT[SLOT] = *(lds_ci32x4*)ap_;                                                              \
+            fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                               \
+        } else {                                                                                       \
+            asm volatile("" : "+v"(fT[SLOT]), "+v"(fL[SLOT]));                                         \
+        }                                                                                              \
+    } while (0)
+// pair J (< PFX) of the NEXT layer, which starts on the next chunk: the weight pipeline runs on across the boundary, so the chunk rendezvous
+// and the LDS latency of a layer's first fragments hide behind the last k-steps of the layer before (PRE_OUT there, PRE_IN here)
+#define REQUEST_NEXT(J, SLOT)                                                                          \
+    do {                                                                                               \
+        if ((J) == 0) {                                                                                \
+            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                              \
+            rg.cur = ring2_next(rg.cur);                                                               \
+        }                                                                                              \
+        lds_char* ap_ = lds + rg.cur + (J) * kPairBytes + lane * 16;                                   \
+        if (!kNoFragReads) {                                                                           \
+            fT[SLOT] = *(lds_ci32x4*)ap_;                                                              \
+            fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                               \
+        } else {                                                                                       \
+            asm volatile("" : "+v"(fT[SLOT]), "+v"(fL[SLOT]));                                         \
+        }                                                                                              \
+    } while (0)
 
 // One fused layer (see run_layer8 in kernels_i8.hip for the arithmetic).  Chunk boundaries of the read sequence are compile-time
 // positions; every layer starts on one.  The whole layer is ONE basic block for the compiler (no branch): with branches inside
@@ -253,7 +236,7 @@ __host__ __device__ constexpr bool field_carries(int W, int variant, int C, int 
 //   RAWL: the layer reads an encoding; rawx = its three raw coordinates, added in fp32 (table behind the scale / bias table).
 //   PHASE (0 / 1) = the wave group (waves 0-3 / 4-7: waves w and w + 4 share a SIMD).  The matrix pipe is arbitrated by age: left
 //   alone, the older wave of a SIMD takes every MFMA slot it wants, reaches the chunk barrier early and waits there for the
-//   younger one (in-kernel stamps, -DSNERF_STAMP: wave 0 spent 30 % of the launch inside s_barrier, wave 4 3 %).  So the
+//   younger one (in-kernel cycle stamps, DESIGN 5.1b: wave 0 spent 30 % of the launch inside s_barrier, wave 4 3 %).  So the
 //   priority alternates per k-step (s_setprio 3 in the k-steps of one's own parity, 0 in the others): wave 0's barrier time
 //   drops to 13 %, the kernel gains 2.5 %.  Tried on top without gain: the epilogue slices in the k-steps where a wave yields,
 //   biased levels ({0,2} against {1,3}: the younger wave then takes the older one's place), alternating the tie-break per
@@ -271,11 +254,7 @@ template <int NB, int KS0, int KS1, bool SIN, bool RAWL = false, int PHASE = 0, 
           bool PRE_OUT = false>
 __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, uint32_t stream_bytes, lds_char* lds, lds_cfloat* tab0, lds_cfloat* tab_l,
                                              const Frag8* in0, const Frag8* in1, Frag8* out, f32x16* raw, Boundary& bd, const CarryDst& pd,
-                                             int wave, int lane, const float* rawx = nullptr
-#ifdef SNERF_STAMP
-                                             , bool stamp_on = false, int stamp_slot = 0
-#endif
-) {
+                                             int wave, int lane, const float* rawx = nullptr) {
     constexpr int KS = KS0 + KS1, NP = NB * KS;
     constexpr int NBP = PEND::NB;
     static_assert(!PRE_OUT || (NP >= PFX && NP % PFX == 0), "the successor expects its pair j in fragment slot j");
@@ -307,43 +286,10 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
     lds_cfloat* ptab_h = base_h;
     auto tabq = [&](int b_, int g_) { return OPQ ? load_tab_quad_h(tab_h, b_, g_) : load_tab_quad(tab_l, b_, h, g_); };
     auto ptabq = [&](int g_) { return OPQ ? load_tab_quad_h(ptab_h, NBP - 1, g_) : load_tab_quad(ptab_l, NBP - 1, h, g_); };
-#if defined(SNERF_ABLATE) && (ABL & 2)     // timing-only: weight fragments stay in registers, no LDS reads
-    constexpr bool ABL2_ = true;
+    if constexpr (kNoFragReads) {
 #pragma unroll
-    for (int q = 0; q < PFX; ++q) { fT[q] = i32x4{lane, 1, 2, 3}; fL[q] = i32x4{4, lane, 6, 7}; }
-#else
-    constexpr bool ABL2_ = false;
-#endif
-#define REQUEST(QN, SLOT)                                                                              \
-    do {                                                                                               \
-        if ((QN) % kChunkPairs == 0) {                                                                 \
-            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                                \
-            if ((QN) > 0) rg.cur = ring2_next(rg.cur);                                                 \
-        }                                                                                              \
-        lds_char* ap_ = lds + rg.cur + ((QN) % kChunkPairs) * kPairBytes + lane * 16;                  \
-        if (!ABL2_) {                                                                                  \
-            fT[SLOT] = *(lds_ci32x4*)ap_;                                                              \
-            fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                               \
-        } else {                                                                                       \
-            asm volatile("" : "+v"(fT[SLOT]), "+v"(fL[SLOT]));                                         \
-        }                                                                                              \
-    } while (0)
-    // pair J (< PFX) of the NEXT layer, which starts on the next chunk: the weight pipeline runs on across the boundary, so the chunk rendezvous
-    // and the LDS latency of a layer's first fragments hide behind the last k-steps of the layer before (PRE_OUT there, PRE_IN here)
-#define REQUEST_NEXT(J, SLOT)                                                                          \
-    do {                                                                                               \
-        if ((J) == 0) {                                                                                \
-            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                                \
-            rg.cur = ring2_next(rg.cur);                                                               \
-        }                                                                                              \
-        lds_char* ap_ = lds + rg.cur + (J) * kPairBytes + lane * 16;                                   \
-        if (!ABL2_) {                                                                                  \
-            fT[SLOT] = *(lds_ci32x4*)ap_;                                                              \
-            fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                               \
-        } else {                                                                                       \
-            asm volatile("" : "+v"(fT[SLOT]), "+v"(fL[SLOT]));                                         \
-        }                                                                                              \
-    } while (0)
+        for (int q = 0; q < PFX; ++q) { fT[q] = i32x4{lane, 1, 2, 3}; fL[q] = i32x4{4, lane, 6, 7}; }
+    }
     if constexpr (!PRE_IN) {
 #pragma unroll
         for (int q = 0; q < PFX; ++q) {
@@ -395,10 +341,8 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
         for (int s = 0; s < KS; ++s) {
             const int q = b * KS + s;
             const i32x4 aT = fT[q % PFX], aL = fL[q % PFX];
-#ifndef SNERF_X2_NOPRIO
             // own parity: this wave's MFMAs first (it runs no epilogue slice in this k-step); else yield to the partner
             if (((s + PHASE) & 1) == 0) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3);
-#endif
             if (q + PFX < NP) REQUEST(q + PFX, q % PFX);
             else if constexpr (PRE_OUT) REQUEST_NEXT(q + PFX - NP, q % PFX);
             if (b > 0 || PEND::on) {
@@ -421,23 +365,9 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
                     }
             }
             asm volatile("" ::: "memory");          // table loads stay in their k-step (the optimiser would gather them up front)
-#ifdef SNERF_X2_GROUPS
-            // interleave inside the k-step: each MFMA followed by its share of the epilogue slice, so that two waves running in
-            // step still alternate on the matrix pipe instead of meeting in a VALU-only stretch
-#pragma unroll
-            for (int mm = 0; mm < 3; ++mm) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-                __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);      // transcendental
-                __builtin_amdgcn_sched_group_barrier(0x002, SNERF_X2_GROUPS, 0);      // VALU
-            }
-#endif
             __builtin_amdgcn_sched_barrier(0);      // ... and so do requests, MFMAs and epilogue slices (register pressure)
         }
     }
-#ifdef SNERF_STAMP
-    stamp(wave, lane, stamp_slot, stamp_on);        // end of the block loop: what follows until the layer's own stamp is the boundary stretch
-#endif
     // the last block of the layer: handed to the next layer, or (nothing to hide its epilogue behind but the partner wave) finished here
 #pragma unroll
     for (int i = 0; i < 16; ++i) m[i] = (int)(((uint32_t)acc.M[i] << 8) + (uint32_t)acc.X[i]);
@@ -456,8 +386,6 @@ __device__ __forceinline__ void run_layer8x2(Ring2& rg, const uint8_t* stream, u
         }
     }
     if constexpr (!PRE_OUT) rg.cur = ring2_next(rg.cur);          // the next layer starts on the next chunk
-#undef REQUEST
-#undef REQUEST_NEXT
 }
 
 // ---- the same layer on v_mfma_i32_16x16x64_i8 (program.h "k64", mlp_i8_device.h FragK): where the chip holds its clock down, the clock depends on the
@@ -480,9 +408,6 @@ struct CarryDstK {
 };
 __host__ __device__ constexpr bool carry_fits_k64(int nb, bool dep) { return !dep || nb >= 5; }
 __host__ __device__ constexpr bool field_carries_k64(int W, int variant, int C, int l) {
-#ifdef SNERF_X2_NO_CARRY
-    return false;
-#endif
     return l != field_last(variant) && carry_fits_k64(k64_blocks(k64_layer(W, C, l)), field_feeds_next(l));
 }
 // quad cg of a block from its merged sums: epi_quad on m[4 cg ..], the digits into dword `dw` of the k-step fragment `ob`
@@ -562,26 +487,10 @@ __device__ __forceinline__ void run_layer16(Ring2& rg, const uint8_t* stream, ui
             rq[0] = tp[0]; rq[1] = tp[1]; rq[2] = tp[2];
         }
     };
-#define REQUEST(QN, SLOT)                                                                              \
-    do {                                                                                               \
-        if ((QN) % kChunkPairs == 0) {                                                                 \
-            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                              \
-            if ((QN) > 0) rg.cur = ring2_next(rg.cur);                                                 \
-        }                                                                                              \
-        lds_char* ap_ = lds + rg.cur + ((QN) % kChunkPairs) * kPairBytes + lane * 16;                  \
-        fT[SLOT] = *(lds_ci32x4*)ap_;                                                                  \
-        fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                                   \
-    } while (0)
-#define REQUEST_NEXT(J, SLOT)                                                                          \
-    do {                                                                                               \
-        if ((J) == 0) {                                                                                \
-            ring_step2<PHASE>(rg, stream, stream_bytes, lds, wave, lane);                              \
-            rg.cur = ring2_next(rg.cur);                                                               \
-        }                                                                                              \
-        lds_char* ap_ = lds + rg.cur + (J) * kPairBytes + lane * 16;                                   \
-        fT[SLOT] = *(lds_ci32x4*)ap_;                                                                  \
-        fL[SLOT] = *(lds_ci32x4*)(ap_ + kFragBytes);                                                   \
-    } while (0)
+    if constexpr (kNoFragReads) {
+#pragma unroll
+        for (int q = 0; q < PFX; ++q) { fT[q] = i32x4{lane, 1, 2, 3}; fL[q] = i32x4{4, lane, 6, 7}; }
+    }
     if constexpr (!PRE_IN) {
 #pragma unroll
         for (int q = 0; q < PFX; ++q) {
@@ -618,9 +527,7 @@ __device__ __forceinline__ void run_layer16(Ring2& rg, const uint8_t* stream, ui
         for (int s = 0; s < KS; ++s) {
             const int q = b * KS + s;
             const i32x4 aT = fT[q % PFX], aL = fL[q % PFX];
-#ifndef SNERF_X2_NOPRIO
             if (((s + PHASE) & 1) == 0) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3);
-#endif
             if (q + PFX < NP) REQUEST(q + PFX, q % PFX);
             else if constexpr (PRE_OUT) REQUEST_NEXT(q + PFX - NP, q % PFX);
             mfma_k64x3(aT, aL, s < KS0 ? in0[s] : in1[s - KS0], acc);
@@ -654,16 +561,13 @@ __device__ __forceinline__ void run_layer16(Ring2& rg, const uint8_t* stream, ui
         }
     }
     if constexpr (!PRE_OUT) rg.cur = ring2_next(rg.cur);          // the next layer starts on the next chunk
+}
 #undef REQUEST
 #undef REQUEST_NEXT
-}
 
 // instances built on the 16x16x64 shape (the others, and every instance under SNERF_I8X2_MFMA32=1, run the 32x32x32 code above)
-#ifndef SNERF_K64_VARIANTS
-#define SNERF_K64_VARIANTS 0xf      // bit v = variant v
-#endif
-__host__ __device__ constexpr bool k64_built(int W, int variant) { return W == 256 && ((SNERF_K64_VARIANTS >> variant) & 1); }
-bool i8x2_k64_built(int W, int variant) { return variant >= 0 && variant <= 3 && k64_built(W, variant); }
+__host__ __device__ constexpr bool k64_built(int W) { return W == 256; }      // all four variants (profiles/r13)
+bool i8x2_k64_built(int W, int variant) { return variant >= 0 && variant <= 3 && k64_built(W); }
 
 template <int W, int VARIANT, int PHASE>
 __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_char* lds, __attribute__((address_space(3))) float* tab_lds,
@@ -694,11 +598,7 @@ __global__ __launch_bounds__(64 * NW2, 1) void mlp_i8x2_kernel(const MlpArgs A) 
         uint32_t wr = 0;
 #pragma unroll
         for (int c = 0; c < RING2_D - 2; ++c) {
-#if defined(SNERF_X2_OLD_LOADS) && !defined(SNERF_STAMP)
-            if (wave < 4) dma_chunk4(A.stream, rg.goff, lds, wr, wave, lane);
-#else
-            dma_chunk2(A.stream, rg.goff, lds, wr, wave, lane);
-#endif
+            if (wave < DMA_WAVES2) dma_chunk4(A.stream, rg.goff, lds, wr, wave, lane);
             rg.goff += kChunkBytes;
             if (rg.goff >= A.stream_bytes) rg.goff = 0;
             wr += kChunkBytes;
@@ -707,11 +607,11 @@ __global__ __launch_bounds__(64 * NW2, 1) void mlp_i8x2_kernel(const MlpArgs A) 
     }
     __syncthreads();   // table visible (drains the prologue DMAs once; harmless)
 
-    // the MFMA shape: by width and variant at compile time (k64_built), and there by the stream the host handed over (A.k64: api.cpp field_launch)
+    // the MFMA shape: by width at compile time (k64_built), and there by the stream the host handed over (A.k64: api.cpp field_launch)
     bool k64 = false;
-    if constexpr (k64_built(W, VARIANT)) k64 = A.k64 != 0;
+    if constexpr (k64_built(W)) k64 = A.k64 != 0;
     if (k64) {
-        if constexpr (k64_built(W, VARIANT)) {
+        if constexpr (k64_built(W)) {
             if (wave < 4) field_tiles16<W, VARIANT, 0>(A, rg, lds, tab_lds, wave, lane);
             else field_tiles16<W, VARIANT, 1>(A, rg, lds, tab_lds, wave, lane);
         }
@@ -756,38 +656,24 @@ __device__ __forceinline__ void field_tiles16(const MlpArgs& A, Ring2& rg, lds_c
         FragK hA[KW], hB[KW];
         float raw[8];
         BoundaryK bd;
+        // The lists of mlp_i8_device.h.  Everything a line does not name comes from the k64 shape of its layer; the carry a layer receives from that
+        // of layer L - 1: HAND(L) = layer L hands its last block to its successor (one flag per boundary, read by both sides).
+#define SHAPE(L) k64_layer(W, C_MAX, L)
 #define TAB(L) k64_table_start(W, C_MAX, L)
-#define NBLK(L) k64_blocks(k64_layer(W, C_MAX, L))
-#define HAND(L) field_carries_k64(W, VARIANT, C_MAX, L)
-#define PRE_I(L) (L != F_FC1)
-#define PRE_O(L) (L != field_last(VARIANT))
-#define PEND_T(P, PSIN, PRAWL) std::conditional_t<HAND(P), Carry<TAB(P), NBLK(P), PSIN, PRAWL, field_feeds_next(P)>, NoCarry>
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW, PEND, PDST, HANDv)                                                     \
-    run_layer16<NBv, K0, K1, SINv, false, PHASE, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),  \
-                                                 IN0, IN1, OUT, RAW, bd, PDST, wave, lane, nullptr)
-#define LAYER_RAW(L, NBv, K0, K1, IN0, IN1, OUT, RX, PEND, PDST, HANDv)                                                        \
-    run_layer16<NBv, K0, K1, true, true, PHASE, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),   \
-                                                IN0, IN1, OUT, nullptr, bd, PDST, wave, lane, RX)
-        const CarryDstK none{nullptr, nullptr, nullptr};
-        static_assert(NBLK(F_FC1) == 4 * KW && NBLK(F_FC9) == 4 * KW2 && NBLK(F_HEAD) == 1 && NBLK(F_S4) == 1 && NBLK(F_A1) == 4 * KW, "block counts below");
-        // trunk
-        LAYER_RAW(F_FC1, W / 16, 1, 0, &pe, nullptr, hA, rx_p, NoCarry, none, HAND(F_FC1));
-        LAYER(F_FC2, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC1, true, true), (CarryDstK{hA, nullptr, rx_p}), HAND(F_FC2));
-        LAYER(F_FC3, W / 16, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC2, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC3));
-        LAYER(F_FC4, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC3, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_FC4));
-        LAYER_RAW(F_FC5, W / 16, KW, 1, hB, &pe, hA, rx_p, PEND_T(F_FC4, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC5));
-        LAYER(F_FC6, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC5, true, true), (CarryDstK{hA, nullptr, rx_p}), HAND(F_FC6));
-        // the lane's own point (l & 31) is one of its two: from here on its coordinates (for the stores) replace the pair's, whose last reader was fc6
-        if constexpr (VARIANT != 3) {
-            const bool up = (lane & 16) != 0;
-            x0 = up ? rx_p[1][0] : rx_p[0][0]; x1 = up ? rx_p[1][1] : rx_p[0][1]; x2 = up ? rx_p[1][2] : rx_p[0][2];
-        }
-        LAYER(F_FC7, W / 16, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC6, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC7));
-        LAYER(F_FC8, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC7, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_FC8));
+#define HAND(L) (L >= F_FC1 && field_carries_k64(W, VARIANT, C_MAX, L))
+#define PEND_T(P) std::conditional_t<HAND(P), Carry<TAB(P), k64_blocks(SHAPE(P)), layer_sine(SHAPE(P)), layer_reads_raw(SHAPE(P)), field_feeds_next(P)>, NoCarry>
+#define LAYER(L, IN0, IN1, OUT, RAW, RX, PO, PR, PX)                                                                                                 \
+    run_layer16<k64_blocks(SHAPE(L)), SHAPE(L).ks0, SHAPE(L).ks1, layer_sine(SHAPE(L)), layer_reads_raw(SHAPE(L)), PHASE, PEND_T(L - 1), HAND(L),   \
+                L != F_FC1, L != field_last(VARIANT)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L), IN0, IN1, OUT, RAW, bd,         \
+                                                      (CarryDstK{PO, PR, PX}), wave, lane, RX)
         FragK x1f[KW2];
-        LAYER(F_FC9, W2 / 16, KW, 0, true, hB, nullptr, x1f, nullptr, PEND_T(F_FC8, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_FC9));
-        // sigma / colour head: rows 0..2 colour, 3 density (lane group 0); with the solar branch behind it the block finishes inside fc_solar_1
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, raw, PEND_T(F_FC9, true, false), (CarryDstK{x1f, nullptr, nullptr}), HAND(F_HEAD));
+        I8_TRUNK(LAYER, &pe, hA, hB, x1f, raw, rx_p,
+                 // the lane's own point (l & 31) is one of its two: from here on its coordinates (for the stores) replace the pair's, whose last reader was fc6
+                 if constexpr (VARIANT != 3) {
+                     const bool up = (lane & 16) != 0;
+                     x0 = up ? rx_p[1][0] : rx_p[0][0]; x1 = up ? rx_p[1][1] : rx_p[0][1]; x2 = up ? rx_p[1][2] : rx_p[0][2];
+                 });
+        // the head's rows 0..2 colour, 3 density (lane group 0); with the solar branch behind it the block finishes inside fc_solar_1
         float col_r, col_g, col_b, rho_raw;
         float sv_raw = 0.f;
         float adj[3 * C_MAX];
@@ -799,33 +685,22 @@ __device__ __forceinline__ void field_tiles16(const MlpArgs& A, Ring2& rg, lds_c
             FragK ps;
             make_pe_sun_k64(rx_s, gq, ps);
             FragK sA[KW2], sB[KW2];
-            LAYER_RAW(F_S1, W2 / 16, KW2, 1, x1f, &ps, sA, rx_s, PEND_T(F_HEAD, false, false), (CarryDstK{nullptr, raw, nullptr}), HAND(F_S1));
-            HEAD_OUT();
-            LAYER(F_S2, W2 / 16, KW2, 0, true, sA, nullptr, sB, nullptr, PEND_T(F_S1, true, true), (CarryDstK{sA, nullptr, rx_s}), HAND(F_S2));
-            LAYER(F_S3, W2 / 16, KW2, 0, true, sB, nullptr, sA, nullptr, PEND_T(F_S2, true, false), (CarryDstK{sB, nullptr, nullptr}), HAND(F_S3));
-            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, raw, PEND_T(F_S3, true, false), (CarryDstK{sA, nullptr, nullptr}), HAND(F_S4));
+            I8_SOLAR(LAYER, x1f, &ps, sA, sB, raw, rx_s, HEAD_OUT(););
             if constexpr (VARIANT == 1) sv_raw = k64_head_row(raw, 0, lane);
         } else {
             HEAD_OUT();
         }
         if constexpr (VARIANT == 0) {
-            LAYER(F_A1, W / 16, KW2, 0, true, x1f, nullptr, hA, nullptr, PEND_T(F_S4, false, false), (CarryDstK{nullptr, raw, nullptr}), HAND(F_A1));
-            sv_raw = k64_head_row(raw, 0, lane);
-            LAYER(F_A2, W / 16, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_A1, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_A2));
-            LAYER(F_A3, W / 16, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_A2, true, false), (CarryDstK{hB, nullptr, nullptr}), HAND(F_A3));
-            LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, raw, PEND_T(F_A3, true, false), (CarryDstK{hA, nullptr, nullptr}), HAND(F_AC));
+            I8_ADJUST(LAYER, x1f, hA, hB, raw, sv_raw = k64_head_row(raw, 0, lane););
 #pragma unroll
             for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = k64_head_row(raw, i, lane);
         }
 #undef HEAD_OUT
 #undef LAYER
-#undef LAYER_RAW
 #undef PEND_T
 #undef HAND
-#undef PRE_I
-#undef PRE_O
 #undef TAB
-#undef NBLK
+#undef SHAPE
         if constexpr (VARIANT == 3) {
             RAYSUM_PASS_END(rs, A, tile, pass, passes, NW2, wave, wave, NW2, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
         } else {
@@ -860,106 +735,61 @@ __device__ __forceinline__ void field_tiles2(const MlpArgs& A, Ring2& rg, lds_ch
         else field_point(A, nc, x0, x1, x2);
         float s0, s1, s2, pcls[C_MAX];
         field_tile_inputs<VARIANT>(A, g, s0, s1, s2, pcls);
-#ifdef SNERF_STAMP
-        const bool stamp_on = blockIdx.x == 0 && tile == (int64_t)blockIdx.x + gridDim.x;      // the workgroup's second tile
-#endif
-        STAMP(0);
         Frag8 pe[PEPOS_KS8];
         make_pe_pos8<VARIANT == 3>(x0, x1, x2, h, pe);
-        STAMP(1);
 
         constexpr int KW = W / 32, KW2 = W2 / 32;
         Frag8 hA[KW], hB[KW];
         f32x16 raw;
         Boundary bd;      // a layer's last block and the next layer's first weight fragments on their way across the boundary (run_layer8x2)
-        // Layer boundaries: field_carries(W, VARIANT, L) = layer L hands its last block to its successor in the chain (one flag per boundary,
-        // read by both sides: HAND(L) in the producer, PEND_T(L, ...) in the receiver).
+        // The lists of mlp_i8_device.h.  Everything a line does not name comes from the FMT_I8 shape of its layer; the carry a layer receives from that
+        // of layer L - 1: HAND(L) = field_carries: layer L hands its last block to its successor in the chain (one flag per boundary, read by both sides).
+#define SHAPE(L) field_layer(W, C_MAX, L, FMT_I8)
 #define TAB(L) prog_table_start(PROG_FIELD, W, C_MAX, L)
-#define NBLK(L) (prog_layer(PROG_FIELD, W, C_MAX, L, FMT_I8).n_out / 32)
-#define HAND(L) field_carries(W, VARIANT, C_MAX, L)
+#define HAND(L) (L >= F_FC1 && field_carries(W, VARIANT, C_MAX, L))
+#define PEND_T(P) std::conditional_t<HAND(P), Carry<TAB(P), SHAPE(P).nb(), layer_sine(SHAPE(P)), layer_reads_raw(SHAPE(P)), field_feeds_next(P)>, NoCarry>
         // the weight pipeline runs across every boundary of the chain where the pair counts allow it (all of them from W = 128 on)
-#ifdef SNERF_X2_NO_XPF
-        constexpr bool XPF = false;          // A/B: every layer requests its own first fragments
-#else
         constexpr bool XPF = KW2 >= PFX && KW2 % PFX == 0;
-#endif
-#define PRE_I(L) (XPF && L != F_FC1)
-#define PRE_O(L) (XPF && L != field_last(VARIANT))
-#define PEND_T(P, PSIN, PRAWL) std::conditional_t<HAND(P), Carry<TAB(P), NBLK(P), PSIN, PRAWL, field_feeds_next(P)>, NoCarry>
-#ifdef SNERF_STAMP
-#define STAMP_ARGS(L) , stamp_on, 24 + L
-#else
-#define STAMP_ARGS(L)
-#endif
-#define LAYER(L, NBv, K0, K1, SINv, IN0, IN1, OUT, RAW, PEND, PDST, HANDv)                                                     \
-    run_layer8x2<NBv, K0, K1, SINv, false, PHASE, VARIANT == 3, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),  \
-                                                  IN0, IN1, OUT, RAW, bd, PDST, wave, lane, nullptr STAMP_ARGS(L))
-#define LAYER_RAW(L, NBv, K0, K1, IN0, IN1, OUT, RX, PEND, PDST, HANDv)                                                        \
-    run_layer8x2<NBv, K0, K1, true, true, PHASE, VARIANT == 3, PEND, HANDv, PRE_I(L), PRE_O(L)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L),   \
-                                                 IN0, IN1, OUT, nullptr, bd, PDST, wave, lane, RX STAMP_ARGS(L))
+#define LAYER(L, IN0, IN1, OUT, RAW, RX, PO, PR, PX)                                                                                                 \
+    run_layer8x2<SHAPE(L).nb(), SHAPE(L).ks0, SHAPE(L).ks1, layer_sine(SHAPE(L)), layer_reads_raw(SHAPE(L)), PHASE, VARIANT == 3, PEND_T(L - 1), HAND(L), \
+                 XPF && L != F_FC1, XPF && L != field_last(VARIANT)>(rg, A.stream, A.stream_bytes, lds, tab_lds, tab_lds + TAB(L), IN0, IN1, OUT, RAW, bd, \
+                                                                     (CarryDst{PO, PR, PX}), wave, lane, RX)
         const float rx_p[3] = {x0, x1, x2}, rx_s[3] = {s0, s1, s2};      // raw coordinates: fp32, no digit range
-        const CarryDst none{nullptr, nullptr, nullptr};
-        static_assert(NBLK(F_FC1) == KW && NBLK(F_FC9) == KW2 && NBLK(F_HEAD) == 1 && NBLK(F_S4) == 1 && NBLK(F_A1) == KW, "block counts below");
-        // trunk (G_NeRF.py:80-91)
-        LAYER_RAW(F_FC1, W / 32, PEPOS_KS8, 0, pe, nullptr, hA, rx_p, NoCarry, none, HAND(F_FC1)); STAMP(2);
-        LAYER(F_FC2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC1, true, true), (CarryDst{hA, nullptr, rx_p}), HAND(F_FC2)); STAMP(3);
-        LAYER(F_FC3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC2, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC3)); STAMP(4);
-        LAYER(F_FC4, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC3, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_FC4)); STAMP(5);
-        LAYER_RAW(F_FC5, W / 32, KW, PEPOS_KS8, hB, pe, hA, rx_p, PEND_T(F_FC4, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC5)); STAMP(6);
-        LAYER(F_FC6, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC5, true, true), (CarryDst{hA, nullptr, rx_p}), HAND(F_FC6)); STAMP(7);
-        LAYER(F_FC7, W / 32, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_FC6, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC7)); STAMP(8);
-        LAYER(F_FC8, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_FC7, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_FC8)); STAMP(9);
         Frag8 x1f[KW2];
-        LAYER(F_FC9, W2 / 32, KW, 0, true, hB, nullptr, x1f, nullptr, PEND_T(F_FC8, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_FC9)); STAMP(10);
-        // sigma / colour head (G_NeRF.py:93-98): regs 0..2 colour, 3 density (lane-half 0).  With the solar branch behind it the head's
-        // block finishes inside fc_solar_1 (which does not read it: spread over the whole block), so `raw` is read behind that layer.
-        LAYER(F_HEAD, 1, KW2, 0, false, x1f, nullptr, nullptr, &raw, PEND_T(F_FC9, true, false), (CarryDst{x1f, nullptr, nullptr}), HAND(F_HEAD)); STAMP(11);
+        I8_TRUNK(LAYER, pe, hA, hB, x1f, &raw, rx_p);
+        // the head's regs 0..2 colour, 3 density (lane-half 0).  With the solar branch behind it the head's block finishes inside fc_solar_1 (which
+        // does not read it: spread over the whole block), so `raw` is read behind that layer.
         float col_r, col_g, col_b, rho_raw;
         float sv_raw = 0.f;
         float adj[3 * C_MAX];
 #pragma unroll
         for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = 0.f;
         if constexpr (VARIANT <= 1) {
-            // solar visibility branch (G_NeRF.py:100-108)
             Frag8 ps[PESUN_KS8];
             make_pe_sun8(s0, s1, s2, h, ps);
             Frag8 sA[KW2], sB[KW2];
-            LAYER_RAW(F_S1, W2 / 32, KW2, PESUN_KS8, x1f, ps, sA, rx_s, PEND_T(F_HEAD, false, false), (CarryDst{nullptr, &raw, nullptr}), HAND(F_S1)); STAMP(12);
-            col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
-            LAYER(F_S2, W2 / 32, KW2, 0, true, sA, nullptr, sB, nullptr, PEND_T(F_S1, true, true), (CarryDst{sA, nullptr, rx_s}), HAND(F_S2)); STAMP(13);
-            LAYER(F_S3, W2 / 32, KW2, 0, true, sB, nullptr, sA, nullptr, PEND_T(F_S2, true, false), (CarryDst{sB, nullptr, nullptr}), HAND(F_S3)); STAMP(14);
             // fc_solar_4's one block finishes inside adjust_layer_1 (variant 0), which reads x1f, not the solar branch
-            LAYER(F_S4, 1, KW2, 0, false, sA, nullptr, nullptr, &raw, PEND_T(F_S3, true, false), (CarryDst{sA, nullptr, nullptr}), HAND(F_S4)); STAMP(15);
+            I8_SOLAR(LAYER, x1f, ps, sA, sB, &raw, rx_s, col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];);
             if constexpr (VARIANT == 1) sv_raw = raw[0];
         } else {
             col_r = raw[0], col_g = raw[1], col_b = raw[2], rho_raw = raw[3];
         }
         if constexpr (VARIANT == 0) {
-            // seasonal colour-adjust branch (T_NeRF_net_v2.py:83-87)
-            LAYER(F_A1, W / 32, KW2, 0, true, x1f, nullptr, hA, nullptr, PEND_T(F_S4, false, false), (CarryDst{nullptr, &raw, nullptr}), HAND(F_A1)); STAMP(16);
-            sv_raw = raw[0];
-            LAYER(F_A2, W / 32, KW, 0, true, hA, nullptr, hB, nullptr, PEND_T(F_A1, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_A2)); STAMP(17);
-            LAYER(F_A3, W / 32, KW, 0, true, hB, nullptr, hA, nullptr, PEND_T(F_A2, true, false), (CarryDst{hB, nullptr, nullptr}), HAND(F_A3)); STAMP(18);
-            LAYER(F_AC, 1, KW, 0, false, hA, nullptr, nullptr, &raw, PEND_T(F_A3, true, false), (CarryDst{hA, nullptr, nullptr}), HAND(F_AC)); STAMP(19);
+            I8_ADJUST(LAYER, x1f, hA, hB, &raw, sv_raw = raw[0];);
 #pragma unroll
             for (int i = 0; i < 3 * C_MAX; ++i) adj[i] = raw[i];
         }
 #undef LAYER
-#undef LAYER_RAW
 #undef PEND_T
 #undef HAND
-#undef PRE_I
-#undef PRE_O
-#undef STAMP_ARGS
 #undef TAB
-#undef NBLK
+#undef SHAPE
         if constexpr (VARIANT == 3) {
             RAYSUM_PASS_END(rs, A, tile, pass, passes, NW2, wave, wave, NW2, true, lane, rho_raw, x0, x1, x2, tab_lds + A.bias_floats);
         } else {
             if (h == 0 && valid) store_field_outputs<VARIANT>(A.out, n, C, x0, x1, x2, col_r, col_g, col_b, rho_raw, sv_raw, adj, pcls);
             tile += gridDim.x;
         }
-        STAMP(20);
     }
     __builtin_amdgcn_s_setprio(0);
 }
@@ -985,13 +815,3 @@ hipError_t launch_mlp_i8x2(int W, int variant, const MlpArgs& a, int n_cu, hipSt
 }
 
 }  // namespace snerf
-
-#ifdef SNERF_STAMP
-extern "C" int snerf_debug_stamps(unsigned long long* host, int n) {
-    if (n > 8 * 64) n = 8 * 64;
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(snerf::g_stamps), (size_t)n * 8);
-    unsigned long long zero[8 * 64] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(snerf::g_stamps), zero, sizeof(zero));
-    return e == hipSuccess ? 0 : -3;
-}
-#endif

@@ -222,4 +222,47 @@ __device__ __forceinline__ void make_pe_sun_k64(const float (*sq)[3], int g, Fra
     }
 }
 
+// ---- The field network's layer lists of the three int8 kernels (mlp_i8_kernel, and field_tiles2 / field_tiles16 of mlp_i8x2_kernel), written once
+// (DESIGN 5.1i).  Macros for the reason FIELD_TRUNK (kernels.hip) is one: a function form changed instructions.  A list line names buffers, program.h
+// gives the rest:
+//     LAYER(L, IN0, IN1, OUT, RAW, RX, PO, PR, PX)
+// L the layer, IN0 / IN1 its input fragments, OUT its digit output or RAW its raw rows (the other is nullptr), RX the raw coordinates of the encoding it
+// reads (or nullptr); PO / PR / PX are OUT / RAW / RX of layer L - 1, where a carried last block of that layer is finished (kernels_i8x2.hip Carry; every
+// variant runs a prefix of the enum order, so the predecessor of L is L - 1).  Block count, k-steps, sine or raw output, encoding or not, table start and
+// the carry's shape are the using kernel's LAYER's to derive from the LayerShape of L and L - 1.  The weight stream cannot branch: a kernel runs these
+// lists in the order of its stream, and a change to a list is a change to all three kernels and both streams (FMT_I8, k64).
+//   trunk (G_NeRF.py:80-91) and sigma / colour head (G_NeRF.py:93-98): pe -> x1f and raw (rows 0..2 colour, 3 density); hA, hB are scratch.  The statements
+//   given after rx_p run behind fc6, the last reader of rx_p
+#define I8_TRUNK(LAYER, pe, hA, hB, x1f, raw, rx_p, ...)                                                                                            \
+    LAYER(F_FC1, pe, nullptr, hA, nullptr, rx_p, nullptr, nullptr, nullptr);                                                                        \
+    LAYER(F_FC2, hA, nullptr, hB, nullptr, nullptr, hA, nullptr, rx_p);                                                                             \
+    LAYER(F_FC3, hB, nullptr, hA, nullptr, nullptr, hB, nullptr, nullptr);                                                                          \
+    LAYER(F_FC4, hA, nullptr, hB, nullptr, nullptr, hA, nullptr, nullptr);                                                                          \
+    LAYER(F_FC5, hB, pe, hA, nullptr, rx_p, hB, nullptr, nullptr);                                                                                  \
+    LAYER(F_FC6, hA, nullptr, hB, nullptr, nullptr, hA, nullptr, rx_p);                                                                             \
+    __VA_ARGS__                                                                                                                                     \
+    LAYER(F_FC7, hB, nullptr, hA, nullptr, nullptr, hB, nullptr, nullptr);                                                                          \
+    LAYER(F_FC8, hA, nullptr, hB, nullptr, nullptr, hA, nullptr, nullptr);                                                                          \
+    LAYER(F_FC9, hB, nullptr, x1f, nullptr, nullptr, hB, nullptr, nullptr);                                                                         \
+    LAYER(F_HEAD, x1f, nullptr, nullptr, raw, nullptr, x1f, nullptr, nullptr)
+//   solar visibility branch (G_NeRF.py:100-108): x1f, ps = PE(sun) -> raw row 0; sA, sB are scratch.  The statements given after rx_s run behind
+//   fc_solar_1: where the head's block is carried into that layer, its rows are complete there
+#define I8_SOLAR(LAYER, x1f, ps, sA, sB, raw, rx_s, ...)                                                                                            \
+    LAYER(F_S1, x1f, ps, sA, nullptr, rx_s, nullptr, raw, nullptr);                                                                                 \
+    __VA_ARGS__                                                                                                                                     \
+    LAYER(F_S2, sA, nullptr, sB, nullptr, nullptr, sA, nullptr, rx_s);                                                                              \
+    LAYER(F_S3, sB, nullptr, sA, nullptr, nullptr, sB, nullptr, nullptr);                                                                           \
+    LAYER(F_S4, sA, nullptr, nullptr, raw, nullptr, sA, nullptr, nullptr)
+//   seasonal colour-adjust branch (T_NeRF_net_v2.py:83-87): x1f -> raw rows 0 .. 3 C_MAX; hA, hB are scratch.  The statements given after raw run behind
+//   adjust_layer_1 (fc_solar_4's carried block is complete there)
+#define I8_ADJUST(LAYER, x1f, hA, hB, raw, ...)                                                                                                     \
+    LAYER(F_A1, x1f, nullptr, hA, nullptr, nullptr, nullptr, raw, nullptr);                                                                         \
+    __VA_ARGS__                                                                                                                                     \
+    LAYER(F_A2, hA, nullptr, hB, nullptr, nullptr, hA, nullptr, nullptr);                                                                           \
+    LAYER(F_A3, hB, nullptr, hA, nullptr, nullptr, hB, nullptr, nullptr);                                                                           \
+    LAYER(F_AC, hA, nullptr, nullptr, raw, nullptr, hA, nullptr, nullptr)
+// what a LAYER reads from the shape (program.h LayerShape) of its layer
+__host__ __device__ constexpr bool layer_sine(const LayerShape& s) { return s.out_kind == OUT_SIN; }
+__host__ __device__ constexpr bool layer_reads_raw(const LayerShape& s) { return raw_kind(s) != IN_NONE; }
+
 }  // namespace snerf

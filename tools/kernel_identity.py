@@ -5,7 +5,8 @@ Each source is compiled in both trees with build.py's FLAGS + EXTRA and `-S --cu
 the device functions they call), and comments, labels and assembler directives are dropped.  Prints IDENTICAL or DIFF per symbol with the instruction
 counts of both sides, and every difference in the kernels' metadata (registers, spills, scratch, LDS).  Exit status 1 on any DIFF.  Whole instruction
 streams are compared, whatever they contain.  --asm-dir DIR keeps the listings (DIR/old, DIR/new); a listing newer than every file of its tree is
-reused, so the unchanged side of a comparison is compiled once."""
+reused, so the unchanged side of a comparison is compiled once.  --flags "-DSNERF_ABLATE -DABL=2" appends flags to both sides (a diagnostic
+build; give each set of flags an --asm-dir of its own)."""
 import argparse
 import os
 import re
@@ -21,11 +22,11 @@ import build  # noqa: E402
 META = [".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size"]
 
 
-def listing(tree, src, out):
+def listing(tree, src, out, flags=()):
     newest = max(os.path.getmtime(os.path.join(tree, f)) for f in os.listdir(tree))
     if not (os.path.exists(out) and os.path.getmtime(out) > newest):
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        subprocess.check_call([build._hipcc()] + build.FLAGS + build.EXTRA.get(src, []) + ["-S", "--cuda-device-only", os.path.join(tree, src), "-o", out])
+        subprocess.check_call([build._hipcc()] + build.FLAGS + build.EXTRA.get(src, []) + list(flags) + ["-S", "--cuda-device-only", os.path.join(tree, src), "-o", out])
     return open(out).read()
 
 
@@ -70,11 +71,12 @@ def main():
     ap.add_argument("sources", nargs="+")
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--jobs", type=int, default=4)
+    ap.add_argument("--flags", default="", help="extra compiler flags for both sides, in one string")
     a = ap.parse_args()
     keep = a.asm_dir or tempfile.mkdtemp(prefix="kernel_identity_")
     jobs = [(side, tree, s) for s in a.sources for side, tree in (("old", a.old), ("new", a.new))]
     with ThreadPoolExecutor(max_workers=a.jobs) as ex:
-        asm = dict(zip([(side, s) for side, _, s in jobs], ex.map(lambda j: listing(j[1], j[2], os.path.join(keep, j[0], j[2] + ".s")), jobs)))
+        asm = dict(zip([(side, s) for side, _, s in jobs], ex.map(lambda j: listing(j[1], j[2], os.path.join(keep, j[0], j[2] + ".s"), a.flags.split()), jobs)))
     n_diff = 0
     for s in a.sources:
         fo, fn, mo, mn = functions(asm["old", s]), functions(asm["new", s]), metadata(asm["old", s]), metadata(asm["new", s])
