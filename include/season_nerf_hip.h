@@ -486,6 +486,51 @@ int snerf_loss_terms_forward(int64_t n_rays, int64_t n_solar_rays, int n_samples
 int snerf_loss_terms_backward(int64_t n_rays, int64_t n_solar_rays, int n_samples, const float* d_rgb, const float* d_gt, const float* d_albedo,
                               const float* d_sky, const float* d_solar_vis, const float* d_pv_exact, const float* d_min3, int world, const float* d_g_vals5,
                               float* d_g_rgb, float* d_g_albedo, float* d_g_sky, float* d_g_solar_vis, void* stream);
+/* ---- the loss terms of the configurations snerf_loss_terms_* does not serve: Barron's adaptive colour loss (Eval_Tools_2.py:421-450) and / or the
+ * DSM-prior phase (:243, :391-412), default solar model.  flags selects the configuration; the value vector follows get_loss's key order:
+ *   SNERF_LOSS_ADAPTIVE                    (8):  Solar_Correction, Solar_Correction_2, Sky_Color_Var, Albedo_Color, Color_ada, Color_alpha, Color_width, Color
+ *   SNERF_LOSS_ADAPTIVE | SNERF_LOSS_PRIOR (12): Solar_Correction, Solar_Correction_2, Sky_Color_Var, Albedo_Color, Alpha_Adjust_ada, Color_ada, Color_alpha,
+ *                                                Color_width, Alpha_Adjust, Alpha_alpha, Alpha_width, Color
+ *   SNERF_LOSS_PRIOR                       (6):  Solar_Correction, Solar_Correction_2, Sky_Color_Var, Albedo_Color, Color, Alpha_Adjust
+ * SNERF_LOSS_SKY_DETACHED: Sky_Color_Var is a value only (the reference detaches it in the prior phase).  Color_ada = mean over [R,3] of
+ * nll(Rendered_Col - GT) with nll(x) = rho(x, alpha, c) + log c + log Z(alpha) (Barron 2019, as season_nerf_amd/adaptive_loss.py states it; parity with
+ * robust_loss_pytorch is NOT pinned); Alpha_Adjust_ada = mean over [R,S] of nll(PE - PE_Supervised) under the second, one-dimensional loss object;
+ * Alpha_Adjust = MSE(PE, PE_Supervised); Color = MSE(d_rgb_merged if given, else d_rgb, GT) - a value only beside the adaptive loss.  alpha / scale are
+ * the float32 vectors the caller formed ([3] for colour, [1] for alpha); log Z is the cubic Hermite spline on d_logz_value / d_logz_slope: 513 float64 numbers
+ * each on the grid alpha_i = 4 i / 512 (float64: rounding the table to float32 alone moves d log Z / d alpha by 1.5e-5).  Pointers a configuration does not use may be NULL.
+ * forward: d_vals and d_weights hold snerf_loss_all_term_count(flags) floats - the weights of sum(value * weight): w_solar / mean(scale colour)^2 for the
+ * two Solar_Correction terms beside the adaptive loss (w_solar otherwise), w_solar for Sky_Color_Var and Albedo_Color, w_color for Color_ada / Color,
+ * w_alpha for Alpha_Adjust(_ada), 1 for the logged means; d_aux14: 14 floats for the backward (albedo minima and their rows as d_min3 above, then
+ * d term / d alpha and d term / d scale per channel of both loss objects).  Values are reduced without floating-point atomics, block sums in a fixed
+ * order: two calls on the same inputs give the same bits.  d_scratch: snerf_loss_all_scratch_bytes() bytes, no initial state needed, one per stream.
+ * backward: from d_g_vals (dL / d vals) to the gradients of snerf_loss_grads; terms that are values only contribute nothing, the gradient of a detached
+ * input is written as zeros; outputs of inputs the configuration lacks may be NULL. */
+#define SNERF_LOSS_ADAPTIVE 1
+#define SNERF_LOSS_PRIOR 2
+#define SNERF_LOSS_SKY_DETACHED 4
+typedef struct snerf_loss_in {
+    int64_t n_rays, n_solar_rays;
+    int n_samples, flags;
+    const float *d_rgb, *d_rgb_merged, *d_gt, *d_albedo, *d_sky;           /* [n_rays,3]; d_rgb_merged optional */
+    const float *d_solar_vis, *d_pv_exact, *d_pe_solar;                    /* sun-ray pass [n_solar_rays, n_samples] */
+    const float *d_pe, *d_pe_supervised;                                   /* prior: image rays [n_rays, n_samples] */
+    const float *d_alpha_color, *d_scale_color;                            /* adaptive: [3] */
+    const float *d_alpha_alpha, *d_scale_alpha;                            /* adaptive + prior: [1] */
+    const double *d_logz_value, *d_logz_slope;                             /* adaptive: [513], float64 */
+    const float* d_albedo_min_global;                                      /* optional [3] + world, as snerf_loss_terms_forward */
+    int world;
+    float w_solar, w_color, w_alpha;
+} snerf_loss_in;
+typedef struct snerf_loss_grads {
+    float *d_g_rgb, *d_g_rgb_merged, *d_g_albedo, *d_g_sky;                /* [n_rays,3] */
+    float *d_g_solar_vis;                                                  /* [n_solar_rays, n_samples] */
+    float *d_g_pe;                                                         /* [n_rays, n_samples] */
+    float *d_g_alpha_color, *d_g_scale_color, *d_g_alpha_alpha, *d_g_scale_alpha;
+} snerf_loss_grads;
+size_t snerf_loss_all_scratch_bytes(void);
+int snerf_loss_all_term_count(int flags);
+int snerf_loss_all_forward(const snerf_loss_in* in, void* d_scratch, float* d_vals, float* d_weights, float* d_aux14, void* stream);
+int snerf_loss_all_backward(const snerf_loss_in* in, const float* d_aux14, const float* d_g_vals, const snerf_loss_grads* out, void* stream);
 /* the same update (torch.optim.Adam, mg_run_NeRF.py:312-320) on caller-owned flat arenas of n floats */
 int snerf_adam_step(float* d_params, const float* d_grads, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                     float eps, int step, void* stream);

@@ -33,6 +33,23 @@ class LoaderOut(C.Structure):
                                           "d_row_index", "d_sc_top", "d_sc_bot")]
 
 
+class LossIn(C.Structure):
+    """snerf_loss_in: what snerf_loss_all_forward / _backward read (NULL = the configuration lacks it)."""
+    _fields_ = [("n_rays", C.c_int64), ("n_solar_rays", C.c_int64), ("n_samples", C.c_int), ("flags", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("d_rgb", "d_rgb_merged", "d_gt", "d_albedo", "d_sky", "d_solar_vis", "d_pv_exact", "d_pe_solar", "d_pe", "d_pe_supervised",
+                                          "d_alpha_color", "d_scale_color", "d_alpha_alpha", "d_scale_alpha", "d_logz_value", "d_logz_slope", "d_albedo_min_global")] + \
+               [("world", C.c_int), ("w_solar", C.c_float), ("w_color", C.c_float), ("w_alpha", C.c_float)]
+
+
+class LossGrads(C.Structure):
+    """snerf_loss_grads: the outputs of snerf_loss_all_backward."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_g_rgb", "d_g_rgb_merged", "d_g_albedo", "d_g_sky", "d_g_solar_vis", "d_g_pe", "d_g_alpha_color", "d_g_scale_color",
+                                          "d_g_alpha_alpha", "d_g_scale_alpha")]
+
+
+LOSS_ADAPTIVE, LOSS_PRIOR, LOSS_SKY_DETACHED = 1, 2, 4      # SNERF_LOSS_* of include/season_nerf_hip.h
+
+
 class I8Estimate(C.Structure):
     """snerf_i8_estimate: the pack-time error model of the int8-digit format (include/season_nerf_hip.h)."""
     _fields_ = [("head_rms", C.c_double * 4), ("hidden_rms", C.c_double), ("worst", C.c_double),
@@ -124,7 +141,12 @@ def lib():
     L.snerf_trainer_adam_step.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]
     L.snerf_trainer_adam_step_dev.argtypes = [vp, vp, vp]
     L.snerf_adam_step.argtypes = [vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]
-    L.snerf_rays_from_camera.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.snerf_loss_all_scratch_bytes.restype = C.c_size_t
+    L.snerf_loss_all_scratch_bytes.argtypes = []
+    L.snerf_loss_all_term_count.argtypes = [i32]
+    L.snerf_loss_all_forward.argtypes = [C.POINTER(LossIn), vp, vp, vp, vp, vp]
+    L.snerf_loss_all_backward.argtypes = [C.POINTER(LossIn), vp, vp, C.POINTER(LossGrads), vp]
+    L.snerf_rays_from_camera.argtypes =[vp, i32, i32, i32, vp, vp, vp]
     L.snerf_ray_grid.argtypes = [i32, i32, i32, i64, i64, vp, i32, vp, vp, vp, vp, vp]
     L.snerf_prior_density.argtypes = [i64, vp, vp, vp, i32, i32, vp, vp, vp]
     L.snerf_surface_distance.argtypes = [i64, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]
@@ -178,5 +200,6 @@ EXPORTS = ["snerf_last_error", "snerf_abi_version", "snerf_model_create", "snerf
            "snerf_trainer_backward_solar", "snerf_trainer_zero_grad", "snerf_trainer_set_allreduce", "snerf_trainer_adam_step", "snerf_trainer_adam_step_dev", "snerf_adam_step", "snerf_trainer_debug_read", "snerf_train_kernel_debug",
            "snerf_rows_debug_set", "snerf_rows_record_reset", "snerf_rows_record_read",
            "snerf_loss_scratch_bytes", "snerf_loss_scratch_init", "snerf_loss_terms_forward", "snerf_loss_terms_backward",
+           "snerf_loss_all_scratch_bytes", "snerf_loss_all_term_count", "snerf_loss_all_forward", "snerf_loss_all_backward",
            "snerf_loader_create", "snerf_loader_destroy", "snerf_loader_batches_per_epoch", "snerf_loader_batch", "snerf_loader_next", "snerf_loader_get_state", "snerf_loader_set_state",
            "snerf_loader_indices_host", "snerf_loader_sc_rays_host", "snerf_loader_philox_host"]

@@ -73,14 +73,21 @@ def _table():
     return _TABLE
 
 
+def table_on(device, dtype=torch.float32):
+    """The table of `_table()` - values and slopes, 513 numbers each - as two tensors on `device`, uploaded once per (dtype, device): what
+    log_base_partition_function interpolates, and what season_nerf::loss_terms_all reads (in float64)."""
+    key = (dtype, torch.device(device))
+    if key not in _TABLE_DEV:            # uploaded once per device: a per-call host->device copy would stall the stream
+        a, v, s = _table()
+        _TABLE_DEV[key] = (torch.as_tensor(v, dtype=dtype, device=device), torch.as_tensor(s, dtype=dtype, device=device))
+    return _TABLE_DEV[key]
+
+
 def log_base_partition_function(alpha):
     """log Z(alpha) for alpha in [0, 4], differentiable in alpha (cubic Hermite interpolation of the table)."""
     a, v, s = _table()
     h = float(a[1] - a[0])
-    key = (alpha.dtype, alpha.device)
-    if key not in _TABLE_DEV:            # uploaded once per device: a per-call host->device copy would stall the stream
-        _TABLE_DEV[key] = (torch.as_tensor(v, dtype=alpha.dtype, device=alpha.device), torch.as_tensor(s, dtype=alpha.dtype, device=alpha.device))
-    va, sa = _TABLE_DEV[key]
+    va, sa = table_on(alpha.device, alpha.dtype)
     u = torch.clamp(alpha, 0.0, float(a[-1])) / h
     i = torch.clamp(u.detach().floor().long(), 0, len(a) - 2)
     f = u - i

@@ -591,10 +591,20 @@ static Tensor loss_scratch(const Tensor& like) {
 
 // Create (and initialise) the reduction scratch of the CURRENT stream now: a captured step calls this on its capture stream BEFORE the capture begins, so that
 // the capture neither allocates it from the graph's private pool nor records its initialisation as a node that re-runs on every replay.
+// the block-sum scratch of loss_terms_all: one per (device, stream) as above; it needs no initial state (snerf_loss_all_forward)
+static Tensor loss_all_scratch(const Tensor& like) {
+    static std::mutex mu;
+    static auto* per_stream = new std::map<std::pair<int, void*>, Tensor>();
+    std::lock_guard<std::mutex> lock(mu);
+    Tensor& s = (*per_stream)[{like.get_device(), cur_stream(like)}];
+    if (!s.defined()) s = at::empty({(int64_t)snerf_loss_all_scratch_bytes()}, like.options().dtype(at::kByte));
+    return s;
+}
 void loss_scratch_prepare(const Tensor& like) {
     check_dev_f32(like, "like");
     c10::hip::HIPGuardMasqueradingAsCUDA g(like.device());
     (void)loss_scratch(like);
+    (void)loss_all_scratch(like);
 }
 
 // ---- scalar loss terms of a training step (get_loss, Eval_Tools_2.py:340-420, default configuration) ---------------------------------
@@ -628,6 +638,78 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> loss_terms_bwd(const Tensor& g_vals, 
     ck(snerf_loss_terms_backward(R, Rs, (int)S, fptr(rgb), fptr(gt), fptr(albedo), fptr(sky), fptr(sv), fptr(pv), fptr(minv), (int)world, fptr(g_vals),
                                  mptr(d_rgb), mptr(d_alb), mptr(d_sky), mptr(d_sv), cur_stream(rgb)), "loss_terms_bwd");
     return {d_rgb, d_alb, d_sky, d_sv};
+}
+
+// ---- the loss terms of the adaptive colour loss and / or the DSM-prior phase (snerf_loss_all_*): values, their weight vector, what the backward needs ----
+struct LossAllIn {
+    const Tensor &rgb, &gt, &albedo, &sky, &sv, &pv, &pe_sun;
+    const c10::optional<Tensor> &rgb_merged, &pe, &pe_sup, &alpha_c, &scale_c, &alpha_a, &scale_a, &logz_v, &logz_s, &alb_min_global;
+};
+static snerf_loss_in loss_all_in(const LossAllIn& t, int64_t world, int64_t flags, double w_solar, double w_color, double w_alpha, bool with_table = true) {
+    check_shape(t.rgb, "rgb", -1, 3);
+    const int64_t R = t.rgb.size(0);
+    check_shape(t.gt, "gt", R, 3); check_shape(t.albedo, "albedo", R, 3); check_shape(t.sky, "sky", R, 3);
+    check_dev_f32(t.sv, "solar_vis"); check_dev_f32(t.pv, "pv_exact"); check_dev_f32(t.pe_sun, "pe_solar");
+    TORCH_CHECK(t.sv.dim() >= 2 && t.pv.numel() == t.sv.numel() && t.pe_sun.numel() == t.sv.numel(), "solar_vis, pv_exact and pe_solar must be [Rs, S(, 1)] tensors of one size");
+    const int64_t Rs = t.sv.size(0), S = t.sv.numel() / Rs;
+    TORCH_CHECK(world >= 1, "world must be >= 1");
+    TORCH_CHECK(flags >= 1 && flags <= 7 && (flags & 3), "flags must select the adaptive colour loss (1) and / or the prior phase (2)");
+    const bool ada = flags & SNERF_LOSS_ADAPTIVE, prior = flags & SNERF_LOSS_PRIOR;
+    TORCH_CHECK(!ada || (t.alpha_c.has_value() && t.scale_c.has_value() && (!with_table || (t.logz_v.has_value() && t.logz_s.has_value()))), "the adaptive colour loss needs alpha_color, scale_color, logz_value, logz_slope");
+    TORCH_CHECK(!prior || (t.pe.has_value() && t.pe_sup.has_value()), "the prior phase needs pe and pe_supervised");
+    TORCH_CHECK(!(ada && prior) || (t.alpha_a.has_value() && t.scale_a.has_value()), "the adaptive loss in the prior phase needs alpha_alpha and scale_alpha");
+    snerf_loss_in in{};
+    in.n_rays = R; in.n_solar_rays = Rs; in.n_samples = (int)S; in.flags = (int)flags;
+    in.d_rgb = fptr(t.rgb); in.d_rgb_merged = optptr(t.rgb_merged, "rgb_merged", R * 3); in.d_gt = fptr(t.gt); in.d_albedo = fptr(t.albedo); in.d_sky = fptr(t.sky);
+    in.d_solar_vis = fptr(t.sv); in.d_pv_exact = fptr(t.pv); in.d_pe_solar = fptr(t.pe_sun);
+    if (prior) { in.d_pe = optptr(t.pe, "pe", R * S); in.d_pe_supervised = optptr(t.pe_sup, "pe_supervised", R * S); }
+    if (ada) {
+        in.d_alpha_color = optptr(t.alpha_c, "alpha_color", 3); in.d_scale_color = optptr(t.scale_c, "scale_color", 3);
+        if (with_table) {
+            for (const auto* tb : {&*t.logz_v, &*t.logz_s})
+                TORCH_CHECK(tb->is_cuda() && tb->scalar_type() == at::kDouble && tb->is_contiguous() && tb->numel() == 513, "logz_value / logz_slope must be contiguous float64 GPU tensors of 513 elements");
+            in.d_logz_value = t.logz_v->data_ptr<double>(); in.d_logz_slope = t.logz_s->data_ptr<double>();
+        }
+        if (prior) { in.d_alpha_alpha = optptr(t.alpha_a, "alpha_alpha", 1); in.d_scale_alpha = optptr(t.scale_a, "scale_alpha", 1); }
+    }
+    in.d_albedo_min_global = optptr(t.alb_min_global, "albedo_min_global", 3);
+    in.world = (int)world; in.w_solar = (float)w_solar; in.w_color = (float)w_color; in.w_alpha = (float)w_alpha;
+    return in;
+}
+// loss_terms_all(...) -> (vals[n], weights[n], aux[14]);  loss_terms_all_bwd(g_vals, ..., aux) -> the ten gradients (an empty tensor where the configuration lacks the input)
+std::tuple<Tensor, Tensor, Tensor> loss_terms_all(const Tensor& rgb, const c10::optional<Tensor>& rgb_merged, const Tensor& gt, const Tensor& albedo, const Tensor& sky,
+                                                  const Tensor& sv, const Tensor& pv, const Tensor& pe_sun, const c10::optional<Tensor>& pe, const c10::optional<Tensor>& pe_sup,
+                                                  const c10::optional<Tensor>& alpha_c, const c10::optional<Tensor>& scale_c, const c10::optional<Tensor>& alpha_a,
+                                                  const c10::optional<Tensor>& scale_a, const c10::optional<Tensor>& logz_v, const c10::optional<Tensor>& logz_s,
+                                                  const c10::optional<Tensor>& alb_min_global, int64_t world, int64_t flags, double w_solar, double w_color, double w_alpha) {
+    const snerf_loss_in in = loss_all_in({rgb, gt, albedo, sky, sv, pv, pe_sun, rgb_merged, pe, pe_sup, alpha_c, scale_c, alpha_a, scale_a, logz_v, logz_s, alb_min_global},
+                                         world, flags, w_solar, w_color, w_alpha);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(rgb.device());
+    const int n = snerf_loss_all_term_count((int)flags);
+    Tensor scratch = loss_all_scratch(rgb);
+    Tensor vals = at::empty({n}, rgb.options()), wts = at::empty({n}, rgb.options()), aux = at::empty({14}, rgb.options());
+    ck(snerf_loss_all_forward(&in, scratch.data_ptr(), mptr(vals), mptr(wts), mptr(aux), cur_stream(rgb)), "loss_terms_all");
+    return {vals, wts, aux};
+}
+std::vector<Tensor> loss_terms_all_bwd(const Tensor& g_vals, const Tensor& rgb, const c10::optional<Tensor>& rgb_merged, const Tensor& gt, const Tensor& albedo, const Tensor& sky,
+                                       const Tensor& sv, const Tensor& pv, const c10::optional<Tensor>& pe, const c10::optional<Tensor>& pe_sup,
+                                       const c10::optional<Tensor>& alpha_c, const c10::optional<Tensor>& scale_c, const c10::optional<Tensor>& alpha_a,
+                                       const c10::optional<Tensor>& scale_a, const Tensor& aux, int64_t flags) {
+    const c10::optional<Tensor> none;
+    // (the backward reads neither the sun rays' PE nor the table nor the global minimum: aux carries what the forward made of them; pv stands in for pe_solar)
+    snerf_loss_in in = loss_all_in({rgb, gt, albedo, sky, sv, pv, pv, rgb_merged, pe, pe_sup, alpha_c, scale_c, alpha_a, scale_a, none, none, none}, 1, flags, 0, 0, 0, false);
+    in.d_logz_value = in.d_logz_slope = (const double*)in.d_alpha_color;      // never read by the backward; non-NULL where the configuration is adaptive
+    check_dev_f32(g_vals, "g_vals"); check_dev_f32(aux, "aux");
+    TORCH_CHECK(g_vals.numel() == snerf_loss_all_term_count((int)flags) && aux.numel() == 14, "g_vals must hold one float per term, aux 14");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(rgb.device());
+    auto like = [&](const c10::optional<Tensor>& t) { return t.has_value() ? at::empty_like(*t) : at::empty({0}, rgb.options()); };
+    const bool ada = flags & SNERF_LOSS_ADAPTIVE, prior = flags & SNERF_LOSS_PRIOR;
+    std::vector<Tensor> o = {at::empty_like(rgb), like(rgb_merged), at::empty_like(albedo), at::empty_like(sky), at::empty_like(sv), like(prior ? pe : none),
+                             like(ada ? alpha_c : none), like(ada ? scale_c : none), like(ada && prior ? alpha_a : none), like(ada && prior ? scale_a : none)};
+    auto p = [](Tensor& t) -> float* { return t.numel() ? t.data_ptr<float>() : nullptr; };
+    const snerf_loss_grads G{p(o[0]), p(o[1]), p(o[2]), p(o[3]), p(o[4]), p(o[5]), p(o[6]), p(o[7]), p(o[8]), p(o[9])};
+    ck(snerf_loss_all_backward(&in, fptr(aux), fptr(g_vals), &G, cur_stream(rgb)), "loss_terms_all_bwd");
+    return o;
 }
 
 // ---- device ray loader: DataLoader(shuffle=True) + data_to_dict + SC_loader of mg_run_NeRF.py:74-84,122-133,229-264 as two kernel launches -----------
@@ -699,6 +781,11 @@ TORCH_LIBRARY(season_nerf, m) {
           "-> (Tensor, Tensor)");
     m.def("loss_terms_bwd(Tensor g_vals, Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor min, int world) "
           "-> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("loss_terms_all(Tensor rgb, Tensor? rgb_merged, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor pe_solar, Tensor? pe, "
+          "Tensor? pe_supervised, Tensor? alpha_color, Tensor? scale_color, Tensor? alpha_alpha, Tensor? scale_alpha, Tensor? logz_value, Tensor? logz_slope, "
+          "Tensor? albedo_min_global, int world, int flags, float w_solar, float w_color, float w_alpha) -> (Tensor, Tensor, Tensor)");
+    m.def("loss_terms_all_bwd(Tensor g_vals, Tensor rgb, Tensor? rgb_merged, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor? pe, "
+          "Tensor? pe_supervised, Tensor? alpha_color, Tensor? scale_color, Tensor? alpha_alpha, Tensor? scale_alpha, Tensor aux, int flags) -> Tensor[]");
     m.def("train_fwd_image(int trainer, Tensor top, Tensor bot, Tensor tvals, Tensor sun, Tensor time, bool train_bn, bool classic, int n_classes, "
           "Tensor? height_map, float trust, Tensor? trust_dev, Tensor[] params) -> Tensor[]");
     m.def("train_bwd_image(int trainer, Tensor(a!) grads, Tensor? g_rgb, Tensor? g_albedo, Tensor? g_sky, Tensor? g_pe, Tensor? rho_prior, float trust, "
@@ -729,6 +816,8 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("loader_next", loader_next);
     m.impl("loss_terms", loss_terms);
     m.impl("loss_terms_bwd", loss_terms_bwd);
+    m.impl("loss_terms_all", loss_terms_all);
+    m.impl("loss_terms_all_bwd", loss_terms_all_bwd);
     m.impl("fused_adam_", fused_adam_);
     m.impl("prior_density", prior_density);
     m.impl("train_fwd_image", train_fwd_image);

@@ -1124,6 +1124,55 @@ int snerf_loss_terms_backward(int64_t n_rays, int64_t n_solar_rays, int n_sample
     return SNERF_OK;
 }
 
+/* The same terms for the adaptive colour loss and / or the DSM-prior phase, with their weight vector (see include/season_nerf_hip.h).  Every argument is
+ * checked before any launch. */
+size_t snerf_loss_all_scratch_bytes(void) { return loss_all_scratch_bytes(); }
+int snerf_loss_all_term_count(int flags) {
+    if (flags < 0 || flags > 7 || !(flags & (SNERF_LOSS_ADAPTIVE | SNERF_LOSS_PRIOR)))
+        return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: flags must select the adaptive colour loss and / or the prior phase (the plain MSE configuration is snerf_loss_terms_*)");
+    return loss_all_idx(flags).n;
+}
+static int loss_all_args(LossAllArgs* a, const snerf_loss_in* in) {
+    if (!in) return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: NULL input description");
+    if (snerf_loss_all_term_count(in->flags) < 0) return SNERF_E_INVALID;
+    if (in->n_rays < 1 || in->n_solar_rays < 1 || in->n_samples < 1 || in->world < 1 || in->n_rays > 0x7fffffffll || in->n_solar_rays > (1ll << 40) / in->n_samples)
+        return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: ray / sample counts and world must be >= 1 (at most 2^31 - 1 image rays)");
+    if (!in->d_rgb || !in->d_gt || !in->d_albedo || !in->d_sky || !in->d_solar_vis || !in->d_pv_exact || !in->d_pe_solar)
+        return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: NULL image-ray or sun-ray input");
+    const bool ada = in->flags & SNERF_LOSS_ADAPTIVE, prior = in->flags & SNERF_LOSS_PRIOR;
+    if (ada && (!in->d_alpha_color || !in->d_scale_color || !in->d_logz_value || !in->d_logz_slope))
+        return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: the adaptive colour loss needs alpha, scale and the log-partition table");
+    if (prior && (!in->d_pe || !in->d_pe_supervised)) return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: the prior phase needs PE and PE_Supervised");
+    if (ada && prior && (!in->d_alpha_alpha || !in->d_scale_alpha))
+        return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: the adaptive loss in the prior phase needs the alpha loss object's alpha and scale");
+    if (!(in->w_solar == in->w_solar) || !(in->w_color == in->w_color) || !(in->w_alpha == in->w_alpha)) return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all: NaN weight");
+    *a = LossAllArgs{in->n_rays, in->n_solar_rays, in->n_samples, in->flags, in->d_rgb, in->d_rgb_merged, in->d_gt, in->d_albedo, in->d_sky, in->d_solar_vis, in->d_pv_exact,
+                     in->d_pe_solar, prior ? in->d_pe : nullptr, prior ? in->d_pe_supervised : nullptr, ada ? in->d_alpha_color : nullptr, ada ? in->d_scale_color : nullptr,
+                     (ada && prior) ? in->d_alpha_alpha : nullptr, (ada && prior) ? in->d_scale_alpha : nullptr, ada ? in->d_logz_value : nullptr,
+                     ada ? in->d_logz_slope : nullptr, in->d_albedo_min_global, in->d_albedo_min_global ? in->world : 1, in->w_solar, in->w_color, in->w_alpha};
+    return SNERF_OK;
+}
+int snerf_loss_all_forward(const snerf_loss_in* in, void* d_scratch, float* d_vals, float* d_weights, float* d_aux14, void* stream) {
+    LossAllArgs a;
+    RC(loss_all_args(&a, in));
+    if (!d_scratch || !d_vals || !d_weights || !d_aux14) return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all_forward: NULL scratch or output");
+    HIPCK(launch_loss_all(a, d_scratch, d_vals, d_weights, d_aux14, (hipStream_t)stream));
+    return SNERF_OK;
+}
+int snerf_loss_all_backward(const snerf_loss_in* in, const float* d_aux14, const float* d_g_vals, const snerf_loss_grads* out, void* stream) {
+    LossAllArgs a;
+    RC(loss_all_args(&a, in));
+    if (!d_aux14 || !d_g_vals || !out) return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all_backward: NULL aux, upstream gradient or output description");
+    const bool ada = in->flags & SNERF_LOSS_ADAPTIVE, prior = in->flags & SNERF_LOSS_PRIOR;
+    if (!out->d_g_rgb || !out->d_g_albedo || !out->d_g_sky || !out->d_g_solar_vis || (a.rgb_merged && !out->d_g_rgb_merged) || (prior && !out->d_g_pe) ||
+        (ada && (!out->d_g_alpha_color || !out->d_g_scale_color)) || (ada && prior && (!out->d_g_alpha_alpha || !out->d_g_scale_alpha)))
+        return snerf_set_error(SNERF_E_INVALID, "snerf_loss_all_backward: NULL gradient output for an input this configuration differentiates");
+    const LossAllGrads G{out->d_g_rgb, out->d_g_rgb_merged, out->d_g_albedo, out->d_g_sky, out->d_g_solar_vis, out->d_g_pe, out->d_g_alpha_color, out->d_g_scale_color,
+                         out->d_g_alpha_alpha, out->d_g_scale_alpha};
+    HIPCK(launch_loss_all_bwd(a, d_g_vals, d_aux14, G, (hipStream_t)stream));
+    return SNERF_OK;
+}
+
 /* the same update on caller-owned arenas (no trainer object): what season_nerf::fused_adam_ binds */
 int snerf_adam_step(float* d_params, const float* d_grads, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
                     int step, void* stream) {

@@ -246,6 +246,43 @@ struct LossArgs {
 hipError_t launch_loss_scratch_init(void* scratch, hipStream_t st);
 hipError_t launch_loss_terms(const LossArgs& a, void* scratch, float* vals5, float* minv3, hipStream_t st);
 hipError_t launch_loss_terms_bwd(const LossArgs& a, const float* g5, const float* minv3, float* d_rgb, float* d_albedo, float* d_sky, float* d_sv, hipStream_t st);
+// the same terms for Barron's adaptive colour loss and / or the DSM-prior phase (default solar model), with the weight vector and the gradients of the loss
+// objects' alpha and scale (train_kernels.hip, snerf_loss_all_* of include/season_nerf_hip.h)
+constexpr int kLossAdaptive = 1, kLossPrior = 2, kLossSkyDetached = 4;
+struct LossAllArgs {
+    int64_t R, Rs;
+    int S, flags;
+    const float *rgb, *rgb_merged, *gt, *albedo, *sky;      // [R,3]; rgb_merged optional: what `Color` is formed on
+    const float *sv, *pv, *pe_sun;                          // sun-ray pass [Rs,S]
+    const float *pe, *pe_sup;                               // prior: PE, PE_Supervised of the image rays [R,S]
+    const float *alpha_c, *scale_c, *alpha_a, *scale_a;     // adaptive: the colour loss object's alpha / scale [3]; adaptive + prior: the alpha loss object's [1]
+    const double *logz_v, *logz_s;                          // adaptive: log Z table, values and slopes [513], float64 (see ada_logz)
+    const float* alb_min_in;
+    int world;
+    float w_sc, w_color, w_alpha;                           // weights of the Solar_Correction family, Color / Color_ada, Alpha_Adjust / Alpha_Adjust_ada
+};
+struct LossAllIdx { int sc, sc2, sky, alb, aa_ada, c_ada, c_alpha, c_width, aa, a_alpha, a_width, color, n; };      // position of each term in the value vector (-1: absent)
+struct LossAllGrads { float *d_rgb, *d_rgb_merged, *d_albedo, *d_sky, *d_sv, *d_pe, *d_alpha_c, *d_scale_c, *d_alpha_a, *d_scale_a; };
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline LossAllIdx loss_all_idx(int flags) {      // the key order training.get_loss produces (Eval_Tools_2.py:361-450)
+    LossAllIdx I{0, 1, 2, 3, -1, -1, -1, -1, -1, -1, -1, -1, 0};
+    const bool ada = flags & kLossAdaptive, prior = flags & kLossPrior;
+    int n = 4;
+    if (!ada) { I.color = n++; if (prior) I.aa = n++; }
+    else {
+        if (prior) I.aa_ada = n++;
+        I.c_ada = n++; I.c_alpha = n++; I.c_width = n++;
+        if (prior) { I.aa = n++; I.a_alpha = n++; I.a_width = n++; }
+        I.color = n++;
+    }
+    I.n = n;
+    return I;
+}
+size_t loss_all_scratch_bytes();
+hipError_t launch_loss_all(const LossAllArgs& a, void* scratch, float* vals, float* wts, float* aux14, hipStream_t st);
+hipError_t launch_loss_all_bwd(const LossAllArgs& a, const float* g, const float* aux14, const LossAllGrads& G, hipStream_t st);
 hipError_t launch_adam_dev(float* params, const float* grads, float* m, float* v, int64_t n, const float* d_hyper6, hipStream_t st);
 // Adam on a flat arena (torch.optim.Adam semantics, no weight decay)
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, int step, hipStream_t st);

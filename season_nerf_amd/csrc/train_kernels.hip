@@ -1398,4 +1398,275 @@ hipError_t launch_loss_terms_bwd(const LossArgs& a, const float* g, const float*
     return hipGetLastError();
 }
 
+// ---- the loss terms of the configurations the three kernels above do not serve: Barron's adaptive colour loss (Eval_Tools_2.py:421-450) and the DSM-prior
+// phase (:243, :391-412), default solar model.  Same three launches - partial sums per block, one finalize wave, one elementwise backward - with two changes:
+//   * no floating-point atomics: every block STORES its sums (kLossAllSums doubles) and its three albedo keys, the finalize wave adds the blocks in a fixed
+//     order (lane l takes blocks l, l + 64, ...; then the shuffle tree) - the values are the same bits from launch to launch, and the scratch needs no
+//     initial state (every slot the finalize reads was written by the partial pass of the same call);
+//   * besides the sums of the terms, per channel of a loss object the sums of rho, d rho / d alpha and d rho / d scale: the gradients with respect to the
+//     loss object's alpha and scale are then saved sums times the upstream gradient (aux, written by the finalize), O(1) in the backward.
+// nll(x) = rho(x, alpha, c) + log c + log Z(alpha) as adaptive_loss.py states it: z = (x / c)^2, b = |alpha - 2| + eps, d = alpha +- eps,
+// rho = (b / d) ((z / b + 1)^(d / 2) - 1).  b, d and sign(alpha - 2) are formed in float32 from the float32 alpha the caller's torch ops formed, with the very
+// operations torch applies (the loss is logarithmically singular in alpha at 2: one ulp of b there moves d rho / d alpha by 10 %); everything per element
+// runs in float64 as expm1(p log1p(z / b)) - the float32 form cancels near alpha = 2.
+struct AdaParams { double b, d, p, A, c, inv_c2, sgn; };
+__device__ inline AdaParams ada_params(float alpha, float scale) {
+    const float eps = 1.1920928955078125e-07f;
+    const float am2 = alpha - 2.f;
+    const float bf = fabsf(am2) + eps;
+    const float df = alpha >= 0.f ? alpha + eps : alpha - eps;
+    AdaParams P;
+    P.b = (double)bf;
+    P.d = (double)df;
+    P.p = 0.5 * P.d;
+    P.A = P.b / P.d;
+    P.c = (double)scale;
+    P.inv_c2 = 1.0 / (P.c * P.c);
+    P.sgn = am2 > 0.f ? 1.0 : (am2 < 0.f ? -1.0 : 0.0);      // d|y|/dy at 0 is 0, as torch.abs differentiates
+    return P;
+}
+// rho and its derivatives with respect to alpha and c at residual x;  returns d rho / d x
+__device__ inline double ada_eval(const AdaParams& P, double x, double* rho, double* d_alpha, double* d_c) {
+    const double z = x * x * P.inv_c2, t = z / P.b, L = log1p(t), e = expm1(P.p * L), up = e + 1.0, q = up / (1.0 + t);      // q = u^(p-1), u = 1 + z / b
+    *rho = P.A * e;
+    *d_alpha = (P.sgn / P.d - P.b / (P.d * P.d)) * e + P.A * up * (0.5 * L - P.p * P.sgn * t / (P.b * (1.0 + t)));
+    *d_c = -(z / P.c) * q;
+    return x * P.inv_c2 * q;
+}
+__device__ inline double ada_dx(const AdaParams& P, double x) {
+    const double t = x * x * P.inv_c2 / P.b;
+    return x * P.inv_c2 * exp((P.p - 1.0) * log1p(t));
+}
+// log Z(alpha) and its derivative: the cubic Hermite form of adaptive_loss.log_base_partition_function on its table (values v, slopes s: 513 numbers
+// each on the grid alpha_i = 4 i / 512).  The table travels in float64: its derivative is 6 f (1 - f) (v1 - v0) / h + ..., and rounding v to float32 alone
+// moves it by 1.5e-5 at alpha = 0.2 (measured) - more than the float32 evaluation of the whole term is off there.
+__device__ inline void ada_logz(float alpha_f, const double* v, const double* s, double* val, double* dval) {
+    const double h = 4.0 / 512.0, alpha = (double)alpha_f;
+    const double a = fmin(fmax(alpha, 0.0), 4.0), u = a / h;
+    int i = (int)floor(u);
+    i = i < 0 ? 0 : (i > 511 ? 511 : i);
+    const double f = u - (double)i, g = 1.0 - f;
+    const double v0 = v[i], v1 = v[i + 1], s0 = h * s[i], s1 = h * s[i + 1];
+    *val = (1.0 + 2.0 * f) * g * g * v0 + f * g * g * s0 + f * f * (3.0 - 2.0 * f) * v1 + f * f * (f - 1.0) * s1;
+    const double dv = -6.0 * f * g * v0 + g * (1.0 - 3.0 * f) * s0 + 6.0 * f * g * v1 + (3.0 * f * f - 2.0 * f) * s1;
+    *dval = (alpha >= 0.0 && alpha <= 4.0) ? dv / h : 0.0;       // torch.clamp passes the gradient inside [min, max]
+}
+// sums per block: 0 Solar_Correction, 1 absorbed, 2 sky, 3 colour squared difference, 4-6 / 7-9 / 10-12 colour rho / d alpha / d c per channel,
+// 13 alpha squared difference, 14 / 15 / 16 alpha rho / d alpha / d c
+constexpr int kLossAllSums = 17, kLossAllMaxBlocks = 1024;
+size_t loss_all_scratch_bytes() { return (size_t)kLossAllMaxBlocks * (kLossAllSums * sizeof(double) + 3 * sizeof(unsigned long long)); }
+__global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs A, double* sums, unsigned long long* mins) {
+    const bool ada = A.flags & kLossAdaptive, prior = A.flags & kLossPrior;
+    __shared__ AdaParams P[4];
+    if (ada && threadIdx.x < 3) P[threadIdx.x] = ada_params(A.alpha_c[threadIdx.x], A.scale_c[threadIdx.x]);
+    if (ada && prior && threadIdx.x == 3) P[3] = ada_params(A.alpha_a[0], A.scale_a[0]);
+    __syncthreads();
+    double acc[kLossAllSums];
+#pragma unroll
+    for (int k = 0; k < kLossAllSums; ++k) acc[k] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const float* col = A.rgb_merged ? A.rgb_merged : A.rgb;       // `Color`: the merged colour in the prior phase in train mode (:413, :450)
+    unsigned long long mn[3] = {kMinInit, kMinInit, kMinInit};
+    for (int64_t rr = t0; rr < A.R; rr += stride) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int64_t i = rr * 3 + c;
+            const float gt = A.gt[i], d = col[i] - gt;
+            acc[3] += (double)(d * d);
+            const float x = (A.sky[i] - .5f) / .5f;
+            if (x > 0.f) acc[2] += (double)(x * x);
+            const unsigned long long key = ((unsigned long long)__float_as_uint(fmaxf(A.albedo[i], 0.f)) << 32) | (unsigned long long)(unsigned)rr;
+            mn[c] = key < mn[c] ? key : mn[c];
+            if (ada) {                                             // the adaptive loss sees the un-merged colour (:422)
+                double rho, da, dc;
+                ada_eval(P[c], (double)A.rgb[i] - (double)gt, &rho, &da, &dc);
+                acc[4 + c] += rho; acc[7 + c] += da; acc[10 + c] += dc;
+            }
+        }
+    }
+    __shared__ unsigned long long bmin[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        unsigned long long v = mn[c];
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long w = __shfl_xor(v, o);
+            v = w < v ? w : v;
+        }
+        if ((threadIdx.x & 63) == 0) bmin[c][threadIdx.x >> 6] = v;
+    }
+    for (int64_t j = t0; j < A.Rs * A.S; j += stride) {
+        const float v = A.sv[j], p = A.pv[j], d = v - p;
+        acc[0] += (double)(d * d);
+        acc[1] += (double)(A.pe_sun[j] * p * v);
+    }
+    if (prior)
+        for (int64_t j = t0; j < A.R * A.S; j += stride) {
+            const float pe = A.pe[j], su = A.pe_sup[j], d = pe - su;
+            acc[13] += (double)(d * d);
+            if (ada) {
+                double rho, da, dc;
+                ada_eval(P[3], (double)pe - (double)su, &rho, &da, &dc);
+                acc[14] += rho; acc[15] += da; acc[16] += dc;
+            }
+        }
+    __shared__ double red[kLossAllSums][4];
+#pragma unroll
+    for (int k = 0; k < kLossAllSums; ++k) {
+        double v = acc[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned long long v = bmin[threadIdx.x][0];
+        for (int k = 1; k < 4; ++k) v = bmin[threadIdx.x][k] < v ? bmin[threadIdx.x][k] : v;
+        mins[(size_t)blockIdx.x * 3 + threadIdx.x] = v;
+    }
+    if (threadIdx.x < kLossAllSums)
+        sums[(size_t)blockIdx.x * kLossAllSums + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+// aux [14]: the three albedo minima, the rows that own them (int bits; as loss_finalize_kernel), then d term / d alpha and d term / d scale of the colour
+// loss object per channel (6) and of the alpha loss object (2): what loss_all_bwd_kernel multiplies with the upstream gradients
+__global__ void loss_all_finalize_kernel(const LossAllArgs A, const double* sums, const unsigned long long* mins, int nblocks, float* vals, float* wts, float* aux) {
+    unsigned long long key[3] = {kMinInit, kMinInit, kMinInit};
+    double s[kLossAllSums];
+#pragma unroll
+    for (int k = 0; k < kLossAllSums; ++k) s[k] = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 64) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) key[c] = mins[(size_t)b * 3 + c] < key[c] ? mins[(size_t)b * 3 + c] : key[c];
+#pragma unroll
+        for (int k = 0; k < kLossAllSums; ++k) s[k] += sums[(size_t)b * kLossAllSums + k];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long w = __shfl_xor(key[c], o);
+            key[c] = w < key[c] ? w : key[c];
+        }
+#pragma unroll
+    for (int k = 0; k < kLossAllSums; ++k)
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);
+    if (threadIdx.x != 0) return;
+    const bool ada = A.flags & kLossAdaptive, prior = A.flags & kLossPrior;
+    const LossAllIdx I = loss_all_idx(A.flags);
+    const double Rs = (double)A.Rs, R = (double)A.R, RS = R * (double)A.S;
+    for (int k = 0; k < 14; ++k) aux[k] = 0.f;
+    vals[I.sc] = (float)(s[0] / Rs);
+    vals[I.sc2] = (float)(1.0 - s[1] / Rs);
+    vals[I.sky] = (float)(s[2] / (3.0 * R));
+    float hsum = 0.f;
+    for (int c = 0; c < 3; ++c) {
+        const float local = __uint_as_float((unsigned)(key[c] >> 32));
+        const float a = A.alb_min_in ? A.alb_min_in[c] : local;
+        aux[c] = a;
+        aux[3 + c] = __int_as_float(local == a ? (int)(unsigned)(key[c] & 0xffffffffull) : -1);
+        if (a < .2f) { const float u = 1.f - a / .2f; hsum += u * u; }
+    }
+    vals[I.alb] = hsum / (float)(R * A.world);
+    vals[I.color] = (float)(s[3] / (3.0 * R));
+    float w_sc = A.w_sc;
+    for (int k = 0; k < I.n; ++k) wts[k] = 1.f;                  // the mean alpha / scale entries: logged values, weight 1 (:431-447)
+    if (ada) {
+        double cst = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            double lz, dlz;
+            ada_logz(A.alpha_c[c], A.logz_v, A.logz_s, &lz, &dlz);
+            const double sc = (double)A.scale_c[c];
+            cst += log(sc) + lz;
+            aux[6 + c] = (float)(s[7 + c] / (3.0 * R) + dlz / 3.0);
+            aux[9 + c] = (float)(s[10 + c] / (3.0 * R) + 1.0 / (3.0 * sc));
+        }
+        vals[I.c_ada] = (float)((s[4] + s[5] + s[6]) / (3.0 * R) + cst / 3.0);
+        vals[I.c_alpha] = ((A.alpha_c[0] + A.alpha_c[1]) + A.alpha_c[2]) / 3.f;
+        const float width = ((A.scale_c[0] + A.scale_c[1]) + A.scale_c[2]) / 3.f;
+        vals[I.c_width] = width;
+        w_sc = A.w_sc / (width * width);                         // Solar_Correction(_2): sc_lambda / mean(scale)^2 (:437-438)
+        wts[I.c_ada] = A.w_color;
+    }
+    if (prior) {
+        vals[I.aa] = (float)(s[13] / RS);
+        wts[I.aa] = A.w_alpha;
+        if (ada) {
+            double lz, dlz;
+            ada_logz(A.alpha_a[0], A.logz_v, A.logz_s, &lz, &dlz);
+            const double sc = (double)A.scale_a[0];
+            vals[I.aa_ada] = (float)(s[14] / RS + log(sc) + lz);
+            aux[12] = (float)(s[15] / RS + dlz);
+            aux[13] = (float)(s[16] / RS + 1.0 / sc);
+            vals[I.a_alpha] = A.alpha_a[0];
+            vals[I.a_width] = A.scale_a[0];
+            wts[I.aa_ada] = A.w_alpha;
+        }
+    }
+    wts[I.sc] = w_sc; wts[I.sc2] = w_sc;
+    wts[I.sky] = A.w_sc; wts[I.alb] = A.w_sc;
+    wts[I.color] = A.w_color;
+}
+__global__ __launch_bounds__(256) void loss_all_bwd_kernel(const LossAllArgs A, const float* g, const float* aux, LossAllGrads G) {
+    const bool ada = A.flags & kLossAdaptive, prior = A.flags & kLossPrior, sky_detached = A.flags & kLossSkyDetached;
+    const LossAllIdx I = loss_all_idx(A.flags);
+    __shared__ AdaParams P[4];
+    if (ada && threadIdx.x < 3) P[threadIdx.x] = ada_params(A.alpha_c[threadIdx.x], A.scale_c[threadIdx.x]);
+    if (ada && prior && threadIdx.x == 3) P[3] = ada_params(A.alpha_a[0], A.scale_a[0]);
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const float g_sc = g[I.sc], g_sk = sky_detached ? 0.f : g[I.sky], g_al = g[I.alb];
+    const float g_col = ada ? 0.f : g[I.color];                                      // `Color` is a logged value beside the adaptive loss (:450)
+    const double g_cada = ada ? (double)g[I.c_ada] : 0.0, g_aada = (ada && prior) ? (double)g[I.aa_ada] : 0.0;
+    const float g_aa = prior ? g[I.aa] : 0.f;
+    const float inv3r = 1.f / (3.f * (float)A.R), invr = 1.f / (float)A.R, invrs = 1.f / (float)A.Rs;
+    const double inv3r_d = 1.0 / (3.0 * (double)A.R), invRS_d = 1.0 / ((double)A.R * (double)A.S);
+    if (blockIdx.x == 0 && ada) {
+        if (threadIdx.x < 3) {
+            G.d_alpha_c[threadIdx.x] = (float)g_cada * aux[6 + threadIdx.x];
+            G.d_scale_c[threadIdx.x] = (float)g_cada * aux[9 + threadIdx.x];
+        }
+        if (prior && threadIdx.x == 3) {
+            G.d_alpha_a[0] = (float)g_aada * aux[12];
+            G.d_scale_a[0] = (float)g_aada * aux[13];
+        }
+    }
+    for (int64_t i = t0; i < A.R * 3; i += stride) {
+        const int c = (int)(i % 3);
+        const float gt = A.gt[i];
+        const float mse = g_col * 2.f * ((A.rgb_merged ? A.rgb_merged[i] : A.rgb[i]) - gt) * inv3r;
+        float d_rgb = A.rgb_merged ? 0.f : mse;
+        if (A.rgb_merged) G.d_rgb_merged[i] = mse;
+        if (ada) d_rgb += (float)(g_cada * ada_dx(P[c], (double)A.rgb[i] - (double)gt) * inv3r_d);
+        G.d_rgb[i] = d_rgb;
+        const float x = (A.sky[i] - .5f) / .5f;
+        G.d_sky[i] = x > 0.f ? g_sk * 4.f * x * inv3r : 0.f;
+        const float a = aux[c];
+        const int own = __float_as_int(aux[3 + c]);
+        G.d_albedo[i] = ((int)(i / 3) == own && a < .2f) ? g_al * 2.f * (1.f - a / .2f) * (-1.f / .2f) * invr : 0.f;
+    }
+    for (int64_t j = t0; j < A.Rs * A.S; j += stride) G.d_sv[j] = g_sc * 2.f * (A.sv[j] - A.pv[j]) * invrs;
+    if (prior)
+        for (int64_t j = t0; j < A.R * A.S; j += stride) {
+            const float pe = A.pe[j], su = A.pe_sup[j];
+            double d = (double)g_aa * 2.0 * (double)(pe - su) * invRS_d;
+            if (ada) d += g_aada * ada_dx(P[3], (double)pe - (double)su) * invRS_d;
+            G.d_pe[j] = (float)d;
+        }
+}
+static int64_t loss_all_blocks(const LossAllArgs& a, int64_t cap) {
+    int64_t n = a.Rs * a.S > a.R * 3 ? a.Rs * a.S : a.R * 3;
+    if ((a.flags & kLossPrior) && a.R * a.S > n) n = a.R * a.S;
+    int64_t b = (n + 255) / 256;
+    return b > cap ? cap : (b < 1 ? 1 : b);
+}
+hipError_t launch_loss_all(const LossAllArgs& a, void* scratch, float* vals, float* wts, float* aux, hipStream_t st) {
+    double* sums = (double*)scratch;
+    unsigned long long* mins = (unsigned long long*)(sums + (size_t)kLossAllMaxBlocks * kLossAllSums);
+    const int64_t b = loss_all_blocks(a, kLossAllMaxBlocks);
+    hipLaunchKernelGGL(loss_all_partial_kernel, dim3((unsigned)b), dim3(256), 0, st, a, sums, mins);
+    hipLaunchKernelGGL(loss_all_finalize_kernel, dim3(1), dim3(64), 0, st, a, (const double*)sums, (const unsigned long long*)mins, (int)b, vals, wts, aux);
+    return hipGetLastError();
+}
+hipError_t launch_loss_all_bwd(const LossAllArgs& a, const float* g, const float* aux, const LossAllGrads& G, hipStream_t st) {
+    hipLaunchKernelGGL(loss_all_bwd_kernel, dim3((unsigned)loss_all_blocks(a, 2048)), dim3(256), 0, st, a, g, aux, G);
+    return hipGetLastError();
+}
+
 }  // namespace snerf

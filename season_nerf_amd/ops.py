@@ -102,6 +102,19 @@ def _register_fakes():
     def _(g_vals, rgb, gt, albedo, sky, solar_vis, pv_exact, min, world):
         return torch.empty_like(rgb), torch.empty_like(albedo), torch.empty_like(sky), torch.empty_like(solar_vis)
 
+    @reg("season_nerf::loss_terms_all")
+    def _(rgb, rgb_merged, gt, albedo, sky, solar_vis, pv_exact, pe_solar, pe, pe_supervised, alpha_color, scale_color, alpha_alpha, scale_alpha, logz_value,
+          logz_slope, albedo_min_global, world, flags, w_solar, w_color, w_alpha):
+        n = {1: 8, 3: 12, 2: 6}[flags & 3]
+        return rgb.new_empty(n), rgb.new_empty(n), rgb.new_empty(14)
+
+    @reg("season_nerf::loss_terms_all_bwd")
+    def _(g_vals, rgb, rgb_merged, gt, albedo, sky, solar_vis, pv_exact, pe, pe_supervised, alpha_color, scale_color, alpha_alpha, scale_alpha, aux, flags):
+        ada, prior = bool(flags & 1), bool(flags & 2)
+        like = lambda t, on=True: torch.empty_like(t) if (t is not None and on) else rgb.new_empty(0)
+        return [torch.empty_like(rgb), like(rgb_merged), torch.empty_like(albedo), torch.empty_like(sky), torch.empty_like(solar_vis), like(pe, prior),
+                like(alpha_color, ada), like(scale_color, ada), like(alpha_alpha, ada and prior), like(scale_alpha, ada and prior)]
+
     @reg("season_nerf::train_fwd_image")
     def _(trainer, top, bot, tvals, sun, time, train_bn, classic, n_classes, height_map, trust, trust_dev, params):
         R, S, C = top.shape[0], tvals.numel(), n_classes

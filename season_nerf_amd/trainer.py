@@ -152,7 +152,8 @@ class GraphedTrainStep:
     the schedule, bias corrections: device-resident, `FusedAdam.make_capturable`) and launches the graph.
 
     Covered: the reference's default run - solar rays on, default solar model, fused Adam - in all of its phases: MSE colour loss (the five loss terms
-    of ONE fused kernel) or Barron's adaptive loss (the generic loss terms in torch ops; the second Adam on the loss object's alpha / scale switches
+    of ONE fused kernel) or Barron's adaptive loss (the generic loss terms in torch ops, or - `fused_loss="all"` - the terms of season_nerf::loss_terms_all,
+    which also serves the MSE loss in the prior phase; the second Adam on the loss object's alpha / scale switches
     to torch's capturable form: step count and learning rate in device tensors, the OneCycle schedule fills the latter before each replay), with or
     without the DSM prior of phase 1 (its trust factor current_step / n_steps sits in ONE device float the composite kernels read at run time -
     snerf_composite_rays_dt / snerf_trainer_backward_image_dt - refreshed before each replay).
@@ -380,6 +381,8 @@ class GraphedTrainStep:
                 # capture time would pull the default stream into the capture (a segfault in hipStreamEndCapture on ROCm 7.2).  Hand out detached values, so the
                 # graph dies here and the captured backward creates its accumulators on the capture stream.
                 loss = tool.last_loss = {k: [v[0].detach() if torch.is_tensor(v[0]) else v[0], v[1]] for k, v in loss.items()}
+            elif getattr(loss, "wvec", None) is not None and tool.optim2 is not None:
+                loss = tool.last_loss = self._snapshot(loss)      # the fused adaptive terms reach the same accumulators through alpha() / scale(): same reason
             return loss
         if self.loader is None and data_dict["Top"].shape[0] != self.R:
             raise ValueError(f"GraphedTrainStep: captured for {self.R} rays, got {data_dict['Top'].shape[0]}")
@@ -403,16 +406,17 @@ class GraphedTrainStep:
         self.calls += 1
         return loss
 
-    def _snapshot(self):
-        """A LossDict of this step's values that the next replay does not overwrite (clone of the 5-float vector)."""
-        src = self.loss
+    def _snapshot(self, src=None):
+        """A LossDict of this step's values that the next replay does not overwrite (clone of the value vector, and of the weight vector where there is one)."""
+        src = self.loss if src is None else src
         if getattr(src, "vec", None) is None:          # the generic terms (adaptive loss, prior phase): one small clone per term
             return {k: [v[0].detach().clone() if torch.is_tensor(v[0]) else v[0], v[1].detach().clone() if torch.is_tensor(v[1]) else v[1]] for k, v in src.items()}
         vec = src.vec.detach().clone()
+        wvec = src.wvec.detach().clone() if getattr(src, "wvec", None) is not None else None
         out = type(src)()
         for i, k in enumerate(src.names):
-            out[k] = [vec[i], src[k][1]]
-        out.vec, out.names = vec, src.names
+            out[k] = [vec[i], wvec[i] if torch.is_tensor(src[k][1]) else src[k][1]]
+        out.vec, out.names, out.wvec = vec, src.names, wvec
         return out
 
 
@@ -429,8 +433,11 @@ class T_NeRF_Net_Tool(Net_tool):
     """
 
     def __init__(self, args, training_DSM, GT_DSM, device, H, WC, *, get_data=None, solar_vecs=None, writer=None, eval_img=None,
-                 fused_adam=True, log_every=1, ada_factory=None, use_graph=False, train_loader=None, val_loader=None):
+                 fused_adam=True, log_every=1, ada_factory=None, use_graph=False, train_loader=None, val_loader=None, fused_loss="default"):
         from .network import T_NeRF
+        if fused_loss not in ("default", "all"):
+            raise ValueError(f"T_NeRF_Net_Tool: fused_loss must be 'default' or 'all', got {fused_loss!r}")
+        self.fused_loss = fused_loss               # carried to every phase's evaluator (All_in_One_Eval.fused_loss)
         self.args, self.device = args, torch.device(device)
         self.writer, self.log_every, self.fused_adam = writer, max(int(log_every), 1), fused_adam
         self.n_steps = n_steps = args.max_train_steps
@@ -497,6 +504,7 @@ class T_NeRF_Net_Tool(Net_tool):
                                              base_solar_vecs=self.solar_vecs)
         else:
             raise ValueError(f"T_NeRF_Net_Tool: invalid learning mode {mode}")
+        self.eval_tool.fused_loss = self.fused_loss
         self._build_optimisers(args.lr, self.Section_Steps[mode - 1], args.lr_alpha_scale)
         self._graphed = None                   # a new evaluator and new optimisers: a captured step of the previous phase is stale
 

@@ -340,7 +340,22 @@ def _register_autograd():
         d_rgb, d_alb, d_sky, d_sv = ops.loss_terms_bwd(g_vals.contiguous(), rgb, gt, albedo, sky, sv, pv, minv, ctx.world)
         return d_rgb, None, d_alb, d_sky, d_sv, None, None, None, None
 
+    def setup_loss_all(ctx, inputs, output):
+        rgb, rgb_m, gt, albedo, sky, sv, pv, pe_sun, pe, pe_sup, a_c, s_c, a_a, s_a = inputs[:14]
+        ctx.save_for_backward(rgb, rgb_m, gt, albedo, sky, sv, pv, pe, pe_sup, a_c, s_c, a_a, s_a, output[2])
+        ctx.flags = int(inputs[18])
+
+    def bwd_loss_all(ctx, g_vals, g_weights, g_aux):
+        # the weight vector and aux are values only; d[i] is an empty tensor where the configuration lacks the input, zeros where the term is detached
+        t = ctx.saved_tensors
+        d = ops.loss_terms_all_bwd(g_vals.contiguous(), *t, ctx.flags)
+        ada, prior, sky_detached = bool(ctx.flags & 1), bool(ctx.flags & 2), bool(ctx.flags & 4)
+        on = lambda g, cond: g if cond else None
+        return (d[0], on(d[1], t[1] is not None and not ada), None, d[2], on(d[3], not sky_detached), d[4], None, None, on(d[5], prior), None,
+                on(d[6], ada), on(d[7], ada), on(d[8], ada and prior), on(d[9], ada and prior), None, None, None, None, None, None, None, None)
+
     torch.library.register_autograd("season_nerf::loss_terms", bwd_loss, setup_context=setup_loss)
+    torch.library.register_autograd("season_nerf::loss_terms_all", bwd_loss_all, setup_context=setup_loss_all)
     torch.library.register_autograd("season_nerf::train_fwd_image", bwd_image, setup_context=setup_image)
     torch.library.register_autograd("season_nerf::train_fwd_points", bwd_points, setup_context=setup_points)
     torch.library.register_autograd("season_nerf::train_fwd_solar", bwd_solar, setup_context=setup)
@@ -482,8 +497,11 @@ class LossDict(dict):
     instead of one multiply and one add per term (trainer.Net_tool.train_step)."""
     vec = None
     names = ()
+    wvec = None            # the weights as a device vector next to `vec` (season_nerf::loss_terms_all: two of them depend on the loss object's scale)
 
     def total(self):
+        if self.wvec is not None:
+            return (self.vec * self.wvec).sum()
         w = [self[k][1] for k in self.names]
         key = tuple(float(x) for x in w)
         cache = LossDict._wcache
@@ -527,6 +545,81 @@ def _fused_loss(ev, net, out, so, gt, weight):
     L["Albedo_Color"] = [v[3], w_sc]
     L["Color"] = [v[4], weight["Color"]]
     L.vec, L.names = vals, ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color")
+    return L
+
+
+_ALL_NAMES = {
+    1: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color_ada", "Color_alpha", "Color_width", "Color"),
+    3: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Alpha_Adjust_ada", "Color_ada", "Color_alpha", "Color_width", "Alpha_Adjust",
+        "Alpha_alpha", "Alpha_width", "Color"),
+    2: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color", "Alpha_Adjust")}      # flags & 3 (adaptive 1, prior 2) -> get_loss's key order
+_ALL_LOGGED = ("Solar_Correction_2", "Color_alpha", "Color_width", "Alpha_alpha", "Alpha_width")                    # values only, in every configuration
+
+
+def _fused_loss_all_ok(ev, args, out, so):
+    """The opt-in op (`All_in_One_Eval.fused_loss == "all"`) serves what `_fused_loss_ok` refuses except the classic solar model: Barron's adaptive colour
+    loss and / or the DSM-prior phase.  Everything it cannot take - a loss object with a fixed alpha or scale or of another class, CPU tensors, a missing
+    PE_Supervised - stays on the tensor ops."""
+    import os
+    from .adaptive_loss import AdaptiveLossFunction
+    if not (os.environ.get("SNERF_FUSED_LOSS", "1") != "0" and getattr(ev, "fused_loss", "default") == "all" and args.Use_Solar and not args.Solar_Type_2
+            and (ev.use_prior or not ev.use_MSE_loss) and isinstance(out, _TrainOut) and out.sky_ray is not None and out["Rendered_Col"].is_cuda
+            and so["Solar_Vis"].is_cuda):
+        return False
+    if ev.use_prior and (out.get("PE_Supervised") is None or out.get("Rendered_Col_Merged") is None):
+        return False
+    if not ev.use_MSE_loss:
+        mods = ev.ada_loss if isinstance(ev.ada_loss, (list, tuple)) else [ev.ada_loss]
+        if len(mods) != (2 if ev.use_prior else 1) or [getattr(m, "num_dims", None) for m in mods] != [3, 1][:len(mods)]:
+            return False
+        for m in mods:
+            if not isinstance(m, AdaptiveLossFunction) or m.latent_alpha is None or m.latent_scale is None or not m.latent_alpha.is_cuda or m.float_dtype != torch.float32:
+                return False
+    return True
+
+
+def _fused_loss_all(ev, net, out, so, gt, weight, train_mode):
+    """The terms of the adaptive colour loss and / or the DSM-prior phase from ONE forward op (two launches) and one backward launch (csrc/train_kernels.hip
+    loss_all_*_kernel).  alpha and scale enter as the tensors the loss object's own alpha() / scale() form - the kernel sees the very float32 alpha - and
+    autograd chains their gradients to the latents.  -> LossDict with `vec`, `wvec` and `names`; each entry [value, weight] as the tensor-op path gives it."""
+    from . import parallel
+    from .adaptive_loss import table_on
+    from .network import _ops
+    _register_autograd()
+    ops = _ops()
+    ada, prior = not ev.use_MSE_loss, bool(ev.use_prior)
+    flags = (1 if ada else 0) | (2 if prior else 0) | (4 if prior else 0)        # Sky_Color_Var is detached in the prior phase (:388)
+    store = getattr(net, "_param_store", None)
+    group = store.bn_sync[0] if (store is not None and store.bn_sync is not None) else None
+    g_min, world = None, 1
+    if parallel.data_parallel(group):
+        g_min, world = parallel.global_min(out["Albedo_Color"].detach().min(0).values, group)
+    a_c = s_c = a_a = s_a = lz_v = lz_s = None
+    if ada:
+        mods = ev.ada_loss if prior else [ev.ada_loss]
+        a_c, s_c = mods[0].alpha(), mods[0].scale()
+        if prior:
+            a_a, s_a = mods[1].alpha(), mods[1].scale()
+        lz_v, lz_s = table_on(a_c.device, torch.float64)
+    pe = out["PE"].contiguous() if prior else None
+    vals, wts, _ = ops.loss_terms_all(out["Rendered_Col"], out["Rendered_Col_Merged"] if (prior and train_mode) else None, gt.contiguous(), out["Albedo_Color"],
+                                      out.sky_ray, so["Solar_Vis"], so["PV_Exact"].detach(), so["PE"].detach(), pe,
+                                      out["PE_Supervised"].detach().contiguous() if prior else None, a_c, s_c, a_a, s_a, lz_v, lz_s, g_min, world, flags,
+                                      float(weight["Solar_Correction"]), float(weight["Color"]), float(weight["Alpha_Adjust"]))
+    wts = wts.detach()
+    names = _ALL_NAMES[flags & 3]
+    v, w = vals.unbind(0), wts.unbind(0)
+    host_w = {"Sky_Color_Var": weight["Solar_Correction"], "Albedo_Color": weight["Solar_Correction"], "Color": weight["Color"], "Color_ada": weight["Color"],
+              "Alpha_Adjust": weight["Alpha_Adjust"], "Alpha_Adjust_ada": weight["Alpha_Adjust"]}
+    L = LossDict()
+    for i, k in enumerate(names):
+        value_only = k in _ALL_LOGGED or (k == "Sky_Color_Var" and prior) or (k == "Color" and ada)
+        if k in ("Solar_Correction", "Solar_Correction_2"):
+            wk = w[i] if ada else weight["Solar_Correction"]         # beside the adaptive loss: sc_lambda / mean(scale)^2, a device scalar (:437-438)
+        else:
+            wk = host_w.get(k, 1.)
+        L[k] = [v[i].detach() if value_only else v[i], wk]
+    L.vec, L.wvec, L.names = vals, wts, names
     return L
 
 
@@ -630,6 +723,8 @@ def get_loss(ev, data_dict, net, current_step, train_mode):
         so = ev.eval_Rho_Only({"Top": starts, "Bot": ends, "Sun_Angle": vec, "Time_Encoded": stime}, net, train_mode, current_step)
         if _fused_loss_ok(ev, args, out, so):
             return _fused_loss(ev, net, out, so, data_dict["GT_Color"].to(dev), weight)
+        if _fused_loss_all_ok(ev, args, out, so):
+            return _fused_loss_all(ev, net, out, so, data_dict["GT_Color"].to(dev), weight, train_mode)
         Loss["Solar_Correction"] = [torch.mean(torch.sum(_sq(so["Solar_Vis"] - so["PV_Exact"].detach()), 1)), weight["Solar_Correction"]]
         absorb = torch.mean(1 - torch.sum(so["PE"].detach() * so["PV_Exact"].detach() * so["Solar_Vis"], 1))
         Loss["Solar_Correction_2"] = [absorb.detach() if not args.Solar_Type_2 else absorb, weight["Solar_Correction"]]
