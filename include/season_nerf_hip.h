@@ -289,6 +289,28 @@ int snerf_field_ray_surface(const snerf_model* m, int64_t n_rays, int n_samples,
 int snerf_field_shadow_walk(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_sun,
                             const float* d_tvals, int flags, float* d_out, void* stream);
 
+/* ---- solar audit: the learned sun visibility against the one the density implies, scored inside the field kernel.
+ * The reference ends a study of a trained scene by rendering each (view, sun) pair with component_render_by_dir(include_exact_solar=True) and comparing, sample
+ * by sample, Est_Solar_Vis with Exact_Solar (T_NeRF_Eval_Utils/mg_Advanced_Solar.py eval_solar_data; the exact block is mg_Img_Eval.py:57-70).  One launch takes
+ * the primary rays of a view (d_top, d_bot [n_rays,3], d_tvals [S]) and ONE sun direction sun3 (three doubles in HOST memory, read before the launch), forms for
+ * every sample s of every ray the secondary ray towards the sun
+ *   p = top (1 - t_s) + bot t_s,   K = (1 - p_z) / (float)sun_z (fp32),   top2 = (float)((double)p + (double)K sun3),   bot2 = p,
+ * walks its S samples from the point outwards, 32 per pass, through the density-only network and scores
+ *   E_s = exp(-sum_{j<S-1} rho_j delta2)         the exact visibility (delta2 = ||top2 - bot2|| / S; the last sample never counts)
+ * against the caller's V = d_est_vis [n_rays,S] (the learned visibility, e.g. of the sun walk) and PS = d_ps [n_rays,S] (snerf_composite_rays).  Per primary
+ * ray d_out [n_rays,8] (32-byte aligned):
+ *   [0] number of samples with E > .5 and V > .5      [1] with E > .5      [2] with V > .5          (floats holding integers)
+ *   [3] sum_s E_s PS_s       [4] sum_s V_s PS_s       [5] sum_s PS_s       [6] sum_s (E_s - V_s)^2       [7] sum_s |E_s - V_s|
+ * From [0..2] and S follow TP / FP / FN / TN of All_Solar_Vis, from [3] and [4] against .3 those of Surface_Solar_Vis.  d_exact [n_rays,S] (may be NULL)
+ * receives E per sample, the reference's Exact_Solar; it equals snerf_field_ray_visibility on the same secondary rays.  The sums are added in a fixed order:
+ * two launches give the same bits.  flags bit1 = a sample of a secondary ray outside [-1,1]^3 gets delta 0; bit2 = no early-out; any other bit is refused.
+ * Early-out: once every secondary ray of a workgroup's group of samples has passed optical depth 18 the group's remaining passes are skipped (E < exp(-18)).
+ * SNERF_E_INVALID, before anything is launched, for a NULL required pointer, n_rays < 0, n_samples < 1, a sun that is not finite or has sun_z <= 0, d_out
+ * off 32 bytes, and unless the model's resolved precision is SNERF_PREC_BF16X3 (width 64, 256 or 512).  n_rays == 0 succeeds and launches nothing. */
+int snerf_field_solar_audit(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals,
+                            const double* sun3 /* host */, const float* d_est_vis, const float* d_ps, int flags, float* d_out, float* d_exact,
+                            void* stream);
+
 /* ---- frame walk: the frames of the reference's fly-through films with the shading and compositing inside the field kernel.
  * The reference renders a film frame from a slab of parallel rays (sample_rays_projective, T_NeRF_Eval_Utils/mg_movie_maker.py:52-70): T_NeRF.forward on
  * every sample, the density zeroed outside the cube, and a compositing of its own with the learned visibility applied per sample (get_Img.eval_rays,

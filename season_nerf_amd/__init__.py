@@ -20,6 +20,7 @@ from . import shadow_eval  # noqa: E402,F401
 from .shadow_eval import ShadowWalk, shadow_walk, eval_shadow_data, shadow_anaylysis, Test_Shadow_Points  # noqa: E402,F401
 from . import movie  # noqa: E402,F401
 from .movie import FrameWalk, frame_walk, frame_end_planes, sample_rays_projective, get_Img  # noqa: E402,F401
+from .solar_audit import SolarAudit, solar_audit, audit_by_dir, eval_solar_data, advanced_solar  # noqa: E402,F401
 from . import validation  # noqa: E402,F401
 from .validation import DSM_Distance, eval_img, image_error  # noqa: E402,F401
 from . import loader  # noqa: E402,F401

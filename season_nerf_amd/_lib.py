@@ -103,6 +103,7 @@ def lib():
     L.snerf_field_sun_walk_rays.argtypes = [vp, i64, i32, vp, vp, vp, i32, vp, vp, C.POINTER(FieldOut), vp]
     L.snerf_field_ray_surface.argtypes = [vp, i64, i32, vp, vp, vp, i32, vp, vp]
     L.snerf_field_shadow_walk.argtypes = [vp, i64, i32, vp, vp, vp, vp, i32, vp, vp]
+    L.snerf_field_solar_audit.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.snerf_field_frame_walk.argtypes = [vp, i64, i32, vp, vp, vp, C.c_float, vp, vp, i32, vp, i32, vp, vp]
     L.snerf_composite_sun_walk.argtypes = [i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(SunWalkOut), vp]
     f32p = vp
@@ -191,7 +192,7 @@ EXPORTS = ["snerf_last_error", "snerf_abi_version", "snerf_model_create", "snerf
            "snerf_model_set_precision", "snerf_model_precision", "snerf_model_i8_estimate", "snerf_model_resolve_precision",
            "snerf_model_pack_host", "snerf_group_forward", "snerf_set_group_kernel", "snerf_field_forward_points", "snerf_field_forward_rays", "snerf_field_ray_visibility",
            "snerf_composite_rays", "snerf_composite_rays_dt", "snerf_composite_sweep",
-           "snerf_model_pack_sun_walk_host", "snerf_field_sun_walk_rays", "snerf_composite_sun_walk", "snerf_field_ray_surface", "snerf_field_shadow_walk", "snerf_field_frame_walk", "snerf_render_workspace_bytes", "snerf_render_rays", "snerf_rays_from_camera", "snerf_ray_grid", "snerf_field_kernel_info",
+           "snerf_model_pack_sun_walk_host", "snerf_field_sun_walk_rays", "snerf_composite_sun_walk", "snerf_field_ray_surface", "snerf_field_shadow_walk", "snerf_field_solar_audit", "snerf_field_frame_walk", "snerf_render_workspace_bytes", "snerf_render_rays", "snerf_rays_from_camera", "snerf_ray_grid", "snerf_field_kernel_info",
            "snerf_prior_density", "snerf_surface_distance", "snerf_image_error", "snerf_transmittance",
            "snerf_linear_scratch_bytes", "snerf_linear_forward", "snerf_linear_dgrad", "snerf_linear_wgrad",
            "snerf_trainer_create", "snerf_trainer_destroy", "snerf_trainer_classes", "snerf_trainer_param_floats", "snerf_trainer_buffer_floats",

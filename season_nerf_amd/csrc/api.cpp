@@ -676,6 +676,42 @@ int snerf_field_shadow_walk(const snerf_model* m, int64_t n_rays, int n_samples,
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "shadow walk kernel launch");
 }
 
+int snerf_field_solar_audit(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals,
+                            const double* sun3, const float* d_est_vis, const float* d_ps, int flags, float* d_out, float* d_exact, void* stream) {
+    if (n_rays < 0 || n_samples < 1 || !d_top || !d_bot || !d_tvals || !sun3 || !d_est_vis || !d_ps || !d_out || ((uintptr_t)d_out & 31))
+        return fail(SNERF_E_INVALID, "snerf_field_solar_audit: bad argument (n_rays >= 0, n_samples >= 1, no NULL pointer but d_exact, d_out 32-byte aligned)");
+    if (!std::isfinite(sun3[0]) || !std::isfinite(sun3[1]) || !std::isfinite(sun3[2]) || !(sun3[2] > 0.0) || !((float)sun3[2] > 0.f))
+        return fail(SNERF_E_INVALID, "snerf_field_solar_audit: the sun direction must be finite with sun_z > 0");
+    if (flags & ~6) return fail(SNERF_E_INVALID, "snerf_field_solar_audit: flags has bits other than 2 (outside the cube: delta 0) and 4 (no early-out)");
+    if (!m) return fail(SNERF_E_INVALID, "snerf_field_solar_audit: NULL model");
+    int rc = check_ready(m);
+    if (rc) return rc;
+    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
+        return fail(SNERF_E_INVALID, "snerf_field_solar_audit: the solar-audit kernels exist for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
+    if (n_rays == 0) return SNERF_OK;
+    const bool ks = ks_width(m->W);
+    SolarAuditArgs a{};
+    a.m.stream = ks ? m->d_stream_ks : m->d_stream[PROG_FIELD];
+    a.m.stream_bytes = (uint32_t)(ks ? field_variant_chunks_ks(m->W, m->C, 3) : field_variant_chunks(m->W, m->C, 3)) * kChunkBytes;
+    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
+    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
+    a.m.n = n_rays;                // primary rays: a workgroup walks the secondary rays of one ray's samples, four (width 512: two) at a time
+    a.m.n_classes = m->C;
+    a.m.top = d_top;
+    a.m.bot = d_bot;
+    a.m.tvals = d_tvals;
+    a.m.n_samples = n_samples;
+    a.m.group_size = 1;
+    a.m.ray_flags = flags & 6;     // bit 3 clear: passes from the point outwards
+    for (int k = 0; k < 3; ++k) a.sun[k] = sun3[k];
+    a.est_vis = d_est_vis;
+    a.ps = d_ps;
+    a.out = d_out;
+    a.exact = d_exact;
+    hipError_t e = launch_solar_audit(m->W, a, m->n_cu, (hipStream_t)stream);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "solar audit kernel launch");
+}
+
 int snerf_field_frame_walk(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals, float delta,
                            const float* d_sun, const float* d_sky, int n_times, const float* d_class_vecs, int flags, float* d_out, void* stream) {
     if (n_rays < 0 || n_samples < 2 || !d_top || !d_bot || !d_tvals || !d_sun || !d_sky || !d_class_vecs || !d_out || ((uintptr_t)d_out & 63) ||

@@ -89,6 +89,19 @@ struct FrameWalkArgs {
     float* out;
 };
 
+// Solar audit (solar_audit_kernel / solar_audit_ks_kernel, mlp_device.h RayAudit): the density-only walk of variant 3 along the secondary rays of the samples of
+// primary rays, formed in the kernel, scored against the learned visibility.  m as in RaySurfaceArgs (m.n = PRIMARY rays, m.top / m.bot theirs), m.ray_flags
+// without bit 3 (passes from the point outwards); sun = the sun direction in float64, by value; est_vis, ps [n, S]; out [n,8] = {n(E > .5 and V > .5),
+// n(E > .5), n(V > .5), sum E PS, sum V PS, sum PS, sum (E - V)^2, sum |E - V|} per primary ray, 32-byte aligned; exact [n, S] or NULL = E per sample.
+struct SolarAuditArgs {
+    MlpArgs m;
+    double sun[3];
+    const float* est_vis;
+    const float* ps;
+    float* out;
+    float* exact;
+};
+
 struct CompOutDev {
     float *rgb, *albedo, *pv, *pe, *ps, *delta, *shadow, *acc, *surf_loc, *surf_dist;
 };
@@ -170,6 +183,8 @@ hipError_t launch_shadow_walk(int W, const ShadowWalkArgs& a, int n_cu, hipStrea
 hipError_t launch_shadow_walk_ks(int W, const ShadowWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_frame_walk(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st);                      // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_frame_walk_ks(int W, const FrameWalkArgs& a, int n_cu, hipStream_t st);
+hipError_t launch_solar_audit(int W, const SolarAuditArgs& a, int n_cu, hipStream_t st);                    // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
+hipError_t launch_solar_audit_ks(int W, const SolarAuditArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_sun_walk(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);                          // kernels.hip (W = 64, 256), kernels_ks.hip (W = 512)
 hipError_t launch_sun_walk_ks(int W, const SunWalkArgs& a, int n_cu, hipStream_t st);
 hipError_t launch_mlp_i8(int W, int variant, const MlpArgs& a, int n_cu, hipStream_t st);                // kernels_i8.hip (field program only)

@@ -1031,4 +1031,50 @@ hipError_t launch_frame_walk(int W, const FrameWalkArgs& a, int n_cu, hipStream_
     return launch_walk(W, frame_walk_kernel<64>, frame_walk_kernel<256>, 3, kFrameLdsFloats * 4, a, n_cu, st);
 }
 
+// =====================================================================================================
+// Solar audit: the VARIANT 3 walk of mlp_kernel (32 samples per pass from the point outwards, the density-only stream: FIELD_TRUNK alone, the depth-18 vote) along
+// secondary rays formed here (mlp_device.h RayAudit; mg_Advanced_Solar.py eval_solar_data, mg_Img_Eval.py:57-70).  A workgroup owns primary ray `ray` and walks
+// the groups of four consecutive samples of it, wave w the secondary ray of sample 4 group + w; the scores wait in LDS rows behind the vote words and leave as one
+// 32-byte row per primary ray: no [R S,3] tops and bottoms, no per-sample array unless asked for, no atomics, no second kernel.
+// Barriers: besides the ring's own (run_layer, passed by all waves in every pass) there are the vote's (raysum_saturated) and the two of rayaudit_end.  None sits in
+// divergent flow: `pass`, `group` and `ray` change by `passes` and `groups` (kernel arguments), A.ray_flags, gridDim and the vote's verdict alone, and the verdict is
+// formed by every wave from the same four LDS words behind the vote's barrier - so all four waves hold the same `pass`, `group` and `ray` at all times, enter the
+// `if`s of RAYAUDIT_PASS_END together and leave the loop together.  What differs between waves (`counts`, the sample index, lane 0's scoring) selects values and
+// plain loads / stores only.
+template <int W>
+__global__ __launch_bounds__(256, 1) void solar_audit_kernel(const SolarAuditArgs SA) {
+    const MlpArgs& A = SA.m;
+    constexpr int W2 = W / 2;
+    FIELD_PROLOGUE(A)
+    __attribute__((address_space(3))) float* vote = bias_lds + A.bias_floats;
+    __attribute__((address_space(3))) float* rows = vote + kVoteBytes / 4;
+
+    const int groups = (A.n_samples + 3) / 4;
+    const int passes = (A.n_samples + 31) / 32;
+    int pass = 0, group = 0;
+    RayAudit rs;
+    for (int64_t ray = blockIdx.x; ray < A.n;) {
+        const int s_wave = group * 4 + wave;
+        float x0, x1, x2;
+        rayaudit_point(rs, A, SA.sun, ray, s_wave < A.n_samples ? s_wave : A.n_samples - 1, pass, lane, x0, x1, x2);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KW = W / 16, KW2 = W2 / 16;
+        Frag hA[KW], hB[KW], x1f[KW2];
+        f32x16 raw;
+        FIELD_TRUNK(FIELD_LAYER, pe, hA, hB, x1f, raw);
+        const float rho_raw = raw[3];       // lane-half 0 holds the density row
+        RAYAUDIT_PASS_END(rs, A, SA, ray, group, groups, 4, pass, passes, s_wave, wave, 4, true, wave, lane, rho_raw, vote, rows, rows + wave * 8);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_solar_audit(int W, const SolarAuditArgs& a, int n_cu, hipStream_t st) {
+    if (W == 512) return launch_solar_audit_ks(W, a, n_cu, st);
+    if (W != 64 && W != 256) return hipErrorInvalidValue;
+    // launch_walk's launch with another tile rule: a tile is a primary ray; the rows of sums are its `lds_extra`, behind the vote words
+    return launch_fused(W == 64 ? solar_audit_kernel<64> : solar_audit_kernel<256>, a.m.n, 256, mlp_lds_bytes(a.m.bias_floats) + kAuditLdsFloats * 4, a, n_cu, st);
+}
+
 }  // namespace snerf

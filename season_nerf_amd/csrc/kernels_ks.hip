@@ -708,6 +708,46 @@ hipError_t launch_frame_walk_ks(int W, const FrameWalkArgs& a, int n_cu, hipStre
     return launch_fused(frame_walk_ks_kernel<512>, field_tiles(a.m.n, 3, KS_TILE_PTS, 2), 256, lds_bytes, a, n_cu, st);
 }
 
+// Solar audit at this width: the VARIANT 3 walk of mlp_ks_kernel (KS_TRUNK alone, the vote) along the secondary rays of the samples of a primary ray (kernels.hip
+// solar_audit_kernel, mlp_device.h RayAudit).  A group is two consecutive samples, one per wave pair; both waves of a pair hold the same optical depth and vote
+// alike, wave 0 of the pair scores.  The barriers are in workgroup-uniform flow for the reason given at solar_audit_kernel.
+template <int W>
+__global__ __launch_bounds__(256, 1) void solar_audit_ks_kernel(const SolarAuditArgs SA) {
+    const MlpArgs& A = SA.m;
+    constexpr int W2 = W / 2;
+    constexpr int PROG = PROG_FIELD;
+    KS_PROLOGUE(A)
+    __attribute__((address_space(3))) float* rows = vote_lds + kVoteBytes / 4;
+
+    const int groups = (A.n_samples + 1) / 2;
+    const int passes = (A.n_samples + 31) / 32;
+    int pass = 0, group = 0;
+    RayAudit rs;
+    for (int64_t ray = blockIdx.x; ray < A.n;) {
+        const int s_wave = group * 2 + pair;
+        float x0, x1, x2;
+        rayaudit_point(rs, A, SA.sun, ray, s_wave < A.n_samples ? s_wave : A.n_samples - 1, pass, lane, x0, x1, x2);
+        Frag pe[PEPOS_KS];
+        make_pe_pos(x0, x1, x2, h, pe);
+
+        constexpr int KH = W / 32, KH2 = W2 / 32;
+        constexpr int NBW = W / 64, NBW2 = W2 / 64;
+        Frag hA[KH], hB[KH], x1f[KH2];
+        f32x16 raw;
+        KS_TRUNK(pe, hA, hB, x1f, raw);
+        const float rho_raw = raw[3];
+        RAYAUDIT_PASS_END(rs, A, SA, ray, group, groups, 2, pass, passes, s_wave, wave, 4, par == 0, wave, lane, rho_raw, vote_lds, rows, rows + pair * 8);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
+}
+
+hipError_t launch_solar_audit_ks(int W, const SolarAuditArgs& a, int n_cu, hipStream_t st) {
+    if (W != 512) return hipErrorInvalidValue;
+    const int lds_bytes = ks_lds_bytes(a.m.bias_floats) + kAuditLdsFloats * 4;
+    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    return launch_fused(solar_audit_ks_kernel<512>, a.m.n, 256, lds_bytes, a, n_cu, st);      // a tile is a primary ray
+}
+
 #undef OWNB
 #undef LAYER
 #undef HEADL

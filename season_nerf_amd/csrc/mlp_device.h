@@ -454,6 +454,122 @@ __device__ __forceinline__ void rayshadow_end(const RayShadow& q, const MlpArgs&
         }                                                                                                                       \
     }
 
+// Solar audit (solar_audit_kernel, solar_audit_ks_kernel): the reference's comparison of the learned sun visibility with the one the density implies
+// (T_NeRF_Eval_Utils/mg_Advanced_Solar.py eval_solar_data on component_render_by_dir(include_exact_solar=True), mg_Img_Eval.py:57-70).  The walk is RaySum's -
+// density-only stream, passes from the point outwards, the depth-18 vote - but the rays walked are formed here: a workgroup owns a PRIMARY ray r and walks the
+// secondary rays of its samples s = 0 .. S-1, four (W = 512: two) at a time, one per wave (wave pair).  Per sample E = exp(-optical depth) is scored against the
+// inputs V = est_vis[r S + s] and PS = ps[r S + s]; the eight sums of a primary ray wait in LDS words behind the vote words, one row per wave, touched by lane 0 of
+// that wave alone until the ray ends.  One float per lane lives across the MFMA chain.
+struct RayAudit {
+    float sum;                      // running optical depth of this lane's samples of the secondary ray (RaySum::sum)
+};
+constexpr int kAuditLdsFloats = 4 * 8;      // behind the vote words: a row of eight sums per wave
+// The secondary ray of sample s of primary ray r (render.py _exact_solar_visibility with sun64, i.e. mg_Img_Eval.py:58-60): bot2 = p = top (1 - t_s) + bot t_s as
+// raysum_point forms it, K = (1 - p_z) / (float)sun_z in fp32, top2 = (float)((double)p + (double)K sun) with the product and the sum rounded separately.
+__device__ __forceinline__ void rayaudit_ends(const MlpArgs& A, const double* sun, int64_t r, int s, float& t0, float& t1, float& t2, float& b0, float& b1, float& b2) {
+    const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
+    b0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
+    b1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
+    b2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
+    const double K = (double)__fdiv_rn(__fsub_rn(1.f, b2), (float)sun[2]);
+    t0 = (float)__dadd_rn((double)b0, __dmul_rn(K, sun[0]));
+    t1 = (float)__dadd_rn((double)b1, __dmul_rn(K, sun[1]));
+    t2 = (float)__dadd_rn((double)b2, __dmul_rn(K, sun[2]));
+}
+// sample position of this lane in pass p of the secondary ray of sample `s` (clamped by the caller) of primary ray r: raysum_point on the ends above
+__device__ __forceinline__ void rayaudit_point(RayAudit& q, const MlpArgs& A, const double* sun, int64_t r, int s, int p, int lane, float& x0, float& x1, float& x2) {
+    float t0, t1, t2, b0, b1, b2;
+    rayaudit_ends(A, sun, r, s, t0, t1, t2, b0, b1, b2);
+    if (p == 0) q.sum = 0.f;
+    const int j = raysum_block(A, p) * 32 + (lane & 31);
+    const float t = A.tvals[j < A.n_samples ? j : A.n_samples - 1], omt = __fsub_rn(1.f, t);
+    x0 = __fadd_rn(__fmul_rn(t0, omt), __fmul_rn(b0, t));
+    x1 = __fadd_rn(__fmul_rn(t1, omt), __fmul_rn(b1, t));
+    x2 = __fadd_rn(__fmul_rn(t2, omt), __fmul_rn(b2, t));
+}
+// raysum_add on the ends above, operation for operation (a basic block of its own and everything re-formed behind the chain, for the reasons given there).
+// `counts`: false for a wave whose sample index is past the ray's last - it walked a clamped point and adds nothing.
+__device__ __forceinline__ void rayaudit_add(RayAudit& q, const MlpArgs& A, const double* sun, int64_t r, int s, bool counts, int p, int lane, float rho_raw) {
+    if (lane >= 32) return;
+    float t0, t1, t2, b0, b1, b2;
+    rayaudit_ends(A, sun, r, s, t0, t1, t2, b0, b1, b2);
+    const float dx = t0 - b0, dy = t1 - b1, dz = t2 - b2;
+    const float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    const int j = raysum_block(A, p) * 32 + (lane & 31);
+    const float t = A.tvals[j < A.n_samples ? j : A.n_samples - 1], omt = __fsub_rn(1.f, t);
+    const float x0 = __fadd_rn(__fmul_rn(t0, omt), __fmul_rn(b0, t));
+    const float x1 = __fadd_rn(__fmul_rn(t1, omt), __fmul_rn(b1, t));
+    const float x2 = __fadd_rn(__fmul_rn(t2, omt), __fmul_rn(b2, t));
+    const bool oob = x0 > 1.f || x0 < -1.f || x1 > 1.f || x1 < -1.f || x2 > 1.f || x2 < -1.f;
+    const bool on = counts && j < A.n_samples - 1 && !((A.ray_flags & 2) && oob);
+    q.sum += on ? __fmul_rn(softplus_f(rho_raw), delta) : 0.f;
+}
+// The end of a secondary ray: E = exp(-sum) by raysum_end's butterfly, stored to exact[i] if asked for, and scored into this wave's row of sums
+// {n(E > .5 and V > .5), n(E > .5), n(V > .5), sum E PS, sum V PS, sum PS, sum (E - V)^2, sum |E - V|} by lane 0.  `first`: the ray's first group clears the row.
+__device__ __forceinline__ void rayaudit_score(const RayAudit& q, bool counts, bool first, int64_t i, const float* est_vis, const float* ps, float* exact, int lane,
+                                               __attribute__((address_space(3))) float* row) {
+    float v = q.sum;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane != 0) return;
+    float a[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = first ? 0.f : row[k];
+    if (counts) {
+        const float E = expf(-v), V = est_vis[i], PS = ps[i];
+        if (exact) exact[i] = E;
+        const bool ex = E > .5f, es = V > .5f;
+        const float d = E - V;
+        a[0] += (ex && es) ? 1.f : 0.f;
+        a[1] += ex ? 1.f : 0.f;
+        a[2] += es ? 1.f : 0.f;
+        a[3] += E * PS;
+        a[4] += V * PS;
+        a[5] += PS;
+        a[6] += d * d;
+        a[7] += fabsf(d);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) row[k] = a[k];
+}
+// The end of a primary ray: the rows of the `n_rows` scoring waves added in the order of the waves, one 32-byte row stored by lane 0 of wave 0.  Both barriers are
+// passed by every wave of the workgroup (the caller's flow is workgroup-uniform, see solar_audit_kernel): the first orders the rows' last stores before the
+// loads, the second the loads before the next ray's first group clears the rows.
+__device__ __forceinline__ void rayaudit_end(float* out, int64_t r, int wave, int lane, int n_rows, __attribute__((address_space(3))) float* rows) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (wave == 0 && lane == 0) {
+        float a[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] = rows[k];
+        for (int w = 1; w < n_rows; ++w)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] += rows[w * 8 + k];
+        *reinterpret_cast<f32x4*>(out + r * 8) = f32x4{a[0], a[1], a[2], a[3]};
+        *reinterpret_cast<f32x4*>(out + r * 8 + 4) = f32x4{a[4], a[5], a[6], a[7]};
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+// The end of a pass, as RAYSUM_PASS_END (a macro for the same reason).  `s_wave`: the sample this wave walks (unclamped); `per_group`: secondary rays per group; `rows`: the
+// rows of sums, `row`: the one of this wave's secondary ray; `writer`: this wave scores for it.  Once the secondary rays of the group are done (last pass, or the workgroup voted itself
+// saturated) they are scored and the next group begins; behind the ray's last group the ray ends and the persistent loop advances.
+#define RAYAUDIT_PASS_END(q, A, SA, ray, group, groups, per_group, pass, passes, s_wave, slot, n_slots, writer, wave, lane, rho_raw, vote, rows, row)   \
+    {                                                                                                                           \
+        const bool counts = (s_wave) < A.n_samples;                                                                             \
+        const int s_c = counts ? (s_wave) : A.n_samples - 1;                                                                    \
+        rayaudit_add(q, A, SA.sun, ray, s_c, counts, pass, lane, rho_raw);                                                      \
+        RaySum depth;                                                                                                           \
+        depth.sum = q.sum;                                                                                                      \
+        if (++pass == (passes) || raysum_saturated(depth, A, counts ? ray : A.n, slot, n_slots, lane, vote)) {                  \
+            if (writer) rayaudit_score(q, counts, group == 0, ray * A.n_samples + s_c, SA.est_vis, SA.ps, SA.exact, lane, row); \
+            pass = 0;                                                                                                           \
+            if (++group == (groups)) {                                                                                          \
+                rayaudit_end(SA.out, ray, wave, lane, per_group, rows);                                                         \
+                group = 0;                                                                                                      \
+                ray += gridDim.x;                                                                                               \
+            }                                                                                                                   \
+        }                                                                                                                       \
+    }
+
 // Film frame (frame_walk_kernel, frame_walk_ks_kernel): the ray surface's walk through the whole layer list of VARIANT 0 - trunk, head, fc_solar_1..4,
 // the colour-adjust branch - with the shading and compositing of the reference's film frames in the pass end (T_NeRF_Eval_Utils/mg_movie_maker.py:108-187):
 //   Out_Img = sum_s PS_s (vis_s + (1 - vis_s) sky) col_s,    HM = sum_s PS_s linspace(0, 2, S)[s]

@@ -22,6 +22,7 @@
 //        -> [shaded[M,T,R,3], season[T,R,3], base[R,3], raw_shadow[M,R], shadow_adjust[M,R,3]]           the M x T grid of a view
 //   season_nerf::ray_surface(model, top[R,3], bot[R,3], tvals[S], flags) -> [R,4] {sum PS, sum PS t, sum PS s, optical depth}      height maps from a density-only ray pass
 //   season_nerf::shadow_walk(model, top[R,3], bot[R,3], sun[R,3], tvals[S], flags) -> [R,8]           the shadow test's per-ray sums (mg_Shadow_Eval.py:72-104,134-163)
+//   season_nerf::solar_audit(model, top[R,3], bot[R,3], tvals[S], sun (3 float64), est_vis[R,S], ps[R,S], flags, want_exact) -> ([R,8], [R,S] or [0,0])   the solar audit's per-ray sums, Exact_Solar (mg_Advanced_Solar.py)
 //   season_nerf::frame_walk(model, top[R,3], bot[R,3], tvals[S], delta, sun[3], sky[3], class_vecs[T,C], flags) -> [R,16]   a film frame's per-ray sums, T <= 4 seasons (mg_movie_maker.py:108-187)
 //   season_nerf::fused_adam_(param!, grad, m!, v!, lr, b1, b2, eps, step) -> ()                         mg_run_NeRF.py:312-320
 // Training engine (csrc/train.cpp; `trainer` = the snerf_trainer handle a season_nerf_amd.training.TrainEngine owns and has bound to its
@@ -320,6 +321,35 @@ Tensor shadow_walk(int64_t model, const Tensor& top, const Tensor& bot, const Te
     ck(snerf_field_shadow_walk((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(sun), fptr(tvals), (int)flags, mptr(out),
                                cur_stream(top)), "shadow_walk");
     return out;
+}
+
+// Solar audit (include/season_nerf_hip.h snerf_field_solar_audit): the eight sums per primary ray the reference's solar audit is formed from, and Exact_Solar
+// per sample if asked for ([0] otherwise).  The sun travels as three float64 values; the model as an integer, as in ray_surface.
+std::tuple<Tensor, Tensor> solar_audit(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, c10::ArrayRef<double> sun, const Tensor& est_vis,
+                                       const Tensor& ps, int64_t flags, bool want_exact) {
+    TORCH_CHECK(model != 0, "season_nerf::solar_audit: NULL model handle");
+    check_shape(top, "top", -1, 3);
+    const int64_t R = top.size(0);
+    check_shape(bot, "bot", R, 3);
+    check_dev_f32(tvals, "tvals");
+    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    const int64_t S = tvals.numel();
+    TORCH_CHECK(sun.size() == 3, "sun must hold 3 values, got ", sun.size());
+    TORCH_CHECK(std::isfinite(sun[0]) && std::isfinite(sun[1]) && std::isfinite(sun[2]) && sun[2] > 0.0 && (float)sun[2] > 0.f,
+                "sun must be finite with sun_z > 0, got (", sun[0], ", ", sun[1], ", ", sun[2], ")");
+    check_dev_f32(est_vis, "est_vis");
+    check_dev_f32(ps, "ps");
+    TORCH_CHECK(est_vis.numel() == R * S, "est_vis must hold R*S = ", R * S, " values, got ", est_vis.sizes());
+    TORCH_CHECK(ps.numel() == R * S, "ps must hold R*S = ", R * S, " values, got ", ps.sizes());
+    TORCH_CHECK(flags >= 0 && (flags & ~(int64_t)6) == 0, "flags must be a combination of 2 (zero delta outside the cube) and 4 (no early-out), got ", flags);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
+    Tensor out = at::empty({R, 8}, top.options());
+    Tensor exact = at::empty({want_exact ? R : 0, want_exact ? S : 0}, top.options());
+    if (R == 0) return {out, exact};
+    const double s3[3] = {sun[0], sun[1], sun[2]};
+    ck(snerf_field_solar_audit((const snerf_model*)model, R, (int)S, fptr(top), fptr(bot), fptr(tvals), s3, fptr(est_vis), fptr(ps), (int)flags, mptr(out),
+                               want_exact ? mptr(exact) : nullptr, cur_stream(top)), "solar_audit");
+    return {out, exact};
 }
 
 // Frame walk (include/season_nerf_hip.h snerf_field_frame_walk): sixteen sums per ray of a film frame, up to four seasons from one field pass.  The model
@@ -766,6 +796,7 @@ TORCH_LIBRARY(season_nerf, m) {
     m.def("sun_walk_fwd(int model, Tensor top, Tensor bot, Tensor tvals, Tensor suns, Tensor? classes) -> Tensor[]");
     m.def("ray_surface(int model, Tensor top, Tensor bot, Tensor tvals, int flags) -> Tensor");
     m.def("shadow_walk(int model, Tensor top, Tensor bot, Tensor sun, Tensor tvals, int flags) -> Tensor");
+    m.def("solar_audit(int model, Tensor top, Tensor bot, Tensor tvals, float[] sun, Tensor est_vis, Tensor ps, int flags, bool want_exact) -> (Tensor, Tensor)");
     m.def("frame_walk(int model, Tensor top, Tensor bot, Tensor tvals, float delta, Tensor sun, Tensor sky, Tensor class_vecs, int flags) -> Tensor");
     m.def("composite_sun_walk(Tensor top, Tensor bot, Tensor tvals, Tensor rho, Tensor col_raw, Tensor adjust, Tensor solar_vis, Tensor sky, Tensor class_vecs, "
           "int flags, Tensor? deltas=None) -> Tensor[]");
@@ -808,6 +839,7 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("composite_sun_walk", composite_sun_walk);
     m.impl("ray_surface", ray_surface);
     m.impl("shadow_walk", shadow_walk);
+    m.impl("solar_audit", solar_audit);
     m.impl("frame_walk", frame_walk);
     m.impl("trainer_adam_step_", trainer_adam_step_);
     m.impl("trainer_adam_step_dev_", trainer_adam_step_dev_);

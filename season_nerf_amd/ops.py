@@ -62,6 +62,11 @@ def _register_fakes():
     def _(model, top, bot, sun, tvals, flags):
         return top.new_empty(top.shape[0], 8)
 
+    @reg("season_nerf::solar_audit")
+    def _(model, top, bot, tvals, sun, est_vis, ps, flags, want_exact):
+        R, S = top.shape[0], tvals.numel()
+        return top.new_empty(R, 8), top.new_empty(R if want_exact else 0, S if want_exact else 0)
+
     @reg("season_nerf::frame_walk")
     def _(model, top, bot, tvals, delta, sun, sky, class_vecs, flags):
         return top.new_empty(top.shape[0], 16)
