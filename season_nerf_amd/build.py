@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(REPO, "build", "obj")
 LIB = os.path.join(HERE, "libseason_nerf_hip.so")
 SOURCES = ["kernels.hip", "kernels_i8.hip", "kernels_i8x2.hip", "kernels_i8_w512.hip", "kernels_ks.hip", "kernels_group.hip", "api.cpp", "pack.cpp", "gemm.hip", "gemm16.hip", "gemm_areg.hip", "train_kernels.hip", "train.cpp", "dsm.hip", "loader.hip"]
-HEADERS = ["gemm_common.h", "gemm_rows.h", "kernels.h", "linear_product.h", "loader_common.h", "mlp_device.h", "mlp_bf16_device.h", "mlp_i8_device.h", "pack.h", "program.h", "rows_debug.h", "train.h", os.path.join("..", "..", "include", "season_nerf_hip.h")]
+HEADERS = ["gemm_common.h", "gemm_rows.h", "kernels.h", "linear_product.h", "loader_common.h", "mlp_device.h", "mlp_bf16_device.h", "mlp_i8_device.h", "pack.h", "program.h", "ray_device.h", "rows_debug.h", "train.h", os.path.join("..", "..", "include", "season_nerf_hip.h")]
 FLAGS = ["-std=c++17", "-O3", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off",
          "-mllvm", "-amdgpu-mfma-vgpr-form=1",    # MFMA accumulators in VGPRs: no v_accvgpr_read per epilogue element
          "-Wno-unused-command-line-argument"]

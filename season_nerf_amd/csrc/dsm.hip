@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "ray_device.h"
 
 namespace snerf {
 
@@ -17,7 +18,7 @@ __global__ __launch_bounds__(256) void prior_density_kernel(int64_t n, const flo
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-    if (outside && (x > 1.f || x < -1.f || y > 1.f || y < -1.f || z > 1.f || z < -1.f)) {      // Eval_Tools_2.py:321-325
+    if (outside && outside_cube(x, y, z)) {      // Eval_Tools_2.py:321-325
         rho[i] = outside[i];
         return;
     }
@@ -37,14 +38,11 @@ __global__ __launch_bounds__(64) void surface_distance_kernel(int64_t n_rays, in
     if (r >= n_rays) return;
     const float tx = top[r * 3], ty = top[r * 3 + 1], tz = top[r * 3 + 2];
     const float bx = bot[r * 3], by = bot[r * 3 + 1], bz = bot[r * 3 + 2];
-    const float ex = tx - bx, ey = ty - by, ez = tz - bz;
-    const float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez))), (float)S);
+    const float delta = ray_delta(tx, ty, tz, bx, by, bz, S);
     double trans = 1.0, sum_p = 0.0, sum_pd = 0.0, run = 0.0;
     for (int s = 0; s < S; ++s) {
-        const float t = tvals[s], omt = __fsub_rn(1.f, t);
-        const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
-        const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
-        const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
+        float px, py, pz;
+        ray_point(tx, ty, tz, bx, by, bz, tvals[s], px, py, pz);
         int64_t ix = (int64_t)(__fmul_rn(__fdiv_rn(__fadd_rn(px, 1.f), 2.f), (float)(dx - 1)));
         int64_t iy = (int64_t)(__fmul_rn(__fdiv_rn(__fadd_rn(py, 1.f), 2.f), (float)(dy - 1)));
         int64_t iz = (int64_t)(__fmul_rn(__fdiv_rn(__fadd_rn(pz, 1.f), 2.f), (float)(S - 1)));
@@ -100,13 +98,13 @@ __global__ __launch_bounds__(256) void transmittance_kernel(int64_t n_rays, int 
         const int s = base + lane;
         const bool in = s < S;
         const float y = in ? rho[r * S + s] * delta[r * S + s] : 0.f;
-        float incl = y;
+        float incl = y;                                   // mirrors wave_incl_scan / wave_excl_of (ray_device.h): as calls, the kernel's schedule differs from the parent's
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const float up = __shfl_up(incl, o, 64);
             if (lane >= o) incl += up;
         }
-        const float below = __shfl_up(incl, 1, 64);       // exclusive prefix = the inclusive value of the lane below, never incl - y (kernels.hip, wave_excl_of)
+        const float below = __shfl_up(incl, 1, 64);       // exclusive prefix = the inclusive value of the lane below, never incl - y
         if (in) pv[r * S + s] = expf(-(carry + (lane == 0 ? 0.f : below)));
         carry += __shfl(incl, 63, 64);
     }

@@ -327,28 +327,7 @@ __global__ __launch_bounds__(256, 1) void sun_walk_kernel(const SunWalkArgs SA) 
 }
 
 // =====================================================================================================
-// compositing: one wavefront per ray (Eval_Tools_2.py:13-16,187-215; mg_run_NeRF.py:188-189)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_incl_scan(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-// The exclusive prefix of the same scan: the inclusive value of the lane below, 0 in lane 0.  NOT incl - v: that recovers the prefix from a
-// sum which an opaque sample's own v = rho * delta dominates, leaving it with half an ulp of v as its absolute error - and the sample's
-// transmittance exp(-prefix), which carries the ray, with that as its relative error ("Transmittance by a shifted scan").
-__device__ __forceinline__ float wave_excl_of(float incl, int lane) {
-    const float below = __shfl_up(incl, 1, 64);
-    return lane == 0 ? 0.f : below;
-}
-
+// compositing: one wavefront per ray (Eval_Tools_2.py:13-16,187-215; mg_run_NeRF.py:188-189); points, deltas, scan and PS: ray_device.h
 __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -356,9 +335,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
     const int S = A.n_samples;
     const float tx = A.top[r * 3], ty = A.top[r * 3 + 1], tz = A.top[r * 3 + 2];
     const float bx = A.bot[r * 3], by = A.bot[r * 3 + 1], bz = A.bot[r * 3 + 2];
-    const float dx = tx - bx, dy = ty - by, dz = tz - bz;
-    // deltas = sqrt(sum((top-bot)^2)) / S   (misc.py:243)
-    const float delta_ray = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)S);
+    const float delta_ray = ray_delta(tx, ty, tz, bx, by, bz, S);
     const bool classic = A.flags & 1, zero_oob = A.flags & 2;
     const float sky0 = A.sky[r * 3], sky1 = A.sky[r * 3 + 1], sky2 = A.sky[r * 3 + 2];
 
@@ -371,20 +348,15 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
         const int s = base + lane;
         const bool in = s < S;
         const int64_t idx = r * S + (in ? s : S - 1);
-        const float t = A.tvals[in ? s : S - 1], omt = __fsub_rn(1.f, t);
-        const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
-        const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
-        const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
+        float px, py, pz;
+        ray_point(tx, ty, tz, bx, by, bz, A.tvals[in ? s : S - 1], px, py, pz);
         float delta = delta_ray;
-        if (zero_oob && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+        if (zero_oob && outside_cube(px, py, pz)) delta = 0.f;
         const float rho = in ? A.rho[idx] : 0.f;
         const float y = in ? rho * delta : 0.f;
-        const float incl = wave_incl_scan(y, lane);
-        const float excl = carry + wave_excl_of(incl, lane);
-        carry += __shfl(incl, 63, 64);
-        const float pv = expf(-excl);
-        const float pe = 1.f - expf(-y);
-        const float ps = in ? pv * pe : 0.f;
+        const RayStep st = transmit_step(y, in, lane, carry);
+        carry = st.carry;
+        const float pv = st.pv, pe = st.pe, ps = st.ps;
         const float sv = in ? A.solar_vis[idx] : 0.f;
         const float k0 = in ? A.col[idx * 3] : 0.f, k1 = in ? A.col[idx * 3 + 1] : 0.f, k2 = in ? A.col[idx * 3 + 2] : 0.f;
         if (in) {
@@ -407,10 +379,9 @@ __global__ __launch_bounds__(256) void composite_kernel(const CompArgs A) {
             const float tr = A.trust_dev ? A.trust_dev[0] : A.trust;
             const float rm = in ? (rho * tr + A.rho_prior[idx] * (1.f - tr)) : 0.f;
             const float ym = rm * delta;
-            const float incl_m = wave_incl_scan(ym, lane);
-            const float excl_m = carry_m + wave_excl_of(incl_m, lane);
-            carry_m += __shfl(incl_m, 63, 64);
-            const float psm = in ? expf(-excl_m) * (1.f - expf(-ym)) : 0.f;
+            const RayStep stm = transmit_step(ym, in, lane, carry_m);
+            carry_m = stm.carry;
+            const float psm = stm.ps;
             if (classic) {
                 m0 += psm * k0 * (sv + (1.f - sv) * sky0);
                 m1 += psm * k1 * (sv + (1.f - sv) * sky1);
@@ -460,6 +431,8 @@ __device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn
 // no idle lanes at S = 96 (three 32-sample steps; one 64-lane step + a half-empty one before), half the accumulator registers per lane, the loads
 // of both halves coalesce (same addresses); the transmittance scan runs over 32 lanes, redundantly in both halves.  The next step's 17 values per
 // sample are requested before the current step is evaluated.
+// This kernel keeps its own copies of ray_delta, ray_point, outside_cube and transmit_step_half (ray_device.h): with any one of them
+// called instead, its register allocation and schedule differ from the parent's from the first instruction on.
 template <bool CLASSIC>
 __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs A) {
     constexpr int TH = T_CHUNK / 2;
@@ -545,7 +518,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const SweepArgs A) {
                 const float t = __shfl_up(incl, o, 32);
                 if (sl >= o) incl += t;
             }
-            const float below = __shfl_up(incl, 1, 32);   // exclusive prefix = the inclusive value of the lane below (see wave_excl_of)
+            const float below = __shfl_up(incl, 1, 32);   // exclusive prefix = the inclusive value of the lane below (see wave_excl_of, ray_device.h)
             const float excl = carry + (sl == 0 ? 0.f : below);
             carry += __shfl(incl, 31, 32);
             const float ps = in ? expf(-excl) * (1.f - expf(-y)) : 0.f;
@@ -620,8 +593,7 @@ __global__ __launch_bounds__(256) void sun_walk_composite_kernel(const SunWalkCo
     if (!explicit_delta) {
         tx = A.top[r * 3]; ty = A.top[r * 3 + 1]; tz = A.top[r * 3 + 2];
         bx = A.bot[r * 3]; by = A.bot[r * 3 + 1]; bz = A.bot[r * 3 + 2];
-        const float dx = tx - bx, dy = ty - by, dz = tz - bz;
-        delta_ray = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)S);
+        delta_ray = ray_delta(tx, ty, tz, bx, by, bz, S);
     }
     const bool zero_oob = (A.flags & 2) && !explicit_delta;
     // ---- PS of the ray
@@ -634,14 +606,12 @@ __global__ __launch_bounds__(256) void sun_walk_composite_kernel(const SunWalkCo
         if (explicit_delta) {
             delta = A.deltas[idx];
         } else if (zero_oob) {
-            const float t = A.tvals[in ? s : S - 1], omt = __fsub_rn(1.f, t);
-            const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
-            const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
-            const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
-            if (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f) delta = 0.f;
+            float px, py, pz;
+            ray_point(tx, ty, tz, bx, by, bz, A.tvals[in ? s : S - 1], px, py, pz);
+            if (outside_cube(px, py, pz)) delta = 0.f;
         }
         const float y = in ? A.rho[idx] * delta : 0.f;
-        const float incl = wave_incl_scan(y, lane);
+        const float incl = wave_incl_scan(y, lane);      // transmit_step's operations, PV and PE formed inside the branch (through the helper the two exps swap)
         const float excl = carry + wave_excl_of(incl, lane);
         carry += __shfl(incl, 63, 64);
         if (in) ps_l[s] = expf(-excl) * (1.f - expf(-y));
@@ -743,18 +713,9 @@ __global__ void rays_from_camera_kernel(const RayGenArgs A) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int pi = (int)(i / A.cols), pj = (int)(i - (int64_t)pi * A.cols);
         const double row = (double)pi * A.ds, col = (double)pj * A.ds;
-        const double* P = A.P;
-        const double a11 = P[0] - P[8] * row, a12 = P[1] - P[9] * row, a21 = P[4] - P[8] * col, a22 = P[5] - P[9] * col;
-        const double den = a11 * a22 - a12 * a21;
         double xy[2][2];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const double hgt = k == 0 ? 1.0 : -1.0;
-            const double c2 = P[6] * hgt + P[7] - P[10] * hgt * col - P[11] * col;     // P23 h + P24 - P33 h y - P34 y
-            const double c1 = P[2] * hgt + P[3] - P[10] * hgt * row - P[11] * row;     // P13 h + P14 - P33 h x - P34 x
-            xy[k][0] = (a12 * c2 - a22 * c1) / den;
-            xy[k][1] = (-a11 * c2 + a21 * c1) / den;
-        }
+        for (int k = 0; k < 2; ++k) invert_P(A.P, row, col, k == 0 ? 1.0 : -1.0, xy[k][0], xy[k][1]);
         const bool good = xy[0][0] <= 1.0 && xy[0][0] >= -1.0 && xy[0][1] <= 1.0 && xy[0][1] >= -1.0 &&
                           xy[1][0] <= 1.0 && xy[1][0] >= -1.0 && xy[1][1] <= 1.0 && xy[1][1] >= -1.0;
         if (A.valid) A.valid[i] = good ? 1 : 0;
@@ -796,6 +757,7 @@ __global__ void ray_grid_kernel(const RayGridArgs A) {
         if (A.mode == 2) {
             // mg_Img_Eval.py:77-84: source pixel = round(linspace(0, img - 1, out)) (half to even, as numpy.round), rays by invert_P at h = +1 / -1
             const double row = rint(linspace_at(0.0, (double)(A.img_rows - 1), A.rows, r)), col = rint(linspace_at(0.0, (double)(A.img_cols - 1), A.cols, c));
+            // mirrors invert_P (ray_device.h): through the helper this kernel's float64 divisions are scheduled differently from the parent's
             const double* P = A.P;
             const double a11 = P[0] - P[8] * row, a12 = P[1] - P[9] * row, a21 = P[4] - P[8] * col, a22 = P[5] - P[9] * col;
             const double den = a11 * a22 - a12 * a21;

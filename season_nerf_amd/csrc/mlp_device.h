@@ -7,6 +7,7 @@
 
 #include "program.h"
 #include "kernels.h"
+#include "ray_device.h"
 #if defined(SNERF_ABLATE) && !defined(ABL)
 #define ABL 0
 #endif
@@ -169,9 +170,6 @@ __device__ __forceinline__ void pe_sincos(const PeArg& a, double scale, float& c
     s = sin2pi(f);
 }
 
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // torch Softplus(beta 1, thr 20)
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-
 // ---- the field program's per-tile work around the layer walk (the same in every fused field kernel)
 // sample position of field point nc (VARIANTs 0-2): given, or sample nc % S of ray nc / S (misc.py:234-247 fused: top*(1-t) + bot*t,
 // two roundings + one add, no fma)
@@ -181,10 +179,10 @@ __device__ __forceinline__ void field_point(const MlpArgs& A, int64_t nc, float&
     } else {
         const int64_t r = nc / A.n_samples;
         const int s = (int)(nc - r * A.n_samples);
-        const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-        x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-        x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-        x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
+        const float t = A.tvals[s];
+        x0 = ray_coord(A.top[r * 3], A.bot[r * 3], t);
+        x1 = ray_coord(A.top[r * 3 + 1], A.bot[r * 3 + 1], t);
+        x2 = ray_coord(A.top[r * 3 + 2], A.bot[r * 3 + 2], t);
     }
 }
 // the per-tile inputs of group g: sun direction (VARIANT <= 1), class probabilities (VARIANT 0), zero where the variant has none.
@@ -214,17 +212,21 @@ struct RaySum {
 // early-out below does: matter that shadows a point of a real scene is the ground / the building the point sits in, i.e. next to the point, and a ray that
 // meets it in its first pass is finished after one evaluation of the network instead of three (ray_flags bit 3 = the old order, sun side first: A/B).
 __device__ __forceinline__ int raysum_block(const MlpArgs& A, int p) { return (A.ray_flags & 8) ? p : (A.n_samples + 31) / 32 - 1 - p; }
-// sample position of this lane in pass p (misc.py:234-247: top (1 - t) + bot t, two roundings + one add).  The ray's end points are re-read
-// every pass (cached loads before the MFMA chain) and once more after it for the segment length: nothing but `sum` lives across the chain.
-__device__ __forceinline__ void raysum_point(RaySum& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
+// sample position of this lane in pass p of a walk (ray_coord: top (1 - t) + bot t).  The ray's end points are re-read every pass (cached loads
+// before the MFMA chain) and once more after it for the segment length: nothing of them lives across the chain.
+__device__ __forceinline__ void walk_point(const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
     const int64_t ray = group * waves + wave;
     const int64_t r = ray < A.n ? ray : A.n - 1;
-    if (p == 0) q.sum = 0.f;
     const int s = raysum_block(A, p) * 32 + (lane & 31);
-    const float t = A.tvals[s < A.n_samples ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
-    x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-    x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-    x2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
+    const float t = A.tvals[s < A.n_samples ? s : A.n_samples - 1];
+    x0 = ray_coord(A.top[r * 3], A.bot[r * 3], t);
+    x1 = ray_coord(A.top[r * 3 + 1], A.bot[r * 3 + 1], t);
+    x2 = ray_coord(A.top[r * 3 + 2], A.bot[r * 3 + 2], t);
+}
+// the same for the visibility sum, whose first pass clears it
+__device__ __forceinline__ void raysum_point(RaySum& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
+    if (p == 0) q.sum = 0.f;
+    walk_point(A, group, waves, wave, p, lane, x0, x1, x2);
 }
 // lane-half 0 holds the density row; the last sample never counts (PV at the last sample is the EXCLUSIVE prefix, Eval_Tools_2.py:13-16);
 // delta = ||top - bot|| / S (misc.py:243) with the composite kernel's operations
@@ -234,10 +236,10 @@ __device__ __forceinline__ void raysum_add(RaySum& q, const MlpArgs& A, int64_t 
     if (lane >= 32) return;
     const int64_t ray = group * waves + wave;
     const int64_t r = ray < A.n ? ray : A.n - 1;
-    const float dx = A.top[r * 3] - A.bot[r * 3], dy = A.top[r * 3 + 1] - A.bot[r * 3 + 1], dz = A.top[r * 3 + 2] - A.bot[r * 3 + 2];
-    const float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    const float delta = ray_delta(A.top[r * 3], A.top[r * 3 + 1], A.top[r * 3 + 2], A.bot[r * 3], A.bot[r * 3 + 1], A.bot[r * 3 + 2], A.n_samples);
     const int s = raysum_block(A, p) * 32 + (lane & 31);
-    {   // the sample position again (the registers that held it during the chain are long gone: fewer values live across it)
+    {   // the sample position again (the registers that held it during the chain are long gone: fewer values live across it).  It and the cube rule mirror
+        // ray_coord / outside_cube (ray_device.h): through either helper the three coordinates' products are scheduled in another order than the parent's
         const float t = A.tvals[s < A.n_samples ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
         x0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
         x1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
@@ -257,9 +259,7 @@ constexpr float kSaturatedDepth = 18.f;
 __device__ __forceinline__ bool raysum_saturated(const RaySum& q, const MlpArgs& A, int64_t ray, int slot, int n_slots, int lane,
                                                  __attribute__((address_space(3))) float* vote) {
     if (A.ray_flags & 4) return false;                        // A/B switch (SNERF_RAYVIS_NO_EARLY_OUT=1): every pass of every ray
-    float v = q.sum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    float v = wave_sum(q.sum);
     if (ray >= A.n) v = 1e30f;                                // a ray past the end never holds the group back
     if (lane == 0) vote[slot] = v;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -268,9 +268,7 @@ __device__ __forceinline__ bool raysum_saturated(const RaySum& q, const MlpArgs&
     return all;
 }
 __device__ __forceinline__ void raysum_end(RaySum& q, const MlpArgs& A, int64_t group, int waves, int wave, int lane) {
-    float v = q.sum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    float v = wave_sum(q.sum);
     const int64_t ray = group * waves + wave;
     if (lane == 0 && ray < A.n) A.out.vis[ray] = expf(-v);
 }
@@ -296,7 +294,8 @@ struct RaySurf {
     float carry;                    // optical depth of the samples of the passes walked so far (the same in lanes 0..31, 0 in the others)
     float acc, mt, mi;              // this lane's partial sums of PS, PS t_s and PS s
 };
-// sample position of this lane in pass p: raysum_point's; the first pass of a ray clears its sums
+// sample position of this lane in pass p: walk_point's, reached through raysum_point on a dummy sum (calling walk_point directly drops two scalar
+// instructions from both ray_surface kernels and renumbers their registers); the first pass of a ray clears its sums
 __device__ __forceinline__ void raysurf_point(RaySurf& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
     RaySum unused;
     raysum_point(unused, A, group, waves, wave, p, lane, x0, x1, x2);
@@ -311,35 +310,24 @@ __device__ __forceinline__ void raysurf_add(RaySurf& q, const MlpArgs& A, int64_
     const int64_t r = ray < A.n ? ray : A.n - 1;
     const float tx = A.top[r * 3], ty = A.top[r * 3 + 1], tz = A.top[r * 3 + 2];
     const float bx = A.bot[r * 3], by = A.bot[r * 3 + 1], bz = A.bot[r * 3 + 2];
-    const float dx = tx - bx, dy = ty - by, dz = tz - bz;
-    float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    float delta = ray_delta(tx, ty, tz, bx, by, bz, A.n_samples);
     const int s = raysum_block(A, p) * 32 + lane;
     const bool in = s < A.n_samples;
-    const float t = A.tvals[in ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
-    const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
-    const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
-    const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
-    if ((A.ray_flags & 2) && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+    const float t = A.tvals[in ? s : A.n_samples - 1];
+    float px, py, pz;
+    ray_point(tx, ty, tz, bx, by, bz, t, px, py, pz);
+    if ((A.ray_flags & 2) && outside_cube(px, py, pz)) delta = 0.f;
     const float y = in ? softplus_f(rho_raw) * delta : 0.f;
-    float incl = y;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        const float u = __shfl_up(incl, o, 32);
-        if (lane >= o) incl += u;
-    }
-    const float below = __shfl_up(incl, 1, 32);
-    const float excl = q.carry + (lane == 0 ? 0.f : below);
-    q.carry += __shfl(incl, 31, 32);
-    const float pv = expf(-excl);
-    const float pe = 1.f - expf(-y);
-    const float ps = in ? pv * pe : 0.f;
+    const RayStep st = transmit_step_half(y, in, lane, q.carry);
+    q.carry = st.carry;
+    const float ps = st.ps;
     q.acc += ps;
     q.mt += ps * t;
     q.mi += ps * (float)s;
 }
 // the ray's four numbers {sum PS, sum PS t, sum PS s, optical depth walked}: one 16-byte store by lane 0
 __device__ __forceinline__ void raysurf_end(const RaySurf& q, const MlpArgs& A, float* out, int64_t ray, int lane) {
-    float acc = q.acc, mt = q.mt, mi = q.mi;
+    float acc = q.acc, mt = q.mt, mi = q.mi;     // three wave_sums (ray_device.h) interleaved: as three calls the shuffles are scheduled differently
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         acc += __shfl_xor(acc, o, 64);
@@ -372,12 +360,11 @@ struct RayShadow {
     float se, ae;                   // sum (PV - vis)^2, sum |PV - vis|
     float psv, acc;                 // sum PS vis, sum PS
 };
-// sample position of this lane in pass p (raysum_point's) and the ray's sun direction; the first pass of a ray clears its sums.  The sun direction is a
+// sample position of this lane in pass p (walk_point's) and the ray's sun direction; the first pass of a ray clears its sums.  The sun direction is a
 // per-tile input: loaded here, before the MFMA chain (field_tile_inputs).
 __device__ __forceinline__ void rayshadow_point(RayShadow& q, const MlpArgs& A, const float* sun, int64_t group, int waves, int wave, int p, int lane,
                                                 float& x0, float& x1, float& x2, float& s0, float& s1, float& s2) {
-    RaySum unused;
-    raysum_point(unused, A, group, waves, wave, p, lane, x0, x1, x2);
+    walk_point(A, group, waves, wave, p, lane, x0, x1, x2);
     const int64_t ray = group * waves + wave;
     const int64_t r = ray < A.n ? ray : A.n - 1;
     s0 = sun[r * 3]; s1 = sun[r * 3 + 1]; s2 = sun[r * 3 + 2];
@@ -391,28 +378,17 @@ __device__ __forceinline__ void rayshadow_add(RayShadow& q, const MlpArgs& A, in
     const int64_t r = ray < A.n ? ray : A.n - 1;
     const float tx = A.top[r * 3], ty = A.top[r * 3 + 1], tz = A.top[r * 3 + 2];
     const float bx = A.bot[r * 3], by = A.bot[r * 3 + 1], bz = A.bot[r * 3 + 2];
-    const float dx = tx - bx, dy = ty - by, dz = tz - bz;
-    float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    float delta = ray_delta(tx, ty, tz, bx, by, bz, A.n_samples);
     const int s = raysum_block(A, p) * 32 + lane;
     const bool in = s < A.n_samples;
-    const float t = A.tvals[in ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
-    const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
-    const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
-    const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
-    if ((A.ray_flags & 2) && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+    const float t = A.tvals[in ? s : A.n_samples - 1];
+    float px, py, pz;
+    ray_point(tx, ty, tz, bx, by, bz, t, px, py, pz);
+    if ((A.ray_flags & 2) && outside_cube(px, py, pz)) delta = 0.f;
     const float y = in ? softplus_f(rho_raw) * delta : 0.f;
-    float incl = y;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        const float u = __shfl_up(incl, o, 32);
-        if (lane >= o) incl += u;
-    }
-    const float below = __shfl_up(incl, 1, 32);
-    const float excl = q.carry + (lane == 0 ? 0.f : below);
-    q.carry += __shfl(incl, 31, 32);
-    const float pv = expf(-excl);
-    const float pe = 1.f - expf(-y);
-    const float ps = in ? pv * pe : 0.f;
+    const RayStep st = transmit_step_half(y, in, lane, q.carry);
+    q.carry = st.carry;
+    const float pv = st.pv, ps = st.ps;
     const float vis = sigmoid_f(sv_raw);
     const bool ex = in && pv > .5f, es = in && vis > .5f;
     const float d = in ? pv - vis : 0.f;
@@ -427,7 +403,7 @@ __device__ __forceinline__ void rayshadow_add(RayShadow& q, const MlpArgs& A, in
 // the ray's eight numbers {n(PV > .5 and vis > .5), n(PV > .5), n(vis > .5), sum (PV - vis)^2, sum |PV - vis|, sum PS vis, sum PS, optical depth walked}:
 // one 32-byte row, two 16-byte stores by lane 0
 __device__ __forceinline__ void rayshadow_end(const RayShadow& q, const MlpArgs& A, float* out, int64_t ray, int lane) {
-    float tp = q.tp, ne = q.ne, nv = q.nv, se = q.se, ae = q.ae, psv = q.psv, acc = q.acc;
+    float tp = q.tp, ne = q.ne, nv = q.nv, se = q.se, ae = q.ae, psv = q.psv, acc = q.acc;      // seven wave_sums interleaved, as raysurf_end's three
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         tp += __shfl_xor(tp, o, 64);
@@ -467,10 +443,10 @@ constexpr int kAuditLdsFloats = 4 * 8;      // behind the vote words: a row of e
 // The secondary ray of sample s of primary ray r (render.py _exact_solar_visibility with sun64, i.e. mg_Img_Eval.py:58-60): bot2 = p = top (1 - t_s) + bot t_s as
 // raysum_point forms it, K = (1 - p_z) / (float)sun_z in fp32, top2 = (float)((double)p + (double)K sun) with the product and the sum rounded separately.
 __device__ __forceinline__ void rayaudit_ends(const MlpArgs& A, const double* sun, int64_t r, int s, float& t0, float& t1, float& t2, float& b0, float& b1, float& b2) {
-    const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-    b0 = __fadd_rn(__fmul_rn(A.top[r * 3], omt), __fmul_rn(A.bot[r * 3], t));
-    b1 = __fadd_rn(__fmul_rn(A.top[r * 3 + 1], omt), __fmul_rn(A.bot[r * 3 + 1], t));
-    b2 = __fadd_rn(__fmul_rn(A.top[r * 3 + 2], omt), __fmul_rn(A.bot[r * 3 + 2], t));
+    const float t = A.tvals[s];
+    b0 = ray_coord(A.top[r * 3], A.bot[r * 3], t);
+    b1 = ray_coord(A.top[r * 3 + 1], A.bot[r * 3 + 1], t);
+    b2 = ray_coord(A.top[r * 3 + 2], A.bot[r * 3 + 2], t);
     const double K = (double)__fdiv_rn(__fsub_rn(1.f, b2), (float)sun[2]);
     t0 = (float)__dadd_rn((double)b0, __dmul_rn(K, sun[0]));
     t1 = (float)__dadd_rn((double)b1, __dmul_rn(K, sun[1]));
@@ -482,10 +458,7 @@ __device__ __forceinline__ void rayaudit_point(RayAudit& q, const MlpArgs& A, co
     rayaudit_ends(A, sun, r, s, t0, t1, t2, b0, b1, b2);
     if (p == 0) q.sum = 0.f;
     const int j = raysum_block(A, p) * 32 + (lane & 31);
-    const float t = A.tvals[j < A.n_samples ? j : A.n_samples - 1], omt = __fsub_rn(1.f, t);
-    x0 = __fadd_rn(__fmul_rn(t0, omt), __fmul_rn(b0, t));
-    x1 = __fadd_rn(__fmul_rn(t1, omt), __fmul_rn(b1, t));
-    x2 = __fadd_rn(__fmul_rn(t2, omt), __fmul_rn(b2, t));
+    ray_point(t0, t1, t2, b0, b1, b2, A.tvals[j < A.n_samples ? j : A.n_samples - 1], x0, x1, x2);
 }
 // raysum_add on the ends above, operation for operation (a basic block of its own and everything re-formed behind the chain, for the reasons given there).
 // `counts`: false for a wave whose sample index is past the ray's last - it walked a clamped point and adds nothing.
@@ -493,9 +466,9 @@ __device__ __forceinline__ void rayaudit_add(RayAudit& q, const MlpArgs& A, cons
     if (lane >= 32) return;
     float t0, t1, t2, b0, b1, b2;
     rayaudit_ends(A, sun, r, s, t0, t1, t2, b0, b1, b2);
-    const float dx = t0 - b0, dy = t1 - b1, dz = t2 - b2;
-    const float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)A.n_samples);
+    const float delta = ray_delta(t0, t1, t2, b0, b1, b2, A.n_samples);
     const int j = raysum_block(A, p) * 32 + (lane & 31);
+    // the point and the cube rule mirror ray_coord / outside_cube (ray_device.h), for the reason given in raysum_add
     const float t = A.tvals[j < A.n_samples ? j : A.n_samples - 1], omt = __fsub_rn(1.f, t);
     const float x0 = __fadd_rn(__fmul_rn(t0, omt), __fmul_rn(b0, t));
     const float x1 = __fadd_rn(__fmul_rn(t1, omt), __fmul_rn(b1, t));
@@ -508,9 +481,7 @@ __device__ __forceinline__ void rayaudit_add(RayAudit& q, const MlpArgs& A, cons
 // {n(E > .5 and V > .5), n(E > .5), n(V > .5), sum E PS, sum V PS, sum PS, sum (E - V)^2, sum |E - V|} by lane 0.  `first`: the ray's first group clears the row.
 __device__ __forceinline__ void rayaudit_score(const RayAudit& q, bool counts, bool first, int64_t i, const float* est_vis, const float* ps, float* exact, int lane,
                                                __attribute__((address_space(3))) float* row) {
-    float v = q.sum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    float v = wave_sum(q.sum);
     if (lane != 0) return;
     float a[8];
 #pragma unroll
@@ -597,7 +568,8 @@ __device__ __forceinline__ void frame_stage_inputs(const FrameWalkArgs& FA, __at
         fin[i] = v;
     }
 }
-// sample position of this lane in pass p: raysum_point's; the first pass of a ray clears its sums
+// sample position of this lane in pass p: walk_point's, through raysum_point on a dummy sum as in raysurf_point and for its reason; the first pass of a
+// ray clears its sums
 __device__ __forceinline__ void rayframe_point(RayFrame& q, const MlpArgs& A, int64_t group, int waves, int wave, int p, int lane, float& x0, float& x1, float& x2) {
     RaySum unused;
     raysum_point(unused, A, group, waves, wave, p, lane, x0, x1, x2);
@@ -621,24 +593,14 @@ __device__ __forceinline__ void rayframe_add(RayFrame& q, const MlpArgs& A, floa
     float delta = frame_delta;
     const int s = raysum_block(A, p) * 32 + lane;
     const bool in = s < A.n_samples;
-    const float t = A.tvals[in ? s : A.n_samples - 1], omt = __fsub_rn(1.f, t);
-    const float px = __fadd_rn(__fmul_rn(tx, omt), __fmul_rn(bx, t));
-    const float py = __fadd_rn(__fmul_rn(ty, omt), __fmul_rn(by, t));
-    const float pz = __fadd_rn(__fmul_rn(tz, omt), __fmul_rn(bz, t));
-    if ((A.ray_flags & 2) && (px > 1.f || px < -1.f || py > 1.f || py < -1.f || pz > 1.f || pz < -1.f)) delta = 0.f;
+    const float t = A.tvals[in ? s : A.n_samples - 1];
+    float px, py, pz;
+    ray_point(tx, ty, tz, bx, by, bz, t, px, py, pz);
+    if ((A.ray_flags & 2) && outside_cube(px, py, pz)) delta = 0.f;
     const float y = in ? softplus_f(rho_raw) * delta : 0.f;
-    float incl = y;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        const float u = __shfl_up(incl, o, 32);
-        if (lane >= o) incl += u;
-    }
-    const float below = __shfl_up(incl, 1, 32);
-    const float excl = q.carry + (lane == 0 ? 0.f : below);
-    q.carry += __shfl(incl, 31, 32);
-    const float pv = expf(-excl);
-    const float pe = 1.f - expf(-y);
-    const float ps = in ? pv * pe : 0.f;
+    const RayStep st = transmit_step_half(y, in, lane, q.carry);
+    q.carry = st.carry;
+    const float ps = st.ps;
     const float vis = sigmoid_f(sv_raw);
     const float sh0 = ps * (vis + (1.f - vis) * fin[3]), sh1 = ps * (vis + (1.f - vis) * fin[4]), sh2 = ps * (vis + (1.f - vis) * fin[5]);
     q.acc += ps;
@@ -664,7 +626,7 @@ __device__ __forceinline__ void rayframe_add(RayFrame& q, const MlpArgs& A, floa
 // the ray's sixteen numbers {rgb of season 0, 1, 2, 3 (0 past n_times), sum PS, sum PS s, optical depth walked, sum PS vis}: one 64-byte row, four
 // 16-byte stores by lane 0
 __device__ __forceinline__ void rayframe_end(const RayFrame& q, const MlpArgs& A, int n_times, float* out, int64_t ray, int lane) {
-    float acc = q.acc, mi = q.mi, psv = q.psv, rgb[3 * kMaxFrameTimes];
+    float acc = q.acc, mi = q.mi, psv = q.psv, rgb[3 * kMaxFrameTimes];      // fifteen wave_sums interleaved, as raysurf_end's three
 #pragma unroll
     for (int i = 0; i < 3 * kMaxFrameTimes; ++i) rgb[i] = q.rgb[i];
 #pragma unroll

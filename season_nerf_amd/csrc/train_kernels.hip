@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "train.h"
+#include "ray_device.h"
 
 namespace snerf {
 
@@ -19,9 +20,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
             hipLaunchKernelGGL(kernel, dim3((unsigned)_b), dim3(256), 0, st, __VA_ARGS__); \
         }                                                                                \
     } while (0)
-
-__device__ __forceinline__ float sigmoid_t(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float softplus_t(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
 // sin/cos of 2^j * fl32(fl32(pi/2)*x), reduced in fp64 (same construction as the inference kernel, misc.py:109-131)
 __device__ __forceinline__ void pe_sc(float x, int j, float& c, float& s) {
@@ -49,8 +47,8 @@ __global__ void pe_points_kernel(const PeArgs A) {
         } else {
             const int64_t r = i / A.n_samples;
             const int s = (int)(i - r * A.n_samples);
-            const float t = A.tvals[s], omt = __fsub_rn(1.f, t);
-            x = __fadd_rn(__fmul_rn(A.top[r * 3 + d], omt), __fmul_rn(A.bot[r * 3 + d], t));
+            const float t = A.tvals[s];
+            x = ray_coord(A.top[r * 3 + d], A.bot[r * 3 + d], t);
         }
         float v;
         if (f < 3) {
@@ -811,8 +809,8 @@ hipError_t launch_bn_bwd2(const float* Z, float* D, int64_t M, int C, int64_t ld
 __global__ void point_out_fwd_kernel(const PointOutArgs A) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t g = i / A.n_samples;
-        if (A.rho) A.rho[i] = softplus_t(A.head[i * 4 + 3]);
-        if (A.sv && A.sv_raw) A.sv[i] = sigmoid_t(A.sv_raw[i]);
+        if (A.rho) A.rho[i] = softplus_f(A.head[i * 4 + 3]);
+        if (A.sv && A.sv_raw) A.sv[i] = sigmoid_f(A.sv_raw[i]);
         if (A.col) {
             float ac[3] = {0.f, 0.f, 0.f};
             for (int c = 0; c < A.C; ++c) {
@@ -821,7 +819,7 @@ __global__ void point_out_fwd_kernel(const PointOutArgs A) {
                 for (int k = 0; k < 3; ++k) ac[k] = __fadd_rn(ac[k], __fmul_rn(A.adj[i * 3 * A.C + 3 * c + k], p));
             }
 #pragma unroll
-            for (int k = 0; k < 3; ++k) A.col[i * 3 + k] = sigmoid_t(A.head[i * 4 + k] + ac[k]);
+            for (int k = 0; k < 3; ++k) A.col[i * 3 + k] = sigmoid_f(A.head[i * 4 + k] + ac[k]);
             if (A.adjust_col) { A.adjust_col[i * 3] = ac[0]; A.adjust_col[i * 3 + 1] = ac[1]; A.adjust_col[i * 3 + 2] = ac[2]; }
         }
     }
@@ -846,7 +844,7 @@ __global__ __launch_bounds__(256) void point_out_bwd_kernel(const PointOutArgs A
         const int64_t g = i / A.n_samples;
         if (A.d_head) {
             const float raw = A.head[i * 4 + 3];
-            A.d_head[i * 4 + 3] = A.d_rho ? A.d_rho[i] * (raw > 20.f ? 1.f : sigmoid_t(raw)) : 0.f;
+            A.d_head[i * 4 + 3] = A.d_rho ? A.d_rho[i] * (raw > 20.f ? 1.f : sigmoid_f(raw)) : 0.f;
             float dpre[3] = {0.f, 0.f, 0.f};
             if (A.d_col) {
 #pragma unroll
@@ -885,24 +883,7 @@ hipError_t launch_point_out(const PointOutArgs& a, bool backward, hipStream_t st
 // compositing backward, one wavefront per ray (forward: Eval_Tools_2.py:187-215, default solar model):
 //   y = rho*delta, PV_s = exp(-sum_{j<s} y_j), PE_s = 1 - exp(-y_s), PS = PV*PE
 //   Albedo = sum PS*col ; u = sum PS*sv (sv detached) ; SV3 = sigmoid(30(u-.2)) ; F = SV3 + (1-SV3)*sky ; RGB = Albedo*F
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wscan_incl(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-// exclusive prefix of wscan_incl: the inclusive value of the lane below, 0 in lane 0 - never incl - v (csrc/kernels.hip, wave_excl_of)
-__device__ __forceinline__ float wscan_excl_of(float incl, int lane) {
-    const float below = __shfl_up(incl, 1, 64);
-    return lane == 0 ? 0.f : below;
-}
+// (wave sum, prefix scan and the forward's transmittance step: ray_device.h)
 // inclusive SUFFIX scan v_lane + .. + v_63, and from it what lies strictly behind a lane (0 in lane 63).  The backward needs sum_{k>s} dPV_k PV_k, which
 // behind an opaque sample is tiny against the chunk's total: tot - inclusive_prefix would leave it with half an ulp of the TOTAL as its absolute error.
 __device__ __forceinline__ float wscan_incl_suffix(float v, int lane) {
@@ -922,8 +903,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= A.n_rays) return;
     const int S = A.n_samples;
-    const float dx = A.top[r * 3] - A.bot[r * 3], dy = A.top[r * 3 + 1] - A.bot[r * 3 + 1], dz = A.top[r * 3 + 2] - A.bot[r * 3 + 2];
-    const float delta = __fdiv_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), (float)S);
+    const float delta = ray_delta(A.top[r * 3], A.top[r * 3 + 1], A.top[r * 3 + 2], A.bot[r * 3], A.bot[r * 3 + 1], A.bot[r * 3 + 2], S);
     const float sky[3] = {A.sky[r * 3], A.sky[r * 3 + 1], A.sky[r * 3 + 2]};
     const bool prior = A.rho_prior != nullptr;
     const float tr = A.trust_dev ? A.trust_dev[0] : A.trust;
@@ -935,28 +915,26 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         const int64_t idx = r * S + (in ? s : S - 1);
         const float rho = A.rho[idx];
         const float y = in ? rho * delta : 0.f;
-        const float incl = wscan_incl(y, lane);
-        const float pv = expf(-(carry + wscan_excl_of(incl, lane)));
-        carry += __shfl(incl, 63, 64);
-        const float ps = in ? pv * (1.f - expf(-y)) : 0.f;
+        const RayStep st = transmit_step(y, in, lane, carry);
+        carry = st.carry;
+        const float ps = st.ps;
 #pragma unroll
         for (int k = 0; k < 3; ++k) alb[k] += ps * A.col[idx * 3 + k];
         u += ps * A.sv[idx];
         if (prior) {
             const float ym = in ? (rho * tr + A.rho_prior[idx] * (1.f - tr)) * delta : 0.f;
-            const float inclm = wscan_incl(ym, lane);
-            const float pvm = expf(-(carry_m + wscan_excl_of(inclm, lane)));
-            carry_m += __shfl(inclm, 63, 64);
-            const float psm = in ? pvm * (1.f - expf(-ym)) : 0.f;
+            const RayStep stm = transmit_step(ym, in, lane, carry_m);
+            carry_m = stm.carry;
+            const float psm = stm.ps;
 #pragma unroll
             for (int k = 0; k < 3; ++k) albm[k] += psm * A.col[idx * 3 + k];
         }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { alb[k] = wsum(alb[k]); albm[k] = wsum(albm[k]); }
-    u = wsum(u);
+    for (int k = 0; k < 3; ++k) { alb[k] = wave_sum(alb[k]); albm[k] = wave_sum(albm[k]); }
+    u = wave_sum(u);
     const bool classic = A.classic != 0;
-    const float sv3 = sigmoid_t((u - 0.2f) * 30.f);
+    const float sv3 = sigmoid_f((u - 0.2f) * 30.f);
     float dalb[3], dalbm[3], dsky[3], dsv3 = 0.f, grgb[3], grgbm[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -986,15 +964,15 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
                 if (prior) pre_m += (rr * tr + A.rho_prior[r * S + s2] * (1.f - tr)) * delta;
             }
         }
-        pre = wsum(pre);
-        pre_m = wsum(pre_m);
+        pre = wave_sum(pre);
+        pre_m = wave_sum(pre_m);
         const int s = ch * 64 + lane;
         const bool in = s < S;
         const int64_t idx = r * S + (in ? s : S - 1);
         const float rho = A.rho[idx];
         const float y = in ? rho * delta : 0.f;
-        const float incl = wscan_incl(y, lane);
-        const float pv = expf(-(pre + wscan_excl_of(incl, lane)));
+        const float incl = wave_incl_scan(y, lane);
+        const float pv = expf(-(pre + wave_excl_of(incl, lane)));
         const float ey = expf(-y);
         const float pe = 1.f - ey;
         float dps = 0.f;
@@ -1031,8 +1009,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
         suffix += tot;
         if (prior) {
             const float ym = in ? (rho * tr + A.rho_prior[idx] * (1.f - tr)) * delta : 0.f;
-            const float inclm = wscan_incl(ym, lane);
-            const float pvm = expf(-(pre_m + wscan_excl_of(inclm, lane)));
+            const float inclm = wave_incl_scan(ym, lane);
+            const float pvm = expf(-(pre_m + wave_excl_of(inclm, lane)));
             const float eym = expf(-ym);
             const float pem = 1.f - eym;
             float dpsm = 0.f;
@@ -1066,7 +1044,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompBwdArgs A)
     }
     if (classic) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) dsky[k] = wsum(dsky[k]);
+        for (int k = 0; k < 3; ++k) dsky[k] = wave_sum(dsky[k]);
         if (lane == 0) { A.d_sky[r * 3] = dsky[0]; A.d_sky[r * 3 + 1] = dsky[1]; A.d_sky[r * 3 + 2] = dsky[2]; }
     }
 }
@@ -1094,7 +1072,7 @@ __global__ void softmax_bwd_kernel(const float* p, const float* dp, float* dx, i
     }
 }
 __global__ void sigmoid_kernel(const float* x, float* y, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = sigmoid_t(x[i]);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = sigmoid_f(x[i]);
 }
 __global__ void sigmoid_bwd_kernel(const float* y, const float* dy, float* dx, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dx[i] = dy[i] * y[i] * (1.f - y[i]);
@@ -1118,7 +1096,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* X, int64_t M, 
     __shared__ float red[4][16];               // same-address atomics serialise: one per column and workgroup
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
-        const float v = c < C ? wsum(s[c]) : 0.f;
+        const float v = c < C ? wave_sum(s[c]) : 0.f;
         if (lane == 0) red[threadIdx.x >> 6][c] = v;
     }
     __syncthreads();

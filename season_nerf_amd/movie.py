@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from .evaluator import sample_parameters_on
-from .render import _f32, _walks, encode_time
+from .render import _f32, _ray_samples, _walks, encode_time
 
 MAX_FRAME_TIMES = 4      # seasons per launch (include/season_nerf_hip.h SNERF_MAX_FRAME_TIMES)
 _CUBE = np.array([[-1, 1.], [-1, 1], [-1, 1]])
@@ -122,8 +122,7 @@ def _frame_layerwise(net, top, bot, tv, S, delta, sun, tim, class_vecs, valid_ra
     """The rows of `frame_walk` for a chunk of rays from `forward_seperate` on the sample points and float64 sums: networks the frame-walk kernels do
     not serve, and a valid range other than the cube.  -> list of [n,16] float64, one per MAX_FRAME_TIMES seasons."""
     n = top.shape[0]
-    t = tv.reshape(1, S, 1)
-    p = top.unsqueeze(1) * (1.0 - t) + bot.unsqueeze(1) * t
+    p, _ = _ray_samples(top, bot, tv, S, False)          # the points only: a frame's delta is the caller's `delta`, not the ray's length / S
     rho, col_raw, vis, sky, _, adj = net.forward_seperate(p.reshape(-1, 3), sun.reshape(1, 3).expand(n * S, 3), tim.reshape(1, 4).expand(n * S, 4))
     d = torch.full((n, S), float(delta), dtype=torch.float64, device=top.device)
     d = torch.where(_outside(p, valid_range), torch.zeros_like(d), d)

@@ -90,14 +90,22 @@ def _exact_solar_visibility(net: T_NeRF, pts, sun_vec, S, zero_oob, chunk_rays=1
     return vis
 
 
-def _visibility_layerwise(net, tops, bots, tv, S, zero_oob):
-    """exp(-sum_{j<S-1} rho_j delta_j) of a chunk of rays from the layer-wise density (networks without a fused kernel)."""
+def _ray_samples(tops, bots, tv, S, zero_oob):
+    """sample_pt_coarse in eval mode (misc.py:234-247) for the layer-wise walks: points [n,S,3] = top (1 - t) + bot t (two products and a sum, fp32) and
+    deltas [n,S] = ||top - bot|| / S, zero where zero_oob and the point lies outside [-1,1]^3 (deltas[Zero_Tool(Xs)] = 0).  The kernels' copy: csrc/ray_device.h."""
     n = tops.shape[0]
     t = tv.reshape(1, S, 1)
-    p = tops.unsqueeze(1) * (1.0 - t) + bots.unsqueeze(1) * t            # misc.py:240-241 (two products and a sum, fp32)
+    p = tops.unsqueeze(1) * (1.0 - t) + bots.unsqueeze(1) * t
     delta = (torch.sqrt(torch.sum((tops - bots) ** 2, 1)) / S).reshape(n, 1).expand(n, S)
     if zero_oob:
         delta = torch.where((p.abs() > 1).any(2), torch.zeros_like(delta), delta)
+    return p, delta
+
+
+def _visibility_layerwise(net, tops, bots, tv, S, zero_oob):
+    """exp(-sum_{j<S-1} rho_j delta_j) of a chunk of rays from the layer-wise density (networks without a fused kernel)."""
+    n = tops.shape[0]
+    p, delta = _ray_samples(tops, bots, tv, S, zero_oob)
     rho = net.forward_Classic_Sigma_Only(p.reshape(-1, 3)).reshape(n, S)
     return torch.exp(-torch.sum((rho * delta)[:, :-1], 1))
 
@@ -159,11 +167,7 @@ def _surface_layerwise(net, tops, bots, tv, S, zero_oob):
     """The four numbers of `ray_surface` for a chunk of rays from the density pass the network has (`forward_Classic_Sigma_Only`) and float64 sums:
     networks the ray-surface kernels do not serve.  PV is the exclusive prefix formed as get_PV forms it (Eval_Tools_2.py:13-16)."""
     n = tops.shape[0]
-    t = tv.reshape(1, S, 1)
-    p = tops.unsqueeze(1) * (1.0 - t) + bots.unsqueeze(1) * t
-    delta = (torch.sqrt(torch.sum((tops - bots) ** 2, 1)) / S).reshape(n, 1).expand(n, S)
-    if zero_oob:
-        delta = torch.where((p.abs() > 1).any(2), torch.zeros_like(delta), delta)
+    p, delta = _ray_samples(tops, bots, tv, S, zero_oob)
     rho = net.forward_Classic_Sigma_Only(p.reshape(-1, 3)).reshape(n, S)
     y = rho.double() * delta.double()
     c = torch.cumsum(torch.cat([torch.zeros_like(y[:, :1]), y], 1), 1)

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .evaluator import get_PV, sample_parameters_on
-from .render import _f32, _walks, world_angle_2_local_vec
+from .render import _f32, _ray_samples, _walks, world_angle_2_local_vec
 
 SCORE_KEYS = ("Acc", "Prec_Sun", "Recall_Sun", "Prec_Shadow", "Recall_Shadow", "Loss", "Avg_Error", "Avg_Offset")
 
@@ -55,22 +55,11 @@ class ShadowWalk:
         return _scores_from_sums(tot[0], tot[1], tot[2], tot[3], tot[4], float(n) * self.n_samples, offset)
 
 
-def _sample_points(tops, bots, tv, S, zero_oob):
-    """sample_pt_coarse in eval mode (misc.py:234-247) with deltas[Zero_Tool(Xs)] = 0: points [n,S,3] and deltas [n,S], fp32."""
-    n = tops.shape[0]
-    t = tv.reshape(1, S, 1)
-    p = tops.unsqueeze(1) * (1.0 - t) + bots.unsqueeze(1) * t
-    delta = (torch.sqrt(torch.sum((tops - bots) ** 2, 1)) / S).reshape(n, 1).expand(n, S)
-    if zero_oob:
-        delta = torch.where((p.abs() > 1).any(2), torch.zeros_like(delta), delta)
-    return p, delta
-
-
 def _shadow_layerwise(net, tops, bots, suns, tv, S, zero_oob):
     """The eight numbers of `shadow_walk` for a chunk of rays from `forward_Solar` on the sample points and float64 sums: networks the shadow-walk
     kernels do not serve.  PV is the exclusive prefix formed as get_PV forms it (Eval_Tools_2.py:13-16)."""
     n = tops.shape[0]
-    p, delta = _sample_points(tops, bots, tv, S, zero_oob)
+    p, delta = _ray_samples(tops, bots, tv, S, zero_oob)
     sun = suns.unsqueeze(1).expand(n, S, 3).reshape(-1, 3)
     rho, vis, _ = net.forward_Solar(p.reshape(-1, 3), sun, torch.zeros(n * S, 4, device=tops.device))
     y = rho.detach().reshape(n, S).double() * delta.double()
@@ -144,7 +133,7 @@ def eval_shadow_data(shadow_net, shadow_angles, ground_points, Z_points, world_c
         for i in range(M):
             for j in range(0, G, step):
                 k = min(j + step, G)
-                p, delta = _sample_points(tops[i, j:k], bots[i, j:k], tv, Z_points, True)
+                p, delta = _ray_samples(tops[i, j:k], bots[i, j:k], tv, Z_points, True)
                 n = (k - j) * Z_points
                 rho, vis, sky_raw = shadow_net.forward_Solar(p.reshape(-1, 3), suns[i].reshape(1, 3).expand(n, 3), torch.zeros(n, 4, device=dev))
                 pv = get_PV(rho.reshape(k - j, Z_points, 1), delta.reshape(k - j, Z_points, 1).contiguous())

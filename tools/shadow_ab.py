@@ -57,7 +57,7 @@ def per_sample_scores(net, suns, ground, dev, chunk=1 << 16):
         for i in range(0, M * G, chunk):
             j = min(M * G, i + chunk)
             n = j - i
-            p, delta = SE._sample_points(top[i:j], bot[i:j], tv, S, True)
+            p, delta = SE._ray_samples(top[i:j], bot[i:j], tv, S, True)
             rho, vis, _ = net.forward_Solar(p.reshape(-1, 3), sun[i:j].unsqueeze(1).expand(n, S, 3).reshape(-1, 3), torch.zeros(n * S, 4, device=dev))
             pv = sn.get_PV(rho.reshape(n, S, 1), delta.reshape(n, S, 1).contiguous()).reshape(n, S)
             vis = vis.reshape(n, S)
