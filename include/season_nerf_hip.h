@@ -446,6 +446,12 @@ int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out
  *   19 softmax_bwd_kernel       20 sigmoid_kernel            21 sigmoid_bwd_kernel         22 colsum_kernel
  *   23 copy_cols_kernel         24 bcast_rows_kernel         25 reduce_rows_kernel         26 fill_zero_kernel
  *   27 copy_f32_kernel          28 fill_zero_bytes_kernel    29 copy_bytes_kernel
+ *   30..39 wgrad_bf16x3_kernel<FULL, BNZ, TA, TB> (csrc/gemm.hip): 30 <F,F,1,2>  32 <F,F,2,2>  34 <F,F,1,4>  36 <F,F,2,4>  38 <T,F,2,4>, the odd number
+ *         after each the same block shape with BNZ (the BatchNorm ride)
+ *   40 thin_wgrad_kernel<false> 41 thin_wgrad_kernel<true>   42 thin_fwd_kernel<false>     43 thin_fwd_kernel<true>    (<true>: activation on load)
+ * "wgrad" returns more than a kernel number - one byte per launch, the first launch in the low byte, the second byte 0 when there was one launch:
+ *         kernel (30..39) | partial << 6 | reverse << 7;  partial: two-stage reduction through the partial-sum scratch (else fp32 atomics), reverse: the
+ *         stages ran from the last to the first (the direction's turn, taken from 32768 rows on).  Two launches: a BatchNorm layer with n_in > 256.
  * Operations - sizes | scalars | pointers ("?" = may be NULL):
  *   pe_points            n, n_samples, ld2 | - | points?, top?, bot?, tvals?, pe, pts?, pe2?     (points, or top + bot + tvals with n_samples | n)
  *   pe_small             rows, in_stride, n_dims, n_freq, out_stride | - | in, out
@@ -457,6 +463,21 @@ int snerf_trainer_debug_read(snerf_trainer* t, const char* name, float* host_out
  *   act_table            n | - | mu?, istd?, gamma?, beta? (all or none), dst
  *   sin_fwd              M, C, ldz, ldh | - | Z, H, mu?, istd?, gamma?, beta? (all or none)
  *   thin_dgrad           M, N, K, ldd, ldw, ldc, accumulate, eld | alpha | D, W, W3?, C, ez?, etab?, emu?, eistd?, stats?
+ *   wgrad                M, n_out, n_in, ldz, ldi, ldw, tab_cols, ldzz, M_global, route (1) | alpha, bias_alpha | dZ, In, dW, tab?, z?, gamma?, mu?, istd?, sdy?,
+ *                        sdyx?, dbias?   - the weight gradient as the engine issues it: a Product through run_wgrad on the Rows route (csrc/linear_product.h),
+ *                        dW [n_out, ldw] += alpha dZ^T H, H = In with sin(2 pi (a In + b)) over its first tab_cols columns (tab = [a | b], tab_cols each;
+ *                        tab and tab_cols go together).  z .. sdyx (all or none) are the BatchNorm block: dZ [M, ldz] holds dL/dY on entry and
+ *                        dL/dZ = gamma istd (dY - sdy / M_global - xhat sdyx / M_global) on exit, z [M, ldzz] is the pre-activation, dbias (optional) +=
+ *                        bias_alpha sum_m dZ; with n_in > 256 the layer goes as two launches (256 columns with the block, the rest on the finished dZ).
+ *                        Refused: leading dimensions below their column counts or (ldz, ldi, ldzz) from 2^24 on, a partial BatchNorm block, M_global < M,
+ *                        a ride that would not get one block over the inputs, route 0 (the exact fp32 GEMM: it takes neither a table nor the block, and has
+ *                        no kernel number - snerf_linear_wgrad runs it).
+ *   thin_wgrad           M, N, K, ldd, ldi, ldw, tab_cols | alpha | D, In, dW, dW3?, tab?      dW [K, ldw] += alpha D[:, :K]^T H; dW3 (K = 4 only): row 3
+ *                        of the result is added there instead (two heads as one product).  N a multiple of 4 in 4..1024, ldi a multiple of 4, In on 16 bytes.
+ *   thin_fwd             M, N, K, ldi, ldw, ldo, tab_cols | alpha | In, W, W3?, bias, bias3?, Out, tab?   Out [M, ldo][:, :K] = alpha (H W^T + bias); W3 / bias3
+ *                        (K = 4 only): row 3 of W / element 3 of bias are read there instead.  N a multiple of 4 in 4..256, ldi a multiple of 4, In on 16 bytes.
+ *                        Under a dry run (snerf_rows_debug_set) these three check their arguments, plan and return as always, launch nothing and read no
+ *                        pointer; a dry run's plan reports the direction the next launch will get and does not take its turn.
  *   point_out_fwd / point_out_bwd   n, n_samples, n_classes | - | head, adj, sv_raw, cls, rho, col, sv, adjust_col, d_rho, d_col, d_sv, d_head, d_adj, d_cls,
  *                        d_sv_raw   (each optional as the kernels allow)
  *   softmax              rows, C | - | logits, p             softmax_bwd   rows, C | - | p, dp, dlogits
@@ -473,7 +494,7 @@ int snerf_train_kernel_debug(const char* op, const int64_t* sizes, int n_sizes, 
  * snerf_rows_debug_set - state of the CALLING THREAD, (NULL, 0, 0) restores the default:
  *   switches8: NULL = the process's own environment switches, else eight ints that replace them for every reader - SNERF_GEMM_AREG, SNERF_GEMM_AREG_ACT,
  *              SNERF_AREG_HV, SNERF_GEMM_FULL, SNERF_GEMM_PF, SNERF_GEMM16, SNERF_GEMM16_K320, SNERF_SNAKE, in this order;
- *   dry_run:   snerf_linear_forward / snerf_linear_dgrad check their arguments and route as always; the route - and on the row-GEMM route the plan - is
+ *   dry_run:   snerf_linear_forward / snerf_linear_dgrad (and the weight-gradient operations of snerf_train_kernel_debug) check their arguments and route as always; the route - and on the row-GEMM route the plan - is
  *              recorded, nothing is launched and no pointer is dereferenced (any aligned non-null addresses will do: no GPU is needed);
  *   x_padded:  the public calls promise that the input's columns n_in .. the next multiple of 16 exist (ld_in covers them) and hold zeros, as the engine
  *              does for its K = 63 / 319 / 575 inputs.

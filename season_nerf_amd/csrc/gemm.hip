@@ -590,11 +590,11 @@ static thread_local LaunchCtx tl_ctx;
 void gemm_launch_context(float* wgrad_partial, size_t wgrad_floats, unsigned* parity) { tl_ctx = LaunchCtx{wgrad_partial, wgrad_floats, parity}; }
 size_t gemm_wgrad_partial_floats() { return (size_t)(gemm_device_cus(true) < 256 ? 256 : gemm_device_cus(true)) * 8 * 2 * 4 * 1024; }
 
-int stream_direction(int64_t rows) {
+int stream_direction(int64_t rows, bool take_turn) {
     static std::atomic<unsigned> launches{0};        // stand-alone launches (snerf_linear_*): one process-wide parity
     if (!rows_switches().snake || rows < 32768) return 0;                  // (a small launch neither gains from a direction nor takes a turn)
-    if (tl_ctx.parity) return (int)((*tl_ctx.parity)++ & 1u);
-    return (int)(launches.fetch_add(1, std::memory_order_relaxed) & 1u);
+    if (tl_ctx.parity) return (int)((take_turn ? (*tl_ctx.parity)++ : *tl_ctx.parity) & 1u);
+    return (int)((take_turn ? launches.fetch_add(1, std::memory_order_relaxed) : launches.load(std::memory_order_relaxed)) & 1u);      // (!take_turn: a plan made for inspection)
 }
 
 int gemm_device_cus(bool whole_xcds) {
@@ -914,31 +914,42 @@ static hipError_t launch_wgrad_as(const WgradX& g, dim3 grid, hipStream_t st) {
     return launch_big_lds<wgrad_bf16x3_kernel<FULL, BNZ, TA, TB>, 131072>(grid, dim3(512), 131072, st, g);
 }
 
-hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t ldi, int64_t M, int n_out, int n_in, float alpha,
-                               float* dW, int64_t ldw, hipStream_t st, const float* in_tab, int in_cols, const WgradBN* bn, int in_tab_stride) {
-    if (M <= 0 || n_out <= 0 || n_in <= 0) return hipSuccess;
-    if (ldz >= (1 << 24) || ldi >= (1 << 24)) return hipErrorInvalidValue;      // 32-bit lane offsets: 64 rows x ld
-    WgradX g{};
-    g.in_tab = in_tab; g.in_cols = in_tab ? in_cols : 0; g.in_tab_stride = in_tab_stride > 0 ? in_tab_stride : g.in_cols;
-    g.dZ = dZ; g.In = In; g.dW = dW; g.M = M; g.ldz = ldz; g.ldi = ldi; g.ldw = ldw; g.n_out = n_out; g.n_in = n_in; g.alpha = alpha;
+// The launcher's decisions, without a launch: the block shape and with it the kernel instance, the grid, the reduction and the direction.  take_turn = false
+// (a plan made for inspection: a dry run) reads the direction the next large launch would get and leaves the turn to it.
+WgradPlan plan_wgrad_bf16x3(int64_t M, int n_out, int n_in, bool bn, bool take_turn) {
+    WgradPlan p{};
     // the workgroup's block of dW: 128 TA x 64 TB - the 128-wide layers get blocks of their own size (SNERF_WGRAD_SMALL=0: always 256 x 256)
     static const int small_blocks = [] { const char* e = getenv("SNERF_WGRAD_SMALL"); return (e && e[0] == '0') ? 0 : 1; }();
-    const int ta = (small_blocks && n_out <= 128) ? 1 : 2, tb = (small_blocks && n_in <= 128) ? 2 : 4;
-    const int bo = 128 * ta, bi = 64 * tb;
-    const int by = (n_out + bo - 1) / bo, bz = (n_in + bi - 1) / bi;
-    int64_t bx = gemm_device_cus(true) / (by * bz);
+    p.ta = (small_blocks && n_out <= 128) ? 1 : 2; p.tb = (small_blocks && n_in <= 128) ? 2 : 4;
+    const int bo = 128 * p.ta, bi = 64 * p.tb;
+    p.by = (n_out + bo - 1) / bo; p.bz = (n_in + bi - 1) / bi;
+    int64_t bx = gemm_device_cus(true) / (p.by * p.bz);
     if (bx < 1) bx = 1;
     int64_t rows = (M + bx - 1) / bx;
     rows = (rows + WG_STAGE - 1) / WG_STAGE * WG_STAGE;
     if (rows < 4 * WG_STAGE) rows = 4 * WG_STAGE;
-    bx = (M + rows - 1) / rows;
-    g.rows_per_block = rows;
-    g.reverse = stream_direction(M);
+    p.bx = (M + rows - 1) / rows;
+    p.rows_per_block = rows;
+    p.reverse = stream_direction(M, take_turn);
     const bool full = n_out % 256 == 0 && n_in % 256 == 0;
-    const dim3 grid((unsigned)bx, by, bz);
+    p.kernel = TK_WGRAD_1X2 + 2 * (full ? 4 : (p.tb == 4 ? 2 : 0) + (p.ta == 2 ? 1 : 0)) + (bn ? 1 : 0);
     static const int two_stage = [] { const char* e = getenv("SNERF_WGRAD_ATOMIC"); return (e && e[0] == '1') ? 0 : 1; }();
     // (a few row blocks, or a thin layer whose blocks are mostly empty: the atomics are cheap enough)
-    if (two_stage && bx >= 8 && 2 * (int64_t)(n_out < bo ? n_out : bo) * (n_in < bi ? n_in : bi) >= (int64_t)bo * bi) {
+    p.partial = (two_stage && p.bx >= 8 && 2 * (int64_t)(n_out < bo ? n_out : bo) * (n_in < bi ? n_in : bi) >= (int64_t)bo * bi) ? 1 : 0;
+    return p;
+}
+
+hipError_t run_wgrad_bf16x3(const WgradPlan& p, float* dZ, int64_t ldz, const float* In, int64_t ldi, int64_t M, int n_out, int n_in, float alpha,
+                            float* dW, int64_t ldw, hipStream_t st, const float* in_tab, int in_cols, const WgradBN* bn, int in_tab_stride) {
+    WgradX g{};
+    g.in_tab = in_tab; g.in_cols = in_tab ? in_cols : 0; g.in_tab_stride = in_tab_stride > 0 ? in_tab_stride : g.in_cols;
+    g.dZ = dZ; g.In = In; g.dW = dW; g.M = M; g.ldz = ldz; g.ldi = ldi; g.ldw = ldw; g.n_out = n_out; g.n_in = n_in; g.alpha = alpha;
+    g.rows_per_block = p.rows_per_block;
+    g.reverse = p.reverse;
+    const int ta = p.ta, tb = p.tb, by = p.by, bz = p.bz;
+    const int64_t bx = p.bx;
+    const dim3 grid((unsigned)bx, by, bz);
+    if (p.partial) {
         g.partial = wgrad_scratch(st, (size_t)bx * by * bz * 8 * ta * tb * 1024);
         if (!g.partial) return hipErrorOutOfMemory;
     }
@@ -951,18 +962,39 @@ hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t 
         static const int log_shapes = [] { const char* e = getenv("SNERF_LOG_WGRAD"); return (e && e[0] == '1') ? 1 : 0; }();      // SNERF_LOG_WGRAD=1: one line per launch (which layers end up on which block shape)
         if (log_shapes)
             fprintf(stderr, "wgrad M=%lld n_out=%d n_in=%d ldz=%lld ldi=%lld ta=%d tb=%d full=%d bn=%d in_tab=%d grid=(%lld,%d,%d) rows/block=%lld partial=%d\n", (long long)M, n_out, n_in,
-                    (long long)ldz, (long long)ldi, ta, tb, (int)full, bn ? 1 : 0, in_tab ? in_cols : 0, (long long)bx, by, bz, (long long)rows, g.partial ? 1 : 0);
+                    (long long)ldz, (long long)ldi, ta, tb, (int)(p.kernel >= TK_WGRAD_FULL), bn ? 1 : 0, in_tab ? in_cols : 0, (long long)bx, by, bz, (long long)p.rows_per_block, g.partial ? 1 : 0);
     }
     hipError_t e;
-    if (full) e = bn ? launch_wgrad_as<true, true, 2, 4>(g, grid, st) : launch_wgrad_as<true, false, 2, 4>(g, grid, st);
-    else if (ta == 2 && tb == 4) e = bn ? launch_wgrad_as<false, true, 2, 4>(g, grid, st) : launch_wgrad_as<false, false, 2, 4>(g, grid, st);
-    else if (ta == 1 && tb == 4) e = bn ? launch_wgrad_as<false, true, 1, 4>(g, grid, st) : launch_wgrad_as<false, false, 1, 4>(g, grid, st);
-    else if (ta == 2 && tb == 2) e = bn ? launch_wgrad_as<false, true, 2, 2>(g, grid, st) : launch_wgrad_as<false, false, 2, 2>(g, grid, st);
-    else e = bn ? launch_wgrad_as<false, true, 1, 2>(g, grid, st) : launch_wgrad_as<false, false, 1, 2>(g, grid, st);
+    switch (p.kernel) {      // (in the order the instances have always been named in: it is the order of their code in the object)
+        case TK_WGRAD_FULL_BN: e = launch_wgrad_as<true, true, 2, 4>(g, grid, st); break;
+        case TK_WGRAD_FULL: e = launch_wgrad_as<true, false, 2, 4>(g, grid, st); break;
+        case TK_WGRAD_2X4_BN: e = launch_wgrad_as<false, true, 2, 4>(g, grid, st); break;
+        case TK_WGRAD_2X4: e = launch_wgrad_as<false, false, 2, 4>(g, grid, st); break;
+        case TK_WGRAD_1X4_BN: e = launch_wgrad_as<false, true, 1, 4>(g, grid, st); break;
+        case TK_WGRAD_1X4: e = launch_wgrad_as<false, false, 1, 4>(g, grid, st); break;
+        case TK_WGRAD_2X2_BN: e = launch_wgrad_as<false, true, 2, 2>(g, grid, st); break;
+        case TK_WGRAD_2X2: e = launch_wgrad_as<false, false, 2, 2>(g, grid, st); break;
+        case TK_WGRAD_1X2_BN: e = launch_wgrad_as<false, true, 1, 2>(g, grid, st); break;
+        case TK_WGRAD_1X2: e = launch_wgrad_as<false, false, 1, 2>(g, grid, st); break;
+        default: return hipErrorInvalidValue;
+    }
     if (e != hipSuccess) return e;
     if (g.partial)
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(8 * ta * tb * 4, by, bz), dim3(256), 0, st, g.partial, (int)bx, dW, ldw, n_out, n_in, alpha, ta, tb);
     return hipGetLastError();
+}
+
+// plan, then execute.  Test introspection (rows_debug.h): the plan is noted for snerf_train_kernel_debug, and under a dry run it takes no turn of the
+// direction and nothing is launched.
+hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t ldi, int64_t M, int n_out, int n_in, float alpha,
+                               float* dW, int64_t ldw, hipStream_t st, const float* in_tab, int in_cols, const WgradBN* bn, int in_tab_stride) {
+    if (M <= 0 || n_out <= 0 || n_in <= 0) return hipSuccess;
+    if (ldz >= (1 << 24) || ldi >= (1 << 24)) return hipErrorInvalidValue;      // 32-bit lane offsets: 64 rows x ld
+    const bool dry = rows_dry_run();
+    const WgradPlan p = plan_wgrad_bf16x3(M, n_out, n_in, bn != nullptr, !dry);
+    wgrad_note_plan(p.kernel | (p.partial << 6) | (p.reverse << 7));
+    if (dry) return (bn && p.bz != 1) ? hipErrorInvalidValue : hipSuccess;
+    return run_wgrad_bf16x3(p, dZ, ldz, In, ldi, M, n_out, n_in, alpha, dW, ldw, st, in_tab, in_cols, bn, in_tab_stride);
 }
 
 hipError_t launch_split_weights(SplitLayout layout, const float* W, int rows, int cols, bool transpose, uint16_t* frag, int n_tiles, int ksteps,

@@ -33,7 +33,8 @@ struct Policy {          // who calls: every intended difference between the eng
 struct Epilogue { const float *z = nullptr, *tab = nullptr, *mu = nullptr, *istd = nullptr; int64_t ld = 0; double* sums = nullptr; };
 struct Product {
     int64_t M = 0; int n_in = 0, n_out = 0; float alpha = 1.f;
-    const float *W = nullptr, *bias = nullptr; float* dW = nullptr;                    // [n_out, n_in] (ld n_in), [n_out];  wgrad: dW += (ld n_in)
+    const float *W = nullptr, *bias = nullptr; float* dW = nullptr;                    // [n_out, n_in] (ld n_in), [n_out];  wgrad: dW += (ld n_in, or lddw)
+    int64_t lddw = 0;                                                                  // wgrad, Rows route: row stride of dW where it is not n_in (0; test hook only)
     // second head: row 3 of W / bias / dW lives here instead (colour rows 0..2 + density row 3 as one K = 4 product; thin route only)
     const float *W3 = nullptr, *bias3 = nullptr; float* dW3 = nullptr;
     // the layer's input [M, ldx];  activation on load: its first tab_cols columns are pre-activations, tab = [a | b];  x_padded: columns n_in .. next multiple of 16 exist and hold zeros
@@ -149,16 +150,17 @@ inline hipError_t run_dgrad(const Product& p, Route r, hipStream_t st) {
 inline hipError_t run_wgrad(const Product& p, Route r, hipStream_t st) {
     if (r == Route::Thin) return launch_thin_wgrad(thin_wgrad_args(p), st);
     if (r == Route::Rows) {
+        const int64_t ldw = p.lddw ? p.lddw : p.n_in;
         if (p.bn && p.n_in > 256) {
             // The BatchNorm dZ pass (engine only) rides in the kernel for one block column over the inputs (in-place dZ): a layer with more than 256 inputs (fc5: [fc4 | PE]) goes as two
             // launches, the first 256 input columns with the dZ pass, then the rest on the finished dZ.  Each launch gets its window of the activation-on-load table ([a | b], b at distance tc).
             const int n0 = 256, tc = p.tab_cols;
-            hipError_t e = launch_wgrad_bf16x3(p.Y, p.ldy, p.X, p.ldx, p.M, p.n_out, n0, p.alpha, p.dW, p.n_in, st, p.tab, tc < n0 ? tc : n0, p.bn, tc);
+            hipError_t e = launch_wgrad_bf16x3(p.Y, p.ldy, p.X, p.ldx, p.M, p.n_out, n0, p.alpha, p.dW, ldw, st, p.tab, tc < n0 ? tc : n0, p.bn, tc);
             if (e != hipSuccess) return e;
             const int rest = tc > n0 ? tc - n0 : 0;
-            return launch_wgrad_bf16x3(p.Y, p.ldy, p.X + n0, p.ldx, p.M, p.n_out, p.n_in - n0, p.alpha, p.dW + n0, p.n_in, st, rest ? p.tab + n0 : nullptr, rest, nullptr, tc);
+            return launch_wgrad_bf16x3(p.Y, p.ldy, p.X + n0, p.ldx, p.M, p.n_out, p.n_in - n0, p.alpha, p.dW + n0, ldw, st, rest ? p.tab + n0 : nullptr, rest, nullptr, tc);
         }
-        return launch_wgrad_bf16x3(p.Y, p.ldy, p.X, p.ldx, p.M, p.n_out, p.n_in, p.alpha, p.dW, p.n_in, st, p.tab, p.tab_cols, p.bn);
+        return launch_wgrad_bf16x3(p.Y, p.ldy, p.X, p.ldx, p.M, p.n_out, p.n_in, p.alpha, p.dW, ldw, st, p.tab, p.tab_cols, p.bn);
     }
     if (p.bn || p.tab) return hipErrorInvalidValue;
     return launch_gemm(gemm_wgrad_args(p), st);

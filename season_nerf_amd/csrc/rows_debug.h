@@ -18,6 +18,13 @@ inline std::atomic<bool> rows_record_on{false};
 // kernel = -1 and the rest 0 - RowsPlan's kernel (RowsKernel), nt, pf, aol, act, hv, tab_lds, zero_bn, split (SplitLayout), grid, LDS bytes.
 constexpr int ROWS_RECORD_INTS = 12;
 
+// the weight-gradient launches of the calling thread since wgrad_note_begin (snerf_train_kernel_debug "wgrad"): per launch kernel | partial << 6 | reverse << 7
+struct WgradNote { bool on; int n; int v[2]; };
+inline thread_local WgradNote tl_wgrad_note = {false, 0, {0, 0}};
+inline void wgrad_note_begin() { tl_wgrad_note = WgradNote{true, 0, {0, 0}}; }
+inline void wgrad_note_plan(int packed) { if (tl_wgrad_note.on && tl_wgrad_note.n < 2) tl_wgrad_note.v[tl_wgrad_note.n++] = packed; }
+inline int wgrad_note_end() { tl_wgrad_note.on = false; return tl_wgrad_note.n == 0 ? -1 : tl_wgrad_note.v[0] | (tl_wgrad_note.n > 1 ? tl_wgrad_note.v[1] << 8 : 0); }
+
 inline bool rows_dry_run() { return tl_rows_debug.active && tl_rows_debug.dry_run; }
 inline bool rows_x_padded() { return tl_rows_debug.active && tl_rows_debug.x_padded; }
 inline bool rows_noting() { return rows_record_on.load(std::memory_order_relaxed) || rows_dry_run(); }

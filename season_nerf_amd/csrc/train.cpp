@@ -824,7 +824,7 @@ int snerf_train_kernel_debug(const char* op, const int64_t* s, int n_sizes, cons
         {"thin_dgrad", 8, 1, 9}, {"point_out_fwd", 3, 0, 15}, {"point_out_bwd", 3, 0, 15}, {"softmax", 2, 0, 2}, {"softmax_bwd", 2, 0, 3},
         {"sigmoid", 1, 0, 2}, {"sigmoid_bwd", 1, 0, 3}, {"colsum", 3, 1, 2}, {"copy_cols", 5, 0, 2}, {"bcast_rows", 5, 0, 2},
         {"reduce_rows", 5, 0, 2}, {"fill_zero", 1, 0, 1}, {"copy_f32", 1, 0, 2}, {"fill_zero_bytes", 1, 0, 1}, {"copy_bytes", 1, 0, 2},
-        {"colpass_rows_per_block", 2, 0, 0}, {"thin_dgrad_rows_per_block", 2, 0, 0}};
+        {"colpass_rows_per_block", 2, 0, 0}, {"thin_dgrad_rows_per_block", 2, 0, 0}, {"wgrad", 10, 2, 11}, {"thin_wgrad", 7, 1, 5}, {"thin_fwd", 7, 1, 7}};
     if (!op) return snerf_set_error(SNERF_E_INVALID, "snerf_train_kernel_debug: NULL operation name");
     const std::string k = op;
     const OpDesc* d = nullptr;
@@ -923,6 +923,56 @@ int snerf_train_kernel_debug(const char* op, const int64_t* s, int n_sizes, cons
         if (!thin_dgrad_ok(a)) return bad("thin_dgrad_ok refuses the shape (N, ldc, eld multiples of 4, 16-byte bases, table and sums with ez)");
         kernel = thin_dgrad_choice(a);
         e = launch_thin_dgrad(a, st);
+    } else if (k == "wgrad") {               // sizes M, n_out, n_in, ldz, ldi, ldw, tab_cols, ldzz, M_global, route; scalars alpha, bias_alpha;
+                                             // pointers dZ, In, dW, tab, z, gamma, mu, istd, sdy, sdyx, dbias
+        const bool ride = p[4] != nullptr;
+        if (s[9] > 1) return bad("route must be 1 (Rows) or 0 (exact fp32)");
+        if (s[0] < 1 || s[1] < 1 || s[2] < 1 || !fits_int(s[1]) || !fits_int(s[2])) return bad("M, n_out or n_in < 1");
+        if (!p[0] || !p[1] || !p[2]) return bad("dZ, In or dW is NULL");
+        if (s[3] < s[1] || s[4] < s[2] || s[5] < s[2]) return bad("a leading dimension below its column count");
+        if (s[3] >= (1 << 24) || s[4] >= (1 << 24) || (ride && s[7] >= (1 << 24))) return bad("a leading dimension of 2^24 or more (32-bit lane offsets over 64 rows)");
+        if ((p[3] != nullptr) != (s[6] > 0) || s[6] > s[2]) return bad("the table needs 1 <= tab_cols <= n_in, tab_cols needs the table");
+        for (int i = 5; i < 10; ++i)
+            if ((p[i] != nullptr) != ride) return bad("the BatchNorm block (z, gamma, mu, istd, sdy, sdyx) is all set or all NULL");
+        if (!ride && p[10]) return bad("dbias without the BatchNorm block");
+        if (ride && (s[7] < s[1] || s[8] < s[0])) return bad("the BatchNorm block needs ldzz >= n_out (a leading dimension) and M_global >= M");
+        if (s[9] == 0) return bad((ride || p[3]) ? "a table or a BatchNorm block needs the Rows route" : "the exact fp32 route has no kernel number: snerf_linear_wgrad runs it");
+        // the ride writes dZ in place: one block over the inputs (bz = 1) per launch - the whole layer up to 256 inputs, the first 256 of a wider one (run_wgrad's split)
+        if (ride && plan_wgrad_bf16x3(s[0], (int)s[1], s[2] > 256 ? 256 : (int)s[2], true, false).bz != 1) return bad("the BatchNorm ride needs bz = 1 and this layer cannot be split to get it");
+        Product q;
+        q.M = s[0]; q.n_out = (int)s[1]; q.n_in = (int)s[2]; q.alpha = f[0]; q.Y = F(0); q.ldy = s[3]; q.X = F(1); q.ldx = s[4]; q.dW = F(2); q.lddw = s[5];
+        q.tab = F(3); q.tab_cols = (int)s[6];
+        const WgradBN bn{F(4), s[7], F(5), F(6), F(7), F(8), F(9), 1.f / (float)s[8], f[1], F(10)};
+        if (ride) q.bn = &bn;
+        wgrad_note_begin();
+        e = run_wgrad(q, Route::Rows, st);
+        kernel = wgrad_note_end();
+    } else if (k == "thin_wgrad") {          // sizes M, N, K, ldd, ldi, ldw, tab_cols; scalar alpha; pointers D, In, dW, dW3, tab
+        ThinWgradArgs a{};
+        a.M = s[0]; a.N = (int)s[1]; a.K = (int)s[2]; a.ldd = s[3]; a.ldi = s[4]; a.ldw = s[5]; a.tab_cols = (int)s[6]; a.tab_stride = a.tab_cols; a.alpha = f[0];
+        a.D = F(0); a.In = F(1); a.dW = F(2); a.dW3 = F(3); a.tab = F(4);
+        if (s[2] < 1 || s[2] > 4) return bad("K must be 1..4");
+        if (s[0] < 1 || s[1] < 4 || s[1] > 1024 || a.ldd < a.K || a.ldi < a.N || a.ldw < a.N) return bad("M < 1, N outside 4..1024 or a leading dimension below its column count");
+        if (!a.D || !a.In || !a.dW) return bad("D, In or dW is NULL");
+        if (a.dW3 && a.K != 4) return bad("dW3 needs K = 4");
+        if ((a.tab != nullptr) != (s[6] > 0) || s[6] > s[1]) return bad("the table needs 1 <= tab_cols <= N, tab_cols needs the table");
+        if (!thin_wgrad_ok(a)) return bad("thin_wgrad_ok refuses the shape (N and ldi multiples of 4, In on 16 bytes)");
+        kernel = thin_wgrad_choice(a);
+        if (rows_dry_run()) return kernel;
+        e = launch_thin_wgrad(a, st);
+    } else if (k == "thin_fwd") {            // sizes M, N, K, ldi, ldw, ldo, tab_cols; scalar alpha; pointers In, W, W3, bias, bias3, Out, tab
+        ThinFwdArgs a{};
+        a.M = s[0]; a.N = (int)s[1]; a.K = (int)s[2]; a.ldi = s[3]; a.ldw = s[4]; a.ldo = s[5]; a.tab_cols = (int)s[6]; a.tab_stride = a.tab_cols; a.alpha = f[0];
+        a.In = F(0); a.W = F(1); a.W3 = F(2); a.bias = F(3); a.bias3 = F(4); a.Out = F(5); a.tab = F(6);
+        if (s[2] < 1 || s[2] > 4) return bad("K must be 1..4");
+        if (s[0] < 1 || s[1] < 4 || s[1] > 256 || a.ldi < a.N || a.ldw < a.N || a.ldo < a.K) return bad("M < 1, N outside 4..256 or a leading dimension below its column count");
+        if (!a.In || !a.W || !a.bias || !a.Out) return bad("In, W, bias or Out is NULL");
+        if ((a.W3 || a.bias3) && a.K != 4) return bad("W3 and bias3 need K = 4");
+        if ((a.tab != nullptr) != (s[6] > 0) || s[6] > s[1]) return bad("the table needs 1 <= tab_cols <= N, tab_cols needs the table");
+        if (!thin_fwd_ok(a)) return bad("thin_fwd_ok refuses the shape (N and ldi multiples of 4, In on 16 bytes)");
+        kernel = thin_fwd_choice(a);
+        if (rows_dry_run()) return kernel;
+        e = launch_thin_fwd(a, st);
     } else if (k == "point_out_fwd" || k == "point_out_bwd") {      // sizes n, n_samples, C; pointers in the order of PointOutArgs
         const bool bwd = k == "point_out_bwd";
         PointOutArgs a{};

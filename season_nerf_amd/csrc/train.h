@@ -63,13 +63,21 @@ struct WgradBN {
     float bias_alpha;
     float* dbias;              // += bias_alpha * sum_m dZ
 };
-int stream_direction(int64_t rows);      // 0 / 1, alternating per large streaming launch (gemm.hip)
+int stream_direction(int64_t rows, bool take_turn = true);      // 0 / 1, alternating per large streaming launch (gemm.hip); !take_turn: the next launch's, left to it
 // per-thread launch context of a training pass: the trainer's wgrad partial-sum scratch and its launch parity (nullptr / 0: none)
 void gemm_launch_context(float* wgrad_partial, size_t wgrad_floats, unsigned* parity);
 size_t gemm_wgrad_partial_floats();      // floats the two-stage weight-gradient reduction needs at most (grid blocks x 8 x 8 x 1024)
 hipError_t launch_wgrad_bf16x3(float* dZ, int64_t ldz, const float* In, int64_t ldi, int64_t M, int n_out, int n_in, float alpha,
                                float* dW, int64_t ldw, hipStream_t st, const float* in_tab = nullptr, int in_cols = 0,
                                const WgradBN* bn = nullptr, int in_tab_stride = 0);      // in_tab_stride: see WgradX (0 = in_cols)
+// ... as a plan and its execution (launch_wgrad_bf16x3 is the two in a row; plan_gemm_rows / run_gemm_rows are the row GEMMs' pair).  The plan launches
+// nothing and reads no pointer: kernel = the TK_WGRAD_* instance, the workgroup's block of dW is 128 ta x 64 tb, the grid (bx, by, bz) = row blocks x
+// blocks over n_out x blocks over n_in, partial = two-stage reduction through the partial-sum scratch (else atomics), reverse = stream_direction().
+// take_turn = false: a plan for inspection - the direction is the one the next large launch will get, and that launch still gets it.
+struct WgradPlan { int kernel, ta, tb; int64_t bx; int by, bz; int64_t rows_per_block; int partial, reverse; };
+WgradPlan plan_wgrad_bf16x3(int64_t M, int n_out, int n_in, bool bn, bool take_turn = true);
+hipError_t run_wgrad_bf16x3(const WgradPlan& p, float* dZ, int64_t ldz, const float* In, int64_t ldi, int64_t M, int n_out, int n_in, float alpha,
+                            float* dW, int64_t ldw, hipStream_t st, const float* in_tab, int in_cols, const WgradBN* bn, int in_tab_stride);
 
 // ---- elementwise / reduction kernels of the training path (train_kernels.hip)
 // The kernel a launcher runs, as the test hook snerf_train_kernel_debug returns it (include/season_nerf_hip.h documents the numbers).  Where a launcher
@@ -78,7 +86,10 @@ enum TrainKernel : int {
     TK_PE_POINTS = 0, TK_PE_SMALL, TK_COLREDUCE, TK_COLPASS_VEC1, TK_COLPASS_VEC2, TK_COLPASS_VEC3, TK_COLPASS_VEC4, TK_BN_BWD2, TK_BN_FINALIZE,
     TK_BN_FINALIZE_SHIFTED, TK_ACT_SUMS_FINALIZE, TK_ACT_TABLE, TK_SIN_FWD, TK_SIN_FWD_VEC, TK_THIN_DGRAD, TK_THIN_DGRAD_ACT, TK_POINT_OUT_FWD,
     TK_POINT_OUT_BWD, TK_SOFTMAX, TK_SOFTMAX_BWD, TK_SIGMOID, TK_SIGMOID_BWD, TK_COLSUM, TK_COPY_COLS, TK_BCAST_ROWS, TK_REDUCE_ROWS, TK_FILL_ZERO,
-    TK_COPY_F32, TK_FILL_ZERO_BYTES, TK_COPY_BYTES, TK_COUNT
+    TK_COPY_F32, TK_FILL_ZERO_BYTES, TK_COPY_BYTES,
+    // wgrad_bf16x3_kernel<FULL, BNZ, TA, TB> (gemm.hip): block shape TA x TB, _BN = BNZ; TK_WGRAD_FULL = <true, ., 2, 4>.  plan_wgrad_bf16x3 relies on the order.
+    TK_WGRAD_1X2, TK_WGRAD_1X2_BN, TK_WGRAD_2X2, TK_WGRAD_2X2_BN, TK_WGRAD_1X4, TK_WGRAD_1X4_BN, TK_WGRAD_2X4, TK_WGRAD_2X4_BN, TK_WGRAD_FULL, TK_WGRAD_FULL_BN,
+    TK_THIN_WGRAD, TK_THIN_WGRAD_ACT, TK_THIN_FWD, TK_THIN_FWD_ACT, TK_COUNT
 };
 struct PeArgs {            // positions (from rays or explicit) -> PE(pos) [N,64] (63 features + zero pad) and points [N,3]
     int64_t n;
@@ -145,6 +156,7 @@ struct ThinFwdArgs {       // forward of heads with K <= 4 outputs in all as one
     int tab_cols, tab_stride;
 };
 bool thin_fwd_ok(const ThinFwdArgs& a);
+inline int thin_fwd_choice(const ThinFwdArgs& a) { return (a.tab && a.tab_cols > 0) ? TK_THIN_FWD_ACT : TK_THIN_FWD; }            // thin_fwd_kernel<true / false>
 hipError_t launch_thin_fwd(const ThinFwdArgs& a, hipStream_t st);
 struct ThinWgradArgs {     // weight gradient of a head with K <= 4 outputs as a stream over its input (train_kernels.hip: thin_wgrad_kernel)
     const float* D;        // [M, ldd]: dL/d(head output), K leading columns
@@ -160,6 +172,7 @@ struct ThinWgradArgs {     // weight gradient of a head with K <= 4 outputs as a
 };
 float* gemm_partial_scratch(hipStream_t st, size_t floats);      // gemm.hip: the calling trainer's pre-carved partial-sum scratch (or the stream's own)
 bool thin_wgrad_ok(const ThinWgradArgs& a);
+inline int thin_wgrad_choice(const ThinWgradArgs& a) { return (a.tab && a.tab_cols > 0) ? TK_THIN_WGRAD_ACT : TK_THIN_WGRAD; }      // thin_wgrad_kernel<true / false>
 hipError_t launch_thin_wgrad(const ThinWgradArgs& a, hipStream_t st);
 
 // BatchNorm finalize: mean = sum/M, var = m2/M, istd; EMA of running stats (momentum 0.01, unbiased var)

@@ -448,7 +448,7 @@ hipError_t launch_thin_fwd(const ThinFwdArgs& a, hipStream_t st) {
     const int rows = 4 * (256 / cpt);
     int64_t blocks = (a.M + rows - 1) / rows;
     if (blocks > 2048) blocks = 2048;
-    if (a.tab && a.tab_cols > 0) hipLaunchKernelGGL((thin_fwd_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt);
+    if (thin_fwd_choice(a) == TK_THIN_FWD_ACT) hipLaunchKernelGGL((thin_fwd_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt);
     else hipLaunchKernelGGL((thin_fwd_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, a, C4, cpt);
     return hipGetLastError();
 }
@@ -581,7 +581,7 @@ hipError_t launch_thin_wgrad(const ThinWgradArgs& a, hipStream_t st) {
     ThinWgradArgs b = a;
     b.partial = gemm_partial_scratch(st, (size_t)blocks * a.K * a.N);
     if (!b.partial) return hipErrorOutOfMemory;
-    if (a.tab && a.tab_cols > 0) hipLaunchKernelGGL((thin_wgrad_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, b, C4, cpt, rpb);
+    if (thin_wgrad_choice(a) == TK_THIN_WGRAD_ACT) hipLaunchKernelGGL((thin_wgrad_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, b, C4, cpt, rpb);
     else hipLaunchKernelGGL((thin_wgrad_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, b, C4, cpt, rpb);
     hipLaunchKernelGGL(thin_wgrad_reduce_kernel, dim3((unsigned)((a.K * a.N + 31) / 32)), dim3(256), 0, st, b.partial, (int)blocks, a.K, a.N, a.dW, a.ldw, a.alpha, a.dW3);
     return hipGetLastError();

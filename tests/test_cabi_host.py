@@ -778,10 +778,64 @@ def test_train_kernel_debug_refuses_before_any_launch(lib):
     refused("fill_zero", [8], [], [None], "NULL")
     refused("copy_bytes", [8], [], [a, None], "NULL")
     refused("colpass_rows_per_block", [8, 6], [], [], "multiple of 4")
-    ops = {"pe_points", "pe_small", "colreduce", "bn_bwd2", "bn_finalize", "bn_finalize_shifted", "act_sums_finalize", "act_table", "sin_fwd", "thin_dgrad",
+    # the weight gradients: sizes M, n_out, n_in, ldz, ldi, ldw, tab_cols, ldzz, M_global, route; pointers dZ, In, dW, tab, z, gamma, mu, istd, sdy, sdyx, dbias
+    wg = lambda **kw: [kw.get(k) for k in ("dZ", "In", "dW", "tab", "z", "gamma", "mu", "istd", "sdy", "sdyx", "dbias")]
+    io = dict(dZ=a, In=a, dW=a)
+    bn = dict(z=a, gamma=a, mu=a, istd=a, sdy=a, sdyx=a)
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0], [1.0, 1.0], wg(**io), "wrong number")
+    refused("wgrad", [0, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io), "< 1")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(dZ=a, In=a), "NULL")
+    refused("wgrad", [8, 64, 64, 63, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io), "leading dimension")          # short ldz, ldi, ldw, ldzz
+    refused("wgrad", [8, 64, 64, 64, 63, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io), "leading dimension")
+    refused("wgrad", [8, 64, 64, 64, 64, 63, 0, 0, 0, 1], [1.0, 1.0], wg(**io), "leading dimension")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 63, 8, 1], [1.0, 1.0], wg(**io, **bn), "leading dimension")
+    refused("wgrad", [8, 64, 64, 1 << 24, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io), "2^24")                    # 32-bit lane offsets: ldz, ldi, and the ride's ldzz
+    refused("wgrad", [8, 64, 64, 64, 1 << 24, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io), "2^24")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 1 << 24, 8, 1], [1.0, 1.0], wg(**io, **bn), "2^24")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 64, 7, 1], [1.0, 1.0], wg(**io, **bn), "M_global")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 64, 8, 1], [1.0, 1.0], wg(**io, **{**bn, "istd": None}), "all set or all NULL")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io, mu=a), "all set or all NULL")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io, dbias=a), "dbias without")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 65, 0, 0, 1], [1.0, 1.0], wg(**io, tab=a), "tab_cols")             # more table columns than inputs
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 8, 0, 0, 1], [1.0, 1.0], wg(**io), "tab_cols")                     # columns without a table, a table without columns
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io, tab=a), "tab_cols")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 8, 0, 0, 0], [1.0, 1.0], wg(**io, tab=a), "needs the Rows route")  # the exact fp32 GEMM takes neither
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 64, 8, 0], [1.0, 1.0], wg(**io, **bn), "needs the Rows route")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 0], [1.0, 1.0], wg(**io), "no kernel number")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 2], [1.0, 1.0], wg(**io), "route must be")
+    refused("wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(dZ=a, In=a + 2, dW=a), "aligned")
+    # the thin heads' streams: sizes M, N, K, ldd / ldi, ldi / ldw, ldw / ldo, tab_cols; pointers D, In, dW, dW3, tab / In, W, W3, bias, bias3, Out, tab
+    refused("thin_wgrad", [8, 8, 5, 8, 8, 8, 0], [1.0], [a, a, a, None, None], "K must be")
+    refused("thin_wgrad", [8, 2048, 4, 4, 2048, 2048, 0], [1.0], [a, a, a, None, None], "N outside")
+    refused("thin_wgrad", [8, 8, 4, 3, 8, 8, 0], [1.0], [a, a, a, None, None], "leading dimension")
+    refused("thin_wgrad", [8, 8, 4, 4, 8, 7, 0], [1.0], [a, a, a, None, None], "leading dimension")
+    refused("thin_wgrad", [8, 8, 4, 4, 8, 8, 0], [1.0], [a, None, a, None, None], "NULL")
+    refused("thin_wgrad", [8, 8, 3, 4, 8, 8, 0], [1.0], [a, a, a, a, None], "dW3 needs")
+    refused("thin_wgrad", [8, 8, 4, 4, 8, 8, 9], [1.0], [a, a, a, None, a], "tab_cols")
+    refused("thin_wgrad", [8, 8, 4, 4, 8, 8, 4], [1.0], [a, a, a, None, None], "tab_cols")
+    refused("thin_wgrad", [8, 6, 4, 4, 8, 8, 0], [1.0], [a, a, a, None, None], "thin_wgrad_ok")                 # N % 4
+    refused("thin_wgrad", [8, 8, 4, 4, 9, 9, 0], [1.0], [a, a, a, None, None], "thin_wgrad_ok")                 # ldi % 4: misaligned rows
+    refused("thin_wgrad", [8, 8, 4, 4, 8, 8, 0], [1.0], [a, a + 4, a, None, None], "thin_wgrad_ok")             # In off 16 bytes
+    refused("thin_fwd", [8, 8, 0, 8, 8, 4, 0], [1.0], [a, a, None, a, None, a, None], "K must be")
+    refused("thin_fwd", [8, 512, 4, 512, 512, 4, 0], [1.0], [a, a, None, a, None, a, None], "N outside")
+    refused("thin_fwd", [8, 8, 4, 8, 8, 3, 0], [1.0], [a, a, None, a, None, a, None], "leading dimension")
+    refused("thin_fwd", [8, 8, 4, 8, 8, 4, 0], [1.0], [a, a, None, None, None, a, None], "NULL")                # the stream always adds a bias
+    refused("thin_fwd", [8, 8, 3, 8, 8, 4, 0], [1.0], [a, a, a, a, None, a, None], "need K = 4")
+    refused("thin_fwd", [8, 8, 3, 8, 8, 4, 0], [1.0], [a, a, None, a, a, a, None], "need K = 4")
+    refused("thin_fwd", [8, 8, 4, 8, 8, 4, 9], [1.0], [a, a, None, a, None, a, a], "tab_cols")
+    refused("thin_fwd", [8, 8, 4, 9, 8, 4, 0], [1.0], [a, a, None, a, None, a, None], "thin_fwd_ok")            # ldi % 4
+    refused("thin_fwd", [8, 8, 4, 8, 8, 4, 0], [1.0], [a + 4, a, None, a, None, a, None], "thin_fwd_ok")        # In off 16 bytes
+    ops = {"wgrad", "thin_wgrad", "thin_fwd","pe_points", "pe_small", "colreduce", "bn_bwd2", "bn_finalize", "bn_finalize_shifted", "act_sums_finalize", "act_table", "sin_fwd", "thin_dgrad",
            "point_out_fwd", "point_out_bwd", "softmax", "softmax_bwd", "sigmoid", "colsum", "copy_cols", "bcast_rows", "reduce_rows", "fill_zero", "copy_bytes"}
     assert ops <= set(bad)
     # what needs no launch answers without a GPU: the launchers' own block sizes
     assert _tk_call(lib, "colpass_rows_per_block", [1221, 64], [], []) == 32
     assert _tk_call(lib, "colpass_rows_per_block", [1 << 20, 64], [], []) == 512
     assert _tk_call(lib, "thin_dgrad_rows_per_block", [100, 4], [], []) == 256
+    # ... and under a dry run (snerf_rows_debug_set) the weight gradient's plan: kernel | partial << 6 | reverse << 7 per launch, the split's second in the next byte
+    assert lib.snerf_rows_debug_set(None, 1, 0) == 0
+    assert _tk_call(lib, "wgrad", [8, 64, 64, 64, 64, 64, 0, 0, 0, 1], [1.0, 1.0], wg(**io)) == 30
+    assert _tk_call(lib, "wgrad", [8, 512, 576, 512, 576, 576, 512, 512, 8, 1], [30.0, 30.0], wg(**io, **bn, tab=a)) == 39 | 36 << 8
+    assert _tk_call(lib, "thin_wgrad", [8, 8, 4, 4, 8, 8, 4], [1.0], [a, a, a, a, a]) == 41
+    assert _tk_call(lib, "thin_fwd", [8, 8, 4, 8, 8, 4, 0], [1.0], [a, a, a, a, a, a, None]) == 42
+    assert lib.snerf_rows_debug_set(None, 0, 0) == 0

@@ -116,8 +116,8 @@ THIN = [  # M, n_in, n_out, ld_go, ld_in, offset of the gradient's first column,
 
 @pytest.mark.parametrize("shape", THIN)
 def test_thin_head_wgrad(shape):
-    """The weight gradient of a head with at most four outputs runs as a stream over its input (thin_wgrad_kernel: exact fp32 FMAs, one atomic add per
-    block and element), with the gradient read as 16-byte rows where its address allows (the colour head) and as scalars where not (the density head:
+    """The weight gradient of a head with at most four outputs runs as a stream over its input (thin_wgrad_kernel: exact fp32 FMAs, every block's K x N sums
+    left in the partial-sum scratch and added up in a fixed order by thin_wgrad_reduce_kernel - no atomics), with the gradient read as 16-byte rows where its address allows (the colour head) and as scalars where not (the density head:
     column 3 of the same [N, 4] buffer), and with the activation applied on load over the leading columns."""
     sn, L, st = _env()
     M, n_in, n_out, ld_go, ld_in, off, ac = shape
