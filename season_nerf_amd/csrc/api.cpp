@@ -30,6 +30,41 @@ int snerf_set_error(int code, const std::string& msg) { return fail(code, msg); 
 static int fail_hip(hipError_t e, const char* what) {
     return fail(SNERF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+static int fail_pack(const std::string& err) {      // what the packer and the error model report: a tensor that is not there, or one of the wrong shape
+    return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
+}
+
+// A/B switches of the environment, read once per process
+struct Switches {
+    bool i8_one_wave;             // SNERF_I8_ONE_WAVE=1: the one-wave int8 kernel (kernels_i8.hip) where the two-wave kernel would run
+    bool i8x2_mfma32;             // SNERF_I8X2_MFMA32=1: the two-wave kernel's 32x32x32 code and stream where its 16x16x64 instances would run
+    bool group_f32;               // SNERF_GROUP_F32=1: width 512, the per-ray networks in the exact-fp32 layer-wise form of rounds 3-5
+    bool group_one_wave;          // SNERF_GROUP_ONE_WAVE=1: snerf_set_group_kernel starts at 1
+    bool rayvis_no_early_out;     // SNERF_RAYVIS_NO_EARLY_OUT=1: ray visibility walks every pass of every ray (mlp_device.h raysum_saturated)
+    bool rayvis_sun_first;        // SNERF_RAYVIS_SUN_FIRST=1: ... its passes in the order before round 6's reversal
+};
+static const Switches& switches() {
+    const auto on = [](const char* name) { return getenv(name) != nullptr; };
+    static const Switches s{on("SNERF_I8_ONE_WAVE"), on("SNERF_I8X2_MFMA32"), on("SNERF_GROUP_F32"), on("SNERF_GROUP_ONE_WAVE"), on("SNERF_RAYVIS_NO_EARLY_OUT"),
+                            on("SNERF_RAYVIS_SUN_FIRST")};
+    return s;
+}
+
+// The packed programs of a model, under the program numbers of snerf_model_pack_host
+enum : int {
+    P_FIELD = PROG_FIELD,      // field network, bf16 pairs in the canonical order (kernels.hip: widths 64, 256)
+    P_GROUP = PROG_GROUP,      // per-ray (time / sun) networks, likewise
+    P_I8 = 2,                  // field network in the int8-digit format (SNERF_PREC_I8X3 only)
+    P_KS = 3,                  // P_FIELD in the K-split order of kernels_ks.hip (width 512)
+    P_KSG = 4,                 // P_GROUP in the same order: width 512 under every precision (round 6; exact fp32 layer by layer before)
+    P_K64 = 5,                 // P_I8's digits in the layout of v_mfma_i32_16x16x64_i8 (program.h "k64": what kernels_i8x2.hip runs at W = 256)
+    P_NUM = 6
+};
+struct ProgramSlot {
+    Packed host;
+    uint8_t* d_stream = nullptr;      // device copies, made by snerf_model_finalize of the programs the model launches
+    float* d_table = nullptr;         // bias table (bf16 programs) / scale, bias and raw-coordinate tables (int8 digits)
+};
 
 struct snerf_model {
     int W = 0, C = 0;
@@ -40,31 +75,40 @@ struct snerf_model {
     snerf_i8_estimate estimate{};
     Weights w;
     bool finalized = false;
-    Packed host[2];
-    Packed host_i8;                  // field program in the int8-digit format (precision SNERF_PREC_I8X3 only)
-    Packed host_k64;                 // ... its digits in the layout of v_mfma_i32_16x16x64_i8 (program.h "k64": what kernels_i8x2.hip runs at W = 256)
-    Packed host_ks;                  // field program in the K-split order of kernels_ks.hip (W = 512 under SNERF_PREC_BF16X3)
-    Packed host_ksg;                 // per-ray (group) program in the same order: W = 512 under every precision (round 6; exact fp32 layer by layer before)
+    ProgramSlot prog[P_NUM];
     // Widths without a bf16 group kernel (512): the per-ray networks (time -> class softmax, sun -> sky colour: one row per ray,
     // 1/S of the field network's work) run layer by layer in exact fp32 (v_mfma_f32_32x32x2_f32, csrc/gemm.hip) - their error is
     // not averaged over a ray's samples, so they get the full precision.  Device copy of the five layers' fp32 weights:
     float* d_group_f32 = nullptr;
     size_t g32_off[10] = {0};        // weight / bias offsets (floats) of time_layer_1, time_layer_2, get_class_layer, fc_sky_color_1, fc_sky_color_2
-    uint8_t* d_stream[2] = {nullptr, nullptr};
-    float* d_bias[2] = {nullptr, nullptr};
-    uint8_t* d_stream_i8 = nullptr;
-    float* d_table_i8 = nullptr;
-    uint8_t* d_stream_k64 = nullptr;
-    float* d_table_k64 = nullptr;
-    uint8_t* d_stream_ks = nullptr;
-    float* d_bias_ks = nullptr;
-    uint8_t* d_stream_ksg = nullptr;
-    float* d_bias_ksg = nullptr;
     // sun walk: device copy of the walk stream (program.h sun_walk_*) of the most recent n_suns, built at the first snerf_field_sun_walk_rays that asks for it
     mutable uint8_t* d_walk = nullptr;
     mutable int walk_suns = 0;
     int n_cu = 0;
 };
+
+static void release(ProgramSlot& s) {
+    if (s.d_stream) (void)hipFree(s.d_stream);
+    if (s.d_table) (void)hipFree(s.d_table);
+    s.d_stream = nullptr;
+    s.d_table = nullptr;
+}
+// device copy of a packed program; one that an earlier, failed snerf_model_finalize left stays, a failure here leaves none behind
+static int upload(ProgramSlot& s) {
+    if (s.d_stream) return SNERF_OK;
+    const size_t stream_bytes = s.host.stream.size(), table_bytes = s.host.bias.size() * 4;
+    const char* what = "hipMalloc";
+    hipError_t e = hipMalloc((void**)&s.d_stream, stream_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&s.d_table, table_bytes);
+    if (e == hipSuccess) {
+        what = "hipMemcpy";
+        e = hipMemcpy(s.d_stream, s.host.stream.data(), stream_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(s.d_table, s.host.bias.data(), table_bytes, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) return SNERF_OK;
+    release(s);
+    return fail_hip(e, what);
+}
 
 struct snerf_loader {
     const float* d_table = nullptr;
@@ -120,8 +164,7 @@ static int i8_estimate(snerf_model* m, snerf_i8_estimate* out) {
     if (m->have_estimate) { *out = m->estimate; return SNERF_OK; }
     I8Estimate e;
     std::string err;
-    if (!estimate_i8(m->w, m->W, m->C, &e, &err))
-        return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
+    if (!estimate_i8(m->w, m->W, m->C, &e, &err)) return fail_pack(err);
     for (int i = 0; i < 4; ++i) out->head_rms[i] = e.head_rms[i];
     out->hidden_rms = e.hidden_rms;
     out->worst = e.worst;
@@ -152,6 +195,21 @@ int snerf_model_set_tensor(snerf_model* m, const char* key, const float* host_da
 static bool bf16_width(int W) { return W == 64 || W == 256; }     // widths the bf16 kernels (kernels.hip) are instantiated for
 static bool ks_width(int W) { return W == 512; }                  // ... the K-split bf16x3 field kernel (kernels_ks.hip): the reference's default width
 
+// Which programs a model of this width and (resolved) precision holds.  Without `want_bf16_field`: the ones it launches, which snerf_model_finalize uploads.
+// With it (snerf_model_pack_host, the sun walk's stream): also the bf16 field program where the model itself runs int8 digits.
+static bool program_needed(const snerf_model* m, int p, bool want_bf16_field) {
+    const bool i8 = m->precision == SNERF_PREC_I8X3;
+    switch (p) {
+        case P_FIELD: return bf16_width(m->W) && (!i8 || want_bf16_field);
+        case P_GROUP: return bf16_width(m->W);
+        case P_I8: return i8;
+        case P_KS: return ks_width(m->W) && (m->precision == SNERF_PREC_BF16X3 || want_bf16_field);
+        case P_KSG: return ks_width(m->W);      // bf16x3 on the wave-pair structure, whatever the field's mode
+        case P_K64: return i8 && i8x2_k64_built(m->W, 0);      // the two-wave kernel's instances on the 16x16x64 shape read their own stream
+    }
+    return false;
+}
+
 static int pack_both(snerf_model* m, bool want_bf16_field = false) {
     if (!m->resolved) {          // SNERF_PREC_AUTO: int8 digits where their error bound holds for these weights
         snerf_i8_estimate e;
@@ -170,47 +228,23 @@ static int pack_both(snerf_model* m, bool want_bf16_field = false) {
     }
     if (!bf16_width(m->W) && m->precision != SNERF_PREC_I8X3 && !(ks_width(m->W) && m->precision == SNERF_PREC_BF16X3))
         return fail(SNERF_E_INVALID, "layer_width " + std::to_string(m->W) + " has fused kernels only under SNERF_PREC_I8X3 and SNERF_PREC_BF16X3");
-    if (ks_width(m->W) && (m->precision == SNERF_PREC_BF16X3 || want_bf16_field) && (m->host_ks.stream.empty() || (want_bf16_field && m->host[PROG_FIELD].stream.empty()))) {
+    static const int order[P_NUM] = {P_KS, P_KSG, P_FIELD, P_GROUP, P_I8, P_K64};      // decides which error a model with several defects reports
+    for (int p : order) {
+        if (!program_needed(m, p, want_bf16_field)) continue;
+        // the K-split programs are permutations of a canonical one, which stays on the host where snerf_model_pack_host can ask for it: the per-ray
+        // networks always, the field network (11 MB) on request
+        const int canon = p == P_KS ? P_FIELD : p == P_KSG ? P_GROUP : -1;
+        const bool keep_canon = canon == P_GROUP || (canon == P_FIELD && want_bf16_field);
+        if (!m->prog[p].host.stream.empty() && !(keep_canon && m->prog[canon].host.stream.empty())) continue;
         std::string err;
-        Packed tmp, ks;
-        if (!pack_program(m->w, PROG_FIELD, m->W, m->C, /*fold_bn=*/true, &tmp, &err) || !permute_program_ks(tmp, m->W, m->C, &ks, &err))
-            return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
-        m->host_ks = std::move(ks);
-        if (want_bf16_field) m->host[PROG_FIELD] = std::move(tmp);      // the canonical order, on request only (snerf_model_pack_host)
-    }
-    if (ks_width(m->W) && m->host_ksg.stream.empty()) {            // the per-ray networks of width 512: bf16x3 on the wave-pair structure, whatever the field's mode
-        std::string err;
-        Packed tmp, ks;
-        if (!pack_program(m->w, PROG_GROUP, m->W, m->C, /*fold_bn=*/true, &tmp, &err) || !permute_program_ks(tmp, m->W, m->C, &ks, &err, PROG_GROUP))
-            return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
-        m->host_ksg = std::move(ks);
-        m->host[PROG_GROUP] = std::move(tmp);                         // the canonical order, for snerf_model_pack_host
-    }
-    for (int p = 0; p < 2; ++p) {
-        if (!bf16_width(m->W)) break;
-        if (!m->host[p].stream.empty()) continue;
-        // under int8 digits the bf16 form of the FIELD program is never launched: packed only on request (snerf_model_pack_host)
-        if (p == PROG_FIELD && m->precision == SNERF_PREC_I8X3 && !want_bf16_field) continue;
-        std::string err;
-        Packed tmp;
-        if (!pack_program(m->w, p, m->W, m->C, /*fold_bn=*/true, &tmp, &err))
-            return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
-        m->host[p] = std::move(tmp);
-    }
-    if (m->precision == SNERF_PREC_I8X3 && m->host_i8.stream.empty()) {
-        std::string err;
-        Packed tmp;
-        if (!pack_program_i8(m->w, PROG_FIELD, m->W, m->C, /*fold_bn=*/true, &tmp, &err))
-            return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
-        m->host_i8 = std::move(tmp);
-    }
-    // the two-wave kernel's instances on the 16x16x64 shape read their own stream; every other int8 kernel keeps the one above
-    if (m->precision == SNERF_PREC_I8X3 && i8x2_k64_built(m->W, 0) && m->host_k64.stream.empty()) {
-        std::string err;
-        Packed tmp;
-        if (!pack_program_k64(m->w, m->W, m->C, /*fold_bn=*/true, &tmp, &err))
-            return fail(err.rfind("missing", 0) == 0 ? SNERF_E_MISSING : SNERF_E_INVALID, err);
-        m->host_k64 = std::move(tmp);
+        Packed out, tmp;
+        const bool ok = canon >= 0 ? pack_program(m->w, canon, m->W, m->C, /*fold_bn=*/true, &tmp, &err) && permute_program_ks(tmp, m->W, m->C, &out, &err, canon)
+                      : p == P_I8  ? pack_program_i8(m->w, PROG_FIELD, m->W, m->C, /*fold_bn=*/true, &out, &err)
+                      : p == P_K64 ? pack_program_k64(m->w, m->W, m->C, /*fold_bn=*/true, &out, &err)
+                                   : pack_program(m->w, p, m->W, m->C, /*fold_bn=*/true, &out, &err);
+        if (!ok) return fail_pack(err);
+        m->prog[p].host = std::move(out);
+        if (keep_canon) m->prog[canon].host = std::move(tmp);
     }
     return SNERF_OK;
 }
@@ -230,9 +264,9 @@ int snerf_model_pack_host(snerf_model* m, int program, uint8_t* stream_out, size
         return fail(SNERF_E_STATE, "program 2 (int8-digit field network) exists only under SNERF_PREC_I8X3");
     if (program == 3 && !ks_width(m->W)) return fail(SNERF_E_STATE, "program 3 (K-split bf16 field network) exists only at width 512");
     if (program == 4 && !ks_width(m->W)) return fail(SNERF_E_STATE, "program 4 (K-split per-ray networks) exists only at width 512");
-    int rc = pack_both(m, program == PROG_FIELD || program == 3);
+    int rc = pack_both(m, program == P_FIELD || program == P_KS);
     if (rc) return rc;
-    const Packed& P = program == 5 ? m->host_k64 : program == 4 ? m->host_ksg : program == 3 ? m->host_ks : program == 2 ? m->host_i8 : m->host[program];
+    const Packed& P = m->prog[program].host;
     if (stream_bytes) *stream_bytes = P.stream.size();
     if (bias_floats) *bias_floats = P.bias.size();
     if (stream_out) std::memcpy(stream_out, P.stream.data(), P.stream.size());
@@ -254,46 +288,8 @@ int snerf_model_finalize(snerf_model* m) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(SNERF_E_HIP, std::string("this library is built for gfx950 only, device is ") + prop.gcnArchName);
     m->n_cu = prop.multiProcessorCount;
-    if (m->precision == SNERF_PREC_BF16X3 && ks_width(m->W)) {
-        const Packed& P = m->host_ks;
-        if ((e = hipMalloc((void**)&m->d_stream_ks, P.stream.size())) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&m->d_bias_ks, P.bias.size() * 4)) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMemcpy(m->d_stream_ks, P.stream.data(), P.stream.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
-        if ((e = hipMemcpy(m->d_bias_ks, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
-    }
-    if (ks_width(m->W)) {
-        const Packed& P = m->host_ksg;
-        if ((e = hipMalloc((void**)&m->d_stream_ksg, P.stream.size())) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&m->d_bias_ksg, P.bias.size() * 4)) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMemcpy(m->d_stream_ksg, P.stream.data(), P.stream.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
-        if ((e = hipMemcpy(m->d_bias_ksg, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
-    }
-    for (int p = 0; p < 2; ++p) {
-        const Packed& P = m->host[p];
-        if (P.stream.empty() || !bf16_width(m->W)) continue;
-        if ((e = hipMalloc((void**)&m->d_stream[p], P.stream.size())) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&m->d_bias[p], P.bias.size() * 4)) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMemcpy(m->d_stream[p], P.stream.data(), P.stream.size(), hipMemcpyHostToDevice)) != hipSuccess)
-            return fail_hip(e, "hipMemcpy");
-        if ((e = hipMemcpy(m->d_bias[p], P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-            return fail_hip(e, "hipMemcpy");
-    }
-    if (m->precision == SNERF_PREC_I8X3) {
-        const Packed& P = m->host_i8;
-        if ((e = hipMalloc((void**)&m->d_stream_i8, P.stream.size())) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&m->d_table_i8, P.bias.size() * 4)) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMemcpy(m->d_stream_i8, P.stream.data(), P.stream.size(), hipMemcpyHostToDevice)) != hipSuccess)
-            return fail_hip(e, "hipMemcpy");
-        if ((e = hipMemcpy(m->d_table_i8, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-            return fail_hip(e, "hipMemcpy");
-    }
-    if (m->precision == SNERF_PREC_I8X3 && !m->host_k64.stream.empty()) {
-        const Packed& P = m->host_k64;
-        if ((e = hipMalloc((void**)&m->d_stream_k64, P.stream.size())) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&m->d_table_k64, P.bias.size() * 4)) != hipSuccess) return fail_hip(e, "hipMalloc");
-        if ((e = hipMemcpy(m->d_stream_k64, P.stream.data(), P.stream.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
-        if ((e = hipMemcpy(m->d_table_k64, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
-    }
+    for (int p = 0; p < P_NUM; ++p)      // the programs this model launches (a bf16 field program packed on request under int8 digits stays on the host)
+        if (program_needed(m, p, false) && (rc = upload(m->prog[p])) != SNERF_OK) return rc;
     if (!bf16_width(m->W)) {      // fp32 weights of the per-ray networks
         static const char* keys[5] = {"time_layer_1.linear", "time_layer_2.linear", "get_class_layer", "G_NeRF_net.fc_sky_color_1.linear",
                                       "G_NeRF_net.fc_sky_color_2"};
@@ -322,18 +318,7 @@ int snerf_model_finalize(snerf_model* m) {
 
 void snerf_model_destroy(snerf_model* m) {
     if (!m) return;
-    for (int p = 0; p < 2; ++p) {
-        if (m->d_stream[p]) (void)hipFree(m->d_stream[p]);
-        if (m->d_bias[p]) (void)hipFree(m->d_bias[p]);
-    }
-    if (m->d_stream_i8) (void)hipFree(m->d_stream_i8);
-    if (m->d_table_i8) (void)hipFree(m->d_table_i8);
-    if (m->d_stream_k64) (void)hipFree(m->d_stream_k64);
-    if (m->d_table_k64) (void)hipFree(m->d_table_k64);
-    if (m->d_stream_ks) (void)hipFree(m->d_stream_ks);
-    if (m->d_bias_ks) (void)hipFree(m->d_bias_ks);
-    if (m->d_stream_ksg) (void)hipFree(m->d_stream_ksg);
-    if (m->d_bias_ksg) (void)hipFree(m->d_bias_ksg);
+    for (ProgramSlot& s : m->prog) release(s);
     if (m->d_group_f32) (void)hipFree(m->d_group_f32);
     if (m->d_walk) (void)hipFree(m->d_walk);
     delete m;
@@ -345,6 +330,14 @@ int snerf_model_classes(const snerf_model* m) { return m ? m->C : 0; }
 static int check_ready(const snerf_model* m) {
     if (!m) return fail(SNERF_E_INVALID, "NULL model");
     if (!m->finalized) return fail(SNERF_E_STATE, "model not finalized (call snerf_model_finalize)");
+    return SNERF_OK;
+}
+// ... for the walk kernels, which exist for the bf16x3 field program only; `what`: "<the kernels> exist", as the message of entry point `fn` names them
+static int check_walk_model(const snerf_model* m, const char* fn, const char* what) {
+    int rc = check_ready(m);
+    if (rc) return rc;
+    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
+        return fail(SNERF_E_INVALID, std::string(fn) + ": the " + what + " for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
     return SNERF_OK;
 }
 
@@ -391,9 +384,76 @@ static int group_forward_f32(const snerf_model* m, int64_t R, const float* d_tim
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "hipFreeAsync");
 }
 
+// ---- what a launch reads: one place decides the stream, its tables and the kernel
+static void set_program(MlpArgs& a, const ProgramSlot& s, size_t stream_bytes) {      // stream_bytes: the part of the stream a tile cycles over
+    a.stream = s.d_stream;
+    a.stream_bytes = (uint32_t)stream_bytes;
+    a.bias = s.d_table;
+    a.bias_floats = (int)s.host.bias.size();
+}
+static snerf_field_out_dev to_dev(const snerf_field_out* out) {
+    return {out->d_rho, out->d_solar_vis, out->d_col_raw, out->d_adjust, out->d_col, out->d_adjust_col, out->d_points, nullptr};
+}
+// the ray part of the arguments: n points or rays, each group_size of them sharing a sun / classes row
+static MlpArgs ray_args(const snerf_model* m, int64_t n, const float* d_top, const float* d_bot, const float* d_tvals, int n_samples, int64_t group_size,
+                        int ray_flags) {
+    MlpArgs a{};
+    a.n = n;
+    a.n_classes = m->C;
+    a.top = d_top;
+    a.bot = d_bot;
+    a.tvals = d_tvals;
+    a.n_samples = n_samples;
+    a.group_size = group_size;
+    a.ray_flags = ray_flags;
+    return a;
+}
+
+// the field program in bf16 pairs, in the order this width's kernels read it (the sun walk's stream is cut from its host copy under every precision)
+static const ProgramSlot& bf16_field(const snerf_model* m) { return m->prog[ks_width(m->W) ? P_KS : P_FIELD]; }
+
+enum FieldKernel { K_BF16, K_KS, K_I8, K_I8X2 };      // kernels.hip (bf16x3 and the bf16 fast mode), kernels_ks.hip, kernels_i8.hip, kernels_i8x2.hip
+struct FieldRoute {
+    FieldKernel kernel;
+    const ProgramSlot* slot;
+    int chunks;                            // chunks per tile: the layers of the variant
+    int k64;                               // the slot is P_K64
+    int tile_points, block, lds_bytes;     // what snerf_field_kernel_info reports
+};
+// Which kernel and which program a field launch of this model gets.  Works on an un-finalized model whose programs are packed; the walk kernels
+// (bf16x3 models only) take slot and chunks from here too.
+static FieldRoute field_route(const snerf_model* m, int variant) {
+    const int W = m->W, C = m->C;
+    FieldRoute r{};
+    if (m->precision == SNERF_PREC_I8X3) {
+        // two waves per SIMD wherever the activations leave room for it; their instances built on v_mfma_i32_16x16x64_i8 (W = 256) read the k64 stream
+        const bool two_waves = W <= 256 && !switches().i8_one_wave;
+        r.kernel = two_waves ? K_I8X2 : K_I8;
+        r.k64 = two_waves && !switches().i8x2_mfma32 && !m->prog[P_K64].host.stream.empty() && i8x2_k64_built(W, variant);
+        r.slot = &m->prog[r.k64 ? P_K64 : P_I8];
+        r.chunks = r.k64 ? k64_chunk_start(W, C, field_variant_layers(variant)) : field_variant_chunks_i8(W, C, variant);
+        r.tile_points = two_waves ? 256 : mlp_tile_points();
+        r.block = two_waves ? 512 : 256;
+        r.lds_bytes = (W > 256 ? 5 : 7) * kChunkBytes + (int)r.slot->host.bias.size() * 4 + kVoteBytes;
+        return r;
+    }
+    const bool ks = ks_width(W);      // 64 points per tile (two wave pairs)
+    r.kernel = ks ? K_KS : K_BF16;
+    r.slot = &bf16_field(m);
+    r.chunks = ks ? field_variant_chunks_ks(W, C, variant) : field_variant_chunks(W, C, variant);
+    r.tile_points = ks ? mlp_ks_tile_points() : mlp_tile_points();
+    r.block = 256;
+    r.lds_bytes = ks ? mlp_ks_lds_bytes((int)r.slot->host.bias.size()) : mlp_lds_bytes((int)r.slot->host.bias.size());
+    return r;
+}
+static void set_program(MlpArgs& a, const FieldRoute& r) {
+    set_program(a, *r.slot, (size_t)r.chunks * kChunkBytes);
+    a.k64 = r.k64;
+}
+
 // 0: kernels_group.hip (output blocks split over the waves), 1: kernels.hip (one wave per 32 rays); SNERF_GROUP_ONE_WAVE=1: start at 1 (A/B)
 static std::atomic<int>& group_kernel_mode() {
-    static std::atomic<int> mode{getenv("SNERF_GROUP_ONE_WAVE") != nullptr ? 1 : 0};
+    static std::atomic<int> mode{switches().group_one_wave ? 1 : 0};
     return mode;
 }
 int snerf_set_group_kernel(int mode) {
@@ -409,14 +469,11 @@ int snerf_group_forward(const snerf_model* m, int64_t n_groups, const float* d_t
     if (n_groups == 0) return SNERF_OK;
     if (n_groups < 0 || !d_time || !d_sun) return fail(SNERF_E_INVALID, "snerf_group_forward: bad argument");
     // width 512: the wave-pair kernel (bf16x3, as the per-ray networks of the other widths); SNERF_GROUP_F32=1: the exact-fp32 layer-wise form of rounds 3-5 (A/B)
-    static const bool group_f32 = getenv("SNERF_GROUP_F32") != nullptr;
-    if (m->d_group_f32 && (group_f32 || !m->d_stream_ksg)) return group_forward_f32(m, n_groups, d_time, d_sun, d_classes, d_sky_raw, d_sky, (hipStream_t)stream);
-    MlpArgs a{};
     const bool ks = ks_width(m->W);
-    a.stream = ks ? m->d_stream_ksg : m->d_stream[PROG_GROUP];
-    a.stream_bytes = ks ? (uint32_t)group_chunks_ks(m->W, m->C) * kChunkBytes : (uint32_t)m->host[PROG_GROUP].stream.size();
-    a.bias = ks ? m->d_bias_ksg : m->d_bias[PROG_GROUP];
-    a.bias_floats = (int)m->host[PROG_GROUP].bias.size();
+    const ProgramSlot& s = m->prog[ks ? P_KSG : P_GROUP];
+    if (m->d_group_f32 && (switches().group_f32 || !s.d_stream)) return group_forward_f32(m, n_groups, d_time, d_sun, d_classes, d_sky_raw, d_sky, (hipStream_t)stream);
+    MlpArgs a{};
+    set_program(a, s, ks ? (size_t)group_chunks_ks(m->W, m->C) * kChunkBytes : s.host.stream.size());
     a.n = n_groups;
     a.n_classes = m->C;
     a.group_size = 1;
@@ -436,49 +493,19 @@ static int field_launch(const snerf_model* m, int variant, MlpArgs& a, const sne
     if (variant < 0 || variant > 3 || (variant == 3 && !(a.out.vis && a.top && a.bot && a.tvals && !a.points)))
         return fail(SNERF_E_INVALID, "variant must be 0, 1 or 2 (3, ray visibility, only through snerf_field_ray_visibility)");
     if (variant == 3 && m->precision == SNERF_PREC_BF16) return fail(SNERF_E_INVALID, "ray visibility: not available in the bf16 fast mode");
-    a.stream = m->d_stream[PROG_FIELD];
-    a.stream_bytes = (uint32_t)field_variant_chunks(m->W, m->C, variant) * kChunkBytes;
-    a.bias = m->d_bias[PROG_FIELD];
-    a.bias_floats = (int)m->host[PROG_FIELD].bias.size();
+    const FieldRoute r = field_route(m, variant);
+    set_program(a, r);
     a.n_classes = m->C;
 #ifdef SNERF_ABLATE
     if (const char* e = getenv("SNERF_ABLATE")) a.debug = (uint32_t)atoi(e);
 #endif
-    if (out) {
-        a.out.rho = out->d_rho; a.out.solar_vis = out->d_solar_vis; a.out.col_raw = out->d_col_raw;
-        a.out.adjust = out->d_adjust; a.out.col = out->d_col; a.out.adjust_col = out->d_adjust_col;
-        a.out.points = out->d_points;
-    }
+    if (out) a.out = to_dev(out);      // (variant 3 comes without: its a.out.vis stays)
     if (variant <= 1 && !a.sun) return fail(SNERF_E_INVALID, "sun directions are required for variants 0 and 1");
-    hipError_t e;
-    if (m->precision == SNERF_PREC_I8X3) {
-        a.stream = m->d_stream_i8;
-        a.stream_bytes = (uint32_t)field_variant_chunks_i8(m->W, m->C, variant) * kChunkBytes;
-        a.bias = m->d_table_i8;
-        a.bias_floats = (int)m->host_i8.bias.size();
-        // two waves per SIMD wherever the activations leave room for it (kernels_i8x2.hip); SNERF_I8_ONE_WAVE=1: A/B switch
-        static const bool one_wave = getenv("SNERF_I8_ONE_WAVE") != nullptr;
-        // the two-wave kernel's instances built on v_mfma_i32_16x16x64_i8 (W = 256) read the k64 stream; SNERF_I8X2_MFMA32=1: their 32x32x32 code (A/B)
-        static const bool mfma32 = getenv("SNERF_I8X2_MFMA32") != nullptr;
-        if (m->W <= 256 && !one_wave) {
-            if (!mfma32 && m->d_stream_k64 && i8x2_k64_built(m->W, variant)) {
-                a.stream = m->d_stream_k64;
-                a.stream_bytes = (uint32_t)k64_chunk_start(m->W, m->C, field_variant_layers(variant)) * kChunkBytes;
-                a.bias = m->d_table_k64;
-                a.bias_floats = (int)m->host_k64.bias.size();
-                a.k64 = 1;
-            }
-            e = launch_mlp_i8x2(m->W, variant, a, m->n_cu, (hipStream_t)stream);
-        } else e = launch_mlp_i8(m->W, variant, a, m->n_cu, (hipStream_t)stream);
-    } else if (ks_width(m->W)) {
-        a.stream = m->d_stream_ks;
-        a.stream_bytes = (uint32_t)field_variant_chunks_ks(m->W, m->C, variant) * kChunkBytes;
-        a.bias = m->d_bias_ks;
-        a.bias_floats = (int)m->host_ks.bias.size();
-        e = launch_mlp_ks(m->W, variant, a, m->n_cu, (hipStream_t)stream);
-    } else {
-        e = launch_mlp(PROG_FIELD, m->W, variant, m->precision == SNERF_PREC_BF16, a, m->n_cu, (hipStream_t)stream);
-    }
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = r.kernel == K_I8X2 ? launch_mlp_i8x2(m->W, variant, a, m->n_cu, st)
+                       : r.kernel == K_I8   ? launch_mlp_i8(m->W, variant, a, m->n_cu, st)
+                       : r.kernel == K_KS   ? launch_mlp_ks(m->W, variant, a, m->n_cu, st)
+                                            : launch_mlp(PROG_FIELD, m->W, variant, m->precision == SNERF_PREC_BF16, a, m->n_cu, st);
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "field kernel launch");
 }
 
@@ -489,11 +516,8 @@ int snerf_field_forward_points(const snerf_model* m, int variant, int64_t n_poin
     if (rc) return rc;
     if (n_points == 0) return SNERF_OK;
     if (n_points < 0 || !d_points || group_size < 1) return fail(SNERF_E_INVALID, "snerf_field_forward_points: bad argument");
-    MlpArgs a{};
-    a.n = n_points;
+    MlpArgs a = ray_args(m, n_points, nullptr, nullptr, nullptr, 1, group_size, 0);
     a.points = d_points;
-    a.n_samples = 1;
-    a.group_size = group_size;
     a.sun = d_sun;
     a.classes = d_classes;
     return field_launch(m, variant, a, out, stream);
@@ -507,13 +531,7 @@ int snerf_field_forward_rays(const snerf_model* m, int variant, int64_t n_rays, 
     if (n_rays == 0) return SNERF_OK;
     if (n_rays < 0 || n_samples < 1 || rays_per_group < 1 || !d_top || !d_bot || !d_tvals)
         return fail(SNERF_E_INVALID, "snerf_field_forward_rays: bad argument");
-    MlpArgs a{};
-    a.n = n_rays * n_samples;
-    a.top = d_top;
-    a.bot = d_bot;
-    a.tvals = d_tvals;
-    a.n_samples = n_samples;
-    a.group_size = (int64_t)n_samples * rays_per_group;
+    MlpArgs a = ray_args(m, n_rays * n_samples, d_top, d_bot, d_tvals, n_samples, (int64_t)n_samples * rays_per_group, 0);
     a.sun = d_sun;
     a.classes = d_classes;
     return field_launch(m, variant, a, out, stream);
@@ -525,7 +543,7 @@ int snerf_model_pack_sun_walk_host(snerf_model* m, int n_suns, uint8_t* stream_o
     int rc = pack_both(m, true);
     if (rc) return rc;
     const bool ks = ks_width(m->W);
-    const Packed& P = ks ? m->host_ks : m->host[PROG_FIELD];
+    const Packed& P = bf16_field(m).host;
     const int chunks = sun_walk_chunks(m->W, m->C, n_suns, ks);
     if (P.stream.size() != (size_t)field_chunk_start(m->W, m->C, F_NUM, ks) * kChunkBytes) return fail(SNERF_E_STATE, "snerf_model_pack_sun_walk_host: packed stream has an unexpected size");
     if (stream_bytes) *stream_bytes = (size_t)chunks * kChunkBytes;
@@ -540,7 +558,8 @@ int snerf_model_pack_sun_walk_host(snerf_model* m, int n_suns, uint8_t* stream_o
 static int walk_stream(const snerf_model* m, int n_suns) {
     if (m->d_walk && m->walk_suns == n_suns) return SNERF_OK;
     const bool ks = ks_width(m->W);
-    const uint8_t* src = (ks ? m->host_ks : m->host[PROG_FIELD]).stream.data();
+    const std::vector<uint8_t>& host = bf16_field(m).host.stream;
+    const uint8_t* src = host.data();
     hipError_t e;
     if (m->d_walk) {                        // another n_suns: hipFree waits for the launches that still read the old copy
         if ((e = hipFree(m->d_walk)) != hipSuccess) return fail_hip(e, "hipFree");
@@ -549,7 +568,7 @@ static int walk_stream(const snerf_model* m, int n_suns) {
     }
     const size_t a = (size_t)field_chunk_start(m->W, m->C, F_S1, ks) * kChunkBytes, b = (size_t)field_chunk_start(m->W, m->C, F_A1, ks) * kChunkBytes,
                  end = (size_t)field_chunk_start(m->W, m->C, F_NUM, ks) * kChunkBytes;
-    if ((ks ? m->host_ks : m->host[PROG_FIELD]).stream.size() != end) return fail(SNERF_E_STATE, "sun walk: the packed field stream has an unexpected size");
+    if (host.size() != end) return fail(SNERF_E_STATE, "sun walk: the packed field stream has an unexpected size");
     if ((e = hipMalloc((void**)&m->d_walk, (size_t)sun_walk_chunks(m->W, m->C, n_suns, ks) * kChunkBytes)) != hipSuccess) return fail_hip(e, "hipMalloc (walk stream)");
     e = hipMemcpy(m->d_walk, src, a, hipMemcpyHostToDevice);
     for (int j = 0; j < n_suns && e == hipSuccess; ++j) e = hipMemcpy(m->d_walk + a + (size_t)j * (b - a), src + a, b - a, hipMemcpyHostToDevice);
@@ -565,36 +584,21 @@ static int walk_stream(const snerf_model* m, int n_suns) {
 
 int snerf_field_sun_walk_rays(const snerf_model* m, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot, const float* d_tvals,
                               int n_suns, const float* d_suns, const float* d_classes, const snerf_field_out* out, void* stream) {
-    int rc = check_ready(m);
+    int rc = check_walk_model(m, "snerf_field_sun_walk_rays", "sun walk exists");
     if (rc) return rc;
-    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
-        return fail(SNERF_E_INVALID, "snerf_field_sun_walk_rays: the sun walk exists for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
     if (n_suns < 1 || n_suns > kMaxWalkSuns) return fail(SNERF_E_INVALID, "snerf_field_sun_walk_rays: n_suns must be in [1," + std::to_string(kMaxWalkSuns) + "]");
     if (n_rays < 0 || n_samples < 1 || !d_top || !d_bot || !d_tvals || !d_suns) return fail(SNERF_E_INVALID, "snerf_field_sun_walk_rays: bad argument");
     if (n_rays == 0) return SNERF_OK;
     rc = walk_stream(m, n_suns);
     if (rc) return rc;
-    const bool ks = ks_width(m->W);
     SunWalkArgs a{};
     a.n_suns = n_suns;
-    a.m.stream = m->d_walk;
-    a.m.stream_bytes = (uint32_t)sun_walk_chunks(m->W, m->C, n_suns, ks) * kChunkBytes;
-    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
-    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
-    a.m.n = n_rays * n_samples;
-    a.m.n_classes = m->C;
-    a.m.top = d_top;
-    a.m.bot = d_bot;
-    a.m.tvals = d_tvals;
-    a.m.n_samples = n_samples;
-    a.m.group_size = a.m.n;
+    a.m = ray_args(m, n_rays * n_samples, d_top, d_bot, d_tvals, n_samples, n_rays * n_samples, 0);
+    set_program(a.m, bf16_field(m), (size_t)sun_walk_chunks(m->W, m->C, n_suns, ks_width(m->W)) * kChunkBytes);
+    a.m.stream = m->d_walk;      // the walk stream in place of the program's own; the bias table is the program's
     a.m.sun = d_suns;
     a.m.classes = d_classes;
-    if (out) {
-        a.m.out.rho = out->d_rho; a.m.out.solar_vis = out->d_solar_vis; a.m.out.col_raw = out->d_col_raw;
-        a.m.out.adjust = out->d_adjust; a.m.out.col = out->d_col; a.m.out.adjust_col = out->d_adjust_col;
-        a.m.out.points = out->d_points;
-    }
+    if (out) a.m.out = to_dev(out);
     hipError_t e = launch_sun_walk(m->W, a, m->n_cu, (hipStream_t)stream);
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "sun walk kernel launch");
 }
@@ -605,16 +609,9 @@ int snerf_field_ray_visibility(const snerf_model* m, int64_t n_rays, int n_sampl
     if (rc) return rc;
     if (n_rays == 0) return SNERF_OK;
     if (n_rays < 0 || n_samples < 1 || !d_top || !d_bot || !d_tvals || !d_vis) return fail(SNERF_E_INVALID, "snerf_field_ray_visibility: bad argument");
-    MlpArgs a{};
-    a.n = n_rays;                  // variant 3: one ray per wave, ceil(S / 32) passes of 32 samples (kernels.h)
-    a.top = d_top;
-    a.bot = d_bot;
-    a.tvals = d_tvals;
-    a.n_samples = n_samples;
-    a.group_size = 1;
-    static const bool no_early_out = getenv("SNERF_RAYVIS_NO_EARLY_OUT") != nullptr;      // A/B switch: walk every pass of every ray (mlp_device.h raysum_saturated)
-    static const bool sun_side_first = getenv("SNERF_RAYVIS_SUN_FIRST") != nullptr;      // A/B switch: the passes in the order before round 6's reversal
-    a.ray_flags = (flags & 2) | (no_early_out ? 4 : 0) | (sun_side_first ? 8 : 0);
+    // variant 3: one ray per wave, ceil(S / 32) passes of 32 samples (kernels.h)
+    MlpArgs a = ray_args(m, n_rays, d_top, d_bot, d_tvals, n_samples, 1,
+                         (flags & 2) | (switches().rayvis_no_early_out ? 4 : 0) | (switches().rayvis_sun_first ? 8 : 0));
     a.out.vis = d_vis;
     return field_launch(m, 3, a, nullptr, stream);
 }
@@ -623,25 +620,13 @@ int snerf_field_ray_surface(const snerf_model* m, int64_t n_rays, int n_samples,
                             int flags, float* d_out, void* stream) {
     if (n_rays < 0 || n_samples < 1 || !d_top || !d_bot || !d_tvals || !d_out || ((uintptr_t)d_out & 15))
         return fail(SNERF_E_INVALID, "snerf_field_ray_surface: bad argument (d_out must be 16-byte aligned)");
-    int rc = check_ready(m);
+    int rc = check_walk_model(m, "snerf_field_ray_surface", "ray-surface kernels exist");
     if (rc) return rc;
-    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
-        return fail(SNERF_E_INVALID, "snerf_field_ray_surface: the ray-surface kernels exist for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
     if (n_rays == 0) return SNERF_OK;
-    const bool ks = ks_width(m->W);
     RaySurfaceArgs a{};
-    a.m.stream = ks ? m->d_stream_ks : m->d_stream[PROG_FIELD];
-    a.m.stream_bytes = (uint32_t)(ks ? field_variant_chunks_ks(m->W, m->C, 3) : field_variant_chunks(m->W, m->C, 3)) * kChunkBytes;
-    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
-    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
-    a.m.n = n_rays;                // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples
-    a.m.n_classes = m->C;
-    a.m.top = d_top;
-    a.m.bot = d_bot;
-    a.m.tvals = d_tvals;
-    a.m.n_samples = n_samples;
-    a.m.group_size = 1;
-    a.m.ray_flags = (flags & 6) | 8;      // bit 3: passes from t = 0 downwards, the order of the prefix
+    // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples; bit 3: passes from t = 0 downwards, the order of the prefix
+    a.m = ray_args(m, n_rays, d_top, d_bot, d_tvals, n_samples, 1, (flags & 6) | 8);
+    set_program(a.m, field_route(m, 3));
     a.out = d_out;
     hipError_t e = launch_ray_surface(m->W, a, m->n_cu, (hipStream_t)stream);
     return e == hipSuccess ? SNERF_OK : fail_hip(e, "ray surface kernel launch");
@@ -651,25 +636,13 @@ int snerf_field_shadow_walk(const snerf_model* m, int64_t n_rays, int n_samples,
                             const float* d_tvals, int flags, float* d_out, void* stream) {
     if (n_rays < 0 || n_samples < 1 || !d_top || !d_bot || !d_sun || !d_tvals || !d_out || ((uintptr_t)d_out & 31))
         return fail(SNERF_E_INVALID, "snerf_field_shadow_walk: bad argument (d_out must be 32-byte aligned)");
-    int rc = check_ready(m);
+    int rc = check_walk_model(m, "snerf_field_shadow_walk", "shadow-walk kernels exist");
     if (rc) return rc;
-    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
-        return fail(SNERF_E_INVALID, "snerf_field_shadow_walk: the shadow-walk kernels exist for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
     if (n_rays == 0) return SNERF_OK;
-    const bool ks = ks_width(m->W);
     ShadowWalkArgs a{};
-    a.m.stream = ks ? m->d_stream_ks : m->d_stream[PROG_FIELD];
-    a.m.stream_bytes = (uint32_t)(ks ? field_variant_chunks_ks(m->W, m->C, 1) : field_variant_chunks(m->W, m->C, 1)) * kChunkBytes;
-    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
-    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
-    a.m.n = n_rays;                // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples, every one of them run
-    a.m.n_classes = m->C;
-    a.m.top = d_top;
-    a.m.bot = d_bot;
-    a.m.tvals = d_tvals;
-    a.m.n_samples = n_samples;
-    a.m.group_size = 1;
-    a.m.ray_flags = (flags & 2) | 8;      // bit 3: passes from t = 0 downwards, the order of the prefix
+    // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples, every one of them run; bit 3: passes from t = 0 downwards, the order of the prefix
+    a.m = ray_args(m, n_rays, d_top, d_bot, d_tvals, n_samples, 1, (flags & 2) | 8);
+    set_program(a.m, field_route(m, 1));
     a.sun = d_sun;
     a.out = d_out;
     hipError_t e = launch_shadow_walk(m->W, a, m->n_cu, (hipStream_t)stream);
@@ -684,25 +657,13 @@ int snerf_field_solar_audit(const snerf_model* m, int64_t n_rays, int n_samples,
         return fail(SNERF_E_INVALID, "snerf_field_solar_audit: the sun direction must be finite with sun_z > 0");
     if (flags & ~6) return fail(SNERF_E_INVALID, "snerf_field_solar_audit: flags has bits other than 2 (outside the cube: delta 0) and 4 (no early-out)");
     if (!m) return fail(SNERF_E_INVALID, "snerf_field_solar_audit: NULL model");
-    int rc = check_ready(m);
+    int rc = check_walk_model(m, "snerf_field_solar_audit", "solar-audit kernels exist");
     if (rc) return rc;
-    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
-        return fail(SNERF_E_INVALID, "snerf_field_solar_audit: the solar-audit kernels exist for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
     if (n_rays == 0) return SNERF_OK;
-    const bool ks = ks_width(m->W);
     SolarAuditArgs a{};
-    a.m.stream = ks ? m->d_stream_ks : m->d_stream[PROG_FIELD];
-    a.m.stream_bytes = (uint32_t)(ks ? field_variant_chunks_ks(m->W, m->C, 3) : field_variant_chunks(m->W, m->C, 3)) * kChunkBytes;
-    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
-    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
-    a.m.n = n_rays;                // primary rays: a workgroup walks the secondary rays of one ray's samples, four (width 512: two) at a time
-    a.m.n_classes = m->C;
-    a.m.top = d_top;
-    a.m.bot = d_bot;
-    a.m.tvals = d_tvals;
-    a.m.n_samples = n_samples;
-    a.m.group_size = 1;
-    a.m.ray_flags = flags & 6;     // bit 3 clear: passes from the point outwards
+    // primary rays: a workgroup walks the secondary rays of one ray's samples, four (width 512: two) at a time; bit 3 clear: passes from the point outwards
+    a.m = ray_args(m, n_rays, d_top, d_bot, d_tvals, n_samples, 1, flags & 6);
+    set_program(a.m, field_route(m, 3));
     for (int k = 0; k < 3; ++k) a.sun[k] = sun3[k];
     a.est_vis = d_est_vis;
     a.ps = d_ps;
@@ -718,25 +679,13 @@ int snerf_field_frame_walk(const snerf_model* m, int64_t n_rays, int n_samples, 
         n_times < 1 || n_times > kMaxFrameTimes || !std::isfinite(delta) || !(delta > 0.f))
         return fail(SNERF_E_INVALID, "snerf_field_frame_walk: bad argument (n_samples >= 2, n_times in [1," + std::to_string(kMaxFrameTimes) +
                                          "], delta finite and positive, d_out 64-byte aligned)");
-    int rc = check_ready(m);
+    int rc = check_walk_model(m, "snerf_field_frame_walk", "frame-walk kernels exist");
     if (rc) return rc;
-    if (m->precision != SNERF_PREC_BF16X3 || !(bf16_width(m->W) || ks_width(m->W)))
-        return fail(SNERF_E_INVALID, "snerf_field_frame_walk: the frame-walk kernels exist for SNERF_PREC_BF16X3 at widths 64, 256 and 512 only");
     if (n_rays == 0) return SNERF_OK;
-    const bool ks = ks_width(m->W);
     FrameWalkArgs a{};
-    a.m.stream = ks ? m->d_stream_ks : m->d_stream[PROG_FIELD];
-    a.m.stream_bytes = (uint32_t)(ks ? field_variant_chunks_ks(m->W, m->C, 0) : field_variant_chunks(m->W, m->C, 0)) * kChunkBytes;
-    a.m.bias = ks ? m->d_bias_ks : m->d_bias[PROG_FIELD];
-    a.m.bias_floats = (int)(ks ? m->host_ks : m->host[PROG_FIELD]).bias.size();
-    a.m.n = n_rays;                // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples
-    a.m.n_classes = m->C;
-    a.m.top = d_top;
-    a.m.bot = d_bot;
-    a.m.tvals = d_tvals;
-    a.m.n_samples = n_samples;
-    a.m.group_size = 1;
-    a.m.ray_flags = (flags & 6) | 8;      // bit 3: passes from t = 0 downwards, the order of the prefix
+    // one ray per wave (wave pair at width 512), ceil(S / 32) passes of 32 samples; bit 3: passes from t = 0 downwards, the order of the prefix
+    a.m = ray_args(m, n_rays, d_top, d_bot, d_tvals, n_samples, 1, (flags & 6) | 8);
+    set_program(a.m, field_route(m, 0));
     a.sun = d_sun;
     a.sky = d_sky;
     a.class_vecs = d_class_vecs;
@@ -796,7 +745,6 @@ int snerf_render_rays(const snerf_model* m, int64_t n_rays, int n_samples, const
         return fail(SNERF_E_INVALID, "snerf_render_rays: bad argument");
     if (workspace_bytes < snerf_render_workspace_bytes(n_rays, n_samples, m->C))
         return fail(SNERF_E_INVALID, "snerf_render_rays: workspace too small");
-    if (n_rays == 0) return SNERF_OK;
     const size_t R = (size_t)n_rays, N = R * (size_t)n_samples;
     char* ws = (char*)d_workspace;
     float* cls = (float*)ws; ws += align256(R * m->C * 4);
@@ -932,22 +880,12 @@ int snerf_field_kernel_info(const snerf_model* m, int64_t n_points, int* grid, i
     if (!m) return fail(SNERF_E_INVALID, "NULL model");
     int rc = pack_both(const_cast<snerf_model*>(m));
     if (rc) return rc;
-    const bool i8 = m->precision == SNERF_PREC_I8X3;
-    static const bool one_wave = getenv("SNERF_I8_ONE_WAVE") != nullptr;         // the A/B switch field_launch honours
-    const bool two_waves = i8 && m->W <= 256 && !one_wave;    // kernels_i8x2.hip: 512 threads, 256 points per tile
-    const bool ks = !i8 && ks_width(m->W);                    // kernels_ks.hip: 64 points per tile (two wave pairs)
-    const int tile = two_waves ? 256 : ks ? mlp_ks_tile_points() : mlp_tile_points();
-    const int64_t tiles = (n_points + tile - 1) / tile;
+    const FieldRoute r = field_route(m, 0);      // what field_launch launches for variant 0
+    const int64_t tiles = (n_points + r.tile_points - 1) / r.tile_points;
     const int ncu = m->n_cu ? m->n_cu : 256;
     if (grid) *grid = (int)(tiles < ncu ? tiles : ncu);
-    if (block) *block = two_waves ? 512 : 256;
-    if (lds_bytes) {
-        static const bool mfma32 = getenv("SNERF_I8X2_MFMA32") != nullptr;      // as field_launch: the tables of the stream the launch gets
-        const bool k64 = two_waves && !mfma32 && !m->host_k64.stream.empty();
-        if (i8) *lds_bytes = (m->W > 256 ? 5 : 7) * kChunkBytes + (int)(k64 ? m->host_k64 : m->host_i8).bias.size() * 4 + kVoteBytes;
-        else if (ks) *lds_bytes = mlp_ks_lds_bytes((int)m->host_ks.bias.size());
-        else *lds_bytes = mlp_lds_bytes((int)m->host[PROG_FIELD].bias.size());
-    }
+    if (block) *block = r.block;
+    if (lds_bytes) *lds_bytes = r.lds_bytes;
     return SNERF_OK;
 }
 

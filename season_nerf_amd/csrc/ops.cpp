@@ -74,6 +74,15 @@ void check_shape(const Tensor& t, const char* name, int64_t rows, int64_t cols) 
     TORCH_CHECK(t.dim() == 2 && (rows < 0 || t.size(0) == rows) && t.size(1) == cols, name, " must be [", rows < 0 ? std::string("N") : std::to_string(rows), ",",
                 cols, "], got ", t.sizes());
 }
+// the rays of an op: top, bot [R,3] and the sample positions tvals [S] with S >= min_samples, all float32 on the device -> (R, S)
+std::pair<int64_t, int64_t> check_rays(const Tensor& top, const Tensor& bot, const Tensor& tvals, int64_t min_samples = 1) {
+    check_shape(top, "top", -1, 3);
+    check_shape(bot, "bot", top.size(0), 3);
+    check_dev_f32(tvals, "tvals");
+    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= min_samples, min_samples > 1 ? "tvals must be [S] with S >= " : "tvals must be [S]",
+                min_samples > 1 ? std::to_string(min_samples) : std::string());
+    return {top.size(0), tvals.numel()};
+}
 void* cur_stream(const Tensor& t) { return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
 
 struct Model : torch::CustomClassHolder {
@@ -158,27 +167,19 @@ std::vector<Tensor> points_fwd(const ModelPtr& M, const Tensor& x, const c10::op
 
 // exact solar visibility of secondary rays (Eval_Tools_2.py:255-271, mg_Img_Eval.py:57-70): one launch, one float per ray
 Tensor ray_visibility(const ModelPtr& M, const Tensor& top, const Tensor& bot, const Tensor& tvals, int64_t flags) {
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
-    TORCH_CHECK(tvals.is_cuda() && tvals.scalar_type() == at::kFloat && tvals.is_contiguous(), "tvals must be a contiguous float32 device tensor");
+    const auto [R, S] = check_rays(top, bot, tvals);
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     Tensor vis = at::empty({R}, top.options());
-    ck(snerf_field_ray_visibility(M->m, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(tvals), (int)flags, mptr(vis), cur_stream(top)), "ray_visibility");
+    ck(snerf_field_ray_visibility(M->m, R, (int)S, fptr(top), fptr(bot), fptr(tvals), (int)flags, mptr(vis), cur_stream(top)), "ray_visibility");
     return vis;
 }
 
 std::tuple<Tensor, Tensor, Tensor, std::vector<Tensor>> render_fwd(const ModelPtr& M, const Tensor& top, const Tensor& bot, const Tensor& sun,
                                                                    const Tensor& time, const Tensor& tvals, int64_t flags, bool want_per_sample, bool want_unmixed) {
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
+    const auto [R, S] = check_rays(top, bot, tvals);
     check_shape(sun, "sun", R, 3);
     check_shape(time, "time", R, 4);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
-    const int64_t S = tvals.numel(), C = M->classes();
+    const int64_t C = M->classes();
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     auto o = top.options();
     Tensor rgb = at::empty({R, 3}, o), depth = at::empty({R, 2}, o), albedo = at::empty({R, 3}, o);
@@ -268,13 +269,9 @@ std::vector<Tensor> composite_sweep(const Tensor& top, const Tensor& bot, const 
 std::vector<Tensor> sun_walk_fwd(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, const Tensor& suns, const c10::optional<Tensor>& classes) {
     TORCH_CHECK(model != 0, "season_nerf::sun_walk_fwd: NULL model handle");
     const snerf_model* m = (const snerf_model*)model;
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    const auto [R, S] = check_rays(top, bot, tvals);
     check_shape(suns, "suns", -1, 3);
-    const int64_t S = tvals.numel(), M = suns.size(0), C = snerf_model_classes(m);
+    const int64_t M = suns.size(0), C = snerf_model_classes(m);
     TORCH_CHECK(M >= 1 && M <= 32, "suns must hold 1 to 32 directions per launch, got ", M);
     if (classes.has_value()) { check_dev_f32(*classes, "classes"); TORCH_CHECK(classes->numel() == C, "classes must hold ", C, " values, got ", classes->sizes()); }
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
@@ -291,16 +288,12 @@ std::vector<Tensor> sun_walk_fwd(int64_t model, const Tensor& top, const Tensor&
 // integer, as in sun_walk_fwd, so that the op has a fake kernel.
 Tensor ray_surface(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, int64_t flags) {
     TORCH_CHECK(model != 0, "season_nerf::ray_surface: NULL model handle");
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    const auto [R, S] = check_rays(top, bot, tvals);
     TORCH_CHECK(flags >= 0 && (flags & ~(int64_t)6) == 0, "flags must be a combination of 2 (zero delta outside the cube) and 4 (no early-out), got ", flags);
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     Tensor out = at::empty({R, 4}, top.options());
     if (R == 0) return out;
-    ck(snerf_field_ray_surface((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(tvals), (int)flags, mptr(out), cur_stream(top)), "ray_surface");
+    ck(snerf_field_ray_surface((const snerf_model*)model, R, (int)S, fptr(top), fptr(bot), fptr(tvals), (int)flags, mptr(out), cur_stream(top)), "ray_surface");
     return out;
 }
 
@@ -308,17 +301,13 @@ Tensor ray_surface(int64_t model, const Tensor& top, const Tensor& bot, const Te
 // travels as an integer, as in ray_surface.
 Tensor shadow_walk(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& sun, const Tensor& tvals, int64_t flags) {
     TORCH_CHECK(model != 0, "season_nerf::shadow_walk: NULL model handle");
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
+    const auto [R, S] = check_rays(top, bot, tvals);
     check_shape(sun, "sun", R, 3);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
     TORCH_CHECK(flags == 0 || flags == 2, "flags must be 0 or 2 (zero delta outside the cube), got ", flags);
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     Tensor out = at::empty({R, 8}, top.options());
     if (R == 0) return out;
-    ck(snerf_field_shadow_walk((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(sun), fptr(tvals), (int)flags, mptr(out),
+    ck(snerf_field_shadow_walk((const snerf_model*)model, R, (int)S, fptr(top), fptr(bot), fptr(sun), fptr(tvals), (int)flags, mptr(out),
                                cur_stream(top)), "shadow_walk");
     return out;
 }
@@ -328,12 +317,7 @@ Tensor shadow_walk(int64_t model, const Tensor& top, const Tensor& bot, const Te
 std::tuple<Tensor, Tensor> solar_audit(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, c10::ArrayRef<double> sun, const Tensor& est_vis,
                                        const Tensor& ps, int64_t flags, bool want_exact) {
     TORCH_CHECK(model != 0, "season_nerf::solar_audit: NULL model handle");
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
-    const int64_t S = tvals.numel();
+    const auto [R, S] = check_rays(top, bot, tvals);
     TORCH_CHECK(sun.size() == 3, "sun must hold 3 values, got ", sun.size());
     TORCH_CHECK(std::isfinite(sun[0]) && std::isfinite(sun[1]) && std::isfinite(sun[2]) && sun[2] > 0.0 && (float)sun[2] > 0.f,
                 "sun must be finite with sun_z > 0, got (", sun[0], ", ", sun[1], ", ", sun[2], ")");
@@ -357,11 +341,7 @@ std::tuple<Tensor, Tensor> solar_audit(int64_t model, const Tensor& top, const T
 Tensor frame_walk(int64_t model, const Tensor& top, const Tensor& bot, const Tensor& tvals, double delta, const Tensor& sun, const Tensor& sky,
                   const Tensor& class_vecs, int64_t flags) {
     TORCH_CHECK(model != 0, "season_nerf::frame_walk: NULL model handle");
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 2, "tvals must be [S] with S >= 2");
+    const auto [R, S] = check_rays(top, bot, tvals, 2);
     check_dev_f32(sun, "sun");
     check_dev_f32(sky, "sky");
     TORCH_CHECK(sun.dim() == 1 && sun.numel() == 3 && sky.dim() == 1 && sky.numel() == 3, "sun and sky must be [3]");
@@ -373,7 +353,7 @@ Tensor frame_walk(int64_t model, const Tensor& top, const Tensor& bot, const Ten
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     Tensor out = at::empty({R, 16}, top.options());
     if (R == 0) return out;
-    ck(snerf_field_frame_walk((const snerf_model*)model, R, (int)tvals.numel(), fptr(top), fptr(bot), fptr(tvals), (float)delta, fptr(sun), fptr(sky),
+    ck(snerf_field_frame_walk((const snerf_model*)model, R, (int)S, fptr(top), fptr(bot), fptr(tvals), (float)delta, fptr(sun), fptr(sky),
                               (int)class_vecs.size(0), fptr(class_vecs), (int)flags, mptr(out), cur_stream(top)), "frame_walk");
     return out;
 }
@@ -447,13 +427,10 @@ std::vector<Tensor> train_fwd_image(int64_t trainer, const Tensor& top, const Te
                                     bool train_bn, bool classic, int64_t n_classes, const c10::optional<Tensor>& height_map, double trust,
                                     const c10::optional<Tensor>& trust_dev, at::TensorList /*params*/) {
     snerf_trainer* t = trainer_of(trainer, n_classes);
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3); check_shape(sun, "sun", R, 3); check_shape(time, "time", R, 4);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
+    const auto [R, S] = check_rays(top, bot, tvals);
+    check_shape(sun, "sun", R, 3); check_shape(time, "time", R, 4);
     TORCH_CHECK(n_classes >= 1 && n_classes <= 5, "n_classes must be in [1, 5]");
-    const int64_t S = tvals.numel(), C = n_classes;
+    const int64_t C = n_classes;
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     auto o = top.options();
     auto e = [&](std::initializer_list<int64_t> sz) { return at::empty(sz, o); };
@@ -551,12 +528,8 @@ void train_bwd_points(int64_t trainer, Tensor grads, const c10::optional<Tensor>
 std::vector<Tensor> train_fwd_solar(int64_t trainer, const Tensor& top, const Tensor& bot, const Tensor& tvals, const Tensor& sun, bool train_bn,
                                     at::TensorList /*params*/) {
     snerf_trainer* t = trainer_of(trainer);
-    check_shape(top, "top", -1, 3);
-    const int64_t R = top.size(0);
-    check_shape(bot, "bot", R, 3); check_shape(sun, "sun", R, 3);
-    check_dev_f32(tvals, "tvals");
-    TORCH_CHECK(tvals.dim() == 1 && tvals.numel() >= 1, "tvals must be [S]");
-    const int64_t S = tvals.numel();
+    const auto [R, S] = check_rays(top, bot, tvals);
+    check_shape(sun, "sun", R, 3);
     c10::hip::HIPGuardMasqueradingAsCUDA g(top.device());
     auto o = top.options();
     Tensor sv = at::empty({R, S, 1}, o), pv = at::empty({R, S, 1}, o), pe = at::empty({R, S, 1}, o), sky_raw = at::empty({R, 3}, o), rho = at::empty({R, S, 1}, o),
