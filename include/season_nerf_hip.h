@@ -670,6 +670,49 @@ int snerf_loader_indices_host(int64_t n_rows, uint64_t seed, int64_t epoch, int6
 int snerf_loader_sc_rays_host(uint64_t seed, int64_t draws, int rank, int64_t first, int64_t count, const float* bounds6, float* top, float* bot);
 int snerf_loader_philox_host(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
 
+/* ---- per-step training inputs: what a training step draws besides its batch, on the device - the random sun rays of the solar-correction loss
+ * (create_solor_rays_uniform, Eval_Tools_2.py:72-108), the jitter of both sampling passes (misc.sample_pt_coarse, misc.py:236-241) and one row of a
+ * schedule table (Adam's six scalars, the DSM prior's trust factor, the second optimiser's learning rate).  Same law as the host draws, not the same
+ * numbers: the stream is Philox4x32-10 keyed with the two halves of splitmix64(seed ^ 0x73746570696e7031) - distinct from the loader's sun-check words.
+ *   Counter (index, draws low, draws high, rank + (block << 24)), rank < 2^24.
+ *     block 0, index = ray i:     w0 azimuth, w1 elevation (u = w * 2^-32 in float64: az = u * 360 - 180, el = u * 89 + 1),
+ *                                 w2 / w3 start x / y (u = (w >> 8) * 2^-24 in fp32: 2 * u - 1, product and sum rounded separately), start z = 1
+ *     block 1, index = ray i:     w0 / w1 the two time angles (fp32 u * fp32(2 pi); cos / sin in float64 of that fp32 angle, rounded to fp32)
+ *     block 2, index = sample s:  w0 / w1 jitter of the image / sun-ray pass: tv[s] = base[s] + fp32(1 / n_samples) * u, rounded separately
+ *   vec = the world -> local direction of (el, az) in float64 (mg_unit_converter.py:5-9,59-68,29-34), written as fp32; ends = fp32(float64(starts) - 2 * vec / vec_z).
+ *   Schedule: d_table [n_table_rows, 8] fp32 on the DEVICE (owned by the caller, alive as long as the handle); row `step` (past the end: the last row)
+ *   goes to d_hyper (columns 0..5), d_trust (6), d_lr2 (7).
+ *   State: four int64 in DEVICE memory {draws, step, reserved, reserved}, read by the draw kernel and advanced (+1, +1) by a one-thread kernel behind it:
+ *   two kernel nodes in a hipGraph, a new draw at every replay.  The handle keeps a host shadow advanced per uncaptured launch.
+ * snerf_step_inputs_create: SNERF_E_INVALID - before anything touches the GPU - for NULL pointers, n_rays < 1 or n_samples < 1 (or >= 2^31), rank outside
+ *   [0, 2^24), a non-finite matrix or centre, n_table_rows < 1.  W2L_H (row-major 4x4) and world_center are HOST arrays.
+ * snerf_step_inputs_draw: every output is optional (NULL = skip); the jitter outputs need d_base [n_samples] (linspace(0, 1, S + 1)[:-1]).
+ * snerf_step_inputs_set_state / _get_state: state4 is a HOST array; both synchronise `stream` and are refused while it captures.
+ * snerf_step_inputs_words_host (no GPU): the raw words of draw `draws` on `rank` - ray_words [n_rays, 8] (blocks 0 and 1), sample_words [n_samples, 4]. */
+typedef struct snerf_step_inputs snerf_step_inputs;
+typedef struct snerf_step_inputs_out {
+    float* d_starts;        /* [R,3] */
+    float* d_ends;          /* [R,3] */
+    float* d_vec;           /* [R,3] */
+    float* d_times;         /* [R,4] */
+    const float* d_base;    /* [S] input */
+    float* d_tv_image;      /* [S] */
+    float* d_tv_solar;      /* [S] */
+    float* d_hyper;         /* [6] */
+    float* d_trust;         /* [1] */
+    float* d_lr2;           /* [1] */
+} snerf_step_inputs_out;
+int snerf_step_inputs_create(uint64_t seed, int64_t n_rays, int64_t n_samples, int rank, const double* W2L_H, const double* world_center,
+                             const float* d_table, int64_t n_table_rows, snerf_step_inputs** out);
+void snerf_step_inputs_destroy(snerf_step_inputs* h);
+int64_t snerf_step_inputs_rays(const snerf_step_inputs* h);          /* n_rays, n_samples, n_table_rows of the handle: what the outputs must hold */
+int64_t snerf_step_inputs_samples(const snerf_step_inputs* h);
+int64_t snerf_step_inputs_table_rows(const snerf_step_inputs* h);
+int snerf_step_inputs_draw(snerf_step_inputs* h, const snerf_step_inputs_out* out, void* stream);
+int snerf_step_inputs_get_state(snerf_step_inputs* h, int64_t* state4, void* stream);
+int snerf_step_inputs_set_state(snerf_step_inputs* h, const int64_t* state4, void* stream);
+int snerf_step_inputs_words_host(uint64_t seed, int64_t draws, int rank, int64_t n_rays, int64_t n_samples, uint32_t* ray_words, uint32_t* sample_words);
+
 /* Name and launch geometry of the dominant kernel (for profiling scripts): fills grid/block/lds bytes. */
 int snerf_field_kernel_info(const snerf_model* m, int64_t n_points, int* grid, int* block, int* lds_bytes);
 

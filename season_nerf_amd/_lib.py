@@ -33,6 +33,11 @@ class LoaderOut(C.Structure):
                                           "d_row_index", "d_sc_top", "d_sc_bot")]
 
 
+class StepInputsOut(C.Structure):
+    """snerf_step_inputs_out: the optional outputs of snerf_step_inputs_draw (NULL = skip) and the jitter's base vector."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_starts", "d_ends", "d_vec", "d_times", "d_base", "d_tv_image", "d_tv_solar", "d_hyper", "d_trust", "d_lr2")]
+
+
 class LossIn(C.Structure):
     """snerf_loss_in: what snerf_loss_all_forward / _backward read (NULL = the configuration lacks it)."""
     _fields_ = [("n_rays", C.c_int64), ("n_solar_rays", C.c_int64), ("n_samples", C.c_int), ("flags", C.c_int)] + \
@@ -174,6 +179,15 @@ def lib():
     L.snerf_loader_indices_host.argtypes = [i64, u64, i64, i64, i64, vp]
     L.snerf_loader_sc_rays_host.argtypes = [u64, i64, i32, i64, i64, vp, vp, vp]
     L.snerf_loader_philox_host.argtypes = [vp, vp, vp]
+    L.snerf_step_inputs_create.argtypes = [u64, i64, i64, i32, vp, vp, vp, i64, C.POINTER(vp)]
+    L.snerf_step_inputs_destroy.argtypes = [vp]
+    L.snerf_step_inputs_destroy.restype = None
+    for fn in (L.snerf_step_inputs_rays, L.snerf_step_inputs_samples, L.snerf_step_inputs_table_rows):
+        fn.restype, fn.argtypes = i64, [vp]
+    L.snerf_step_inputs_draw.argtypes = [vp, C.POINTER(StepInputsOut), vp]
+    L.snerf_step_inputs_get_state.argtypes = [vp, vp, vp]
+    L.snerf_step_inputs_set_state.argtypes = [vp, vp, vp]
+    L.snerf_step_inputs_words_host.argtypes = [u64, i64, i32, i64, i64, vp, vp]
     _lib = L
     return L
 
@@ -203,4 +217,6 @@ EXPORTS = ["snerf_last_error", "snerf_abi_version", "snerf_model_create", "snerf
            "snerf_loss_scratch_bytes", "snerf_loss_scratch_init", "snerf_loss_terms_forward", "snerf_loss_terms_backward",
            "snerf_loss_all_scratch_bytes", "snerf_loss_all_term_count", "snerf_loss_all_forward", "snerf_loss_all_backward",
            "snerf_loader_create", "snerf_loader_destroy", "snerf_loader_batches_per_epoch", "snerf_loader_batch", "snerf_loader_next", "snerf_loader_get_state", "snerf_loader_set_state",
-           "snerf_loader_indices_host", "snerf_loader_sc_rays_host", "snerf_loader_philox_host"]
+           "snerf_loader_indices_host", "snerf_loader_sc_rays_host", "snerf_loader_philox_host",
+           "snerf_step_inputs_create", "snerf_step_inputs_destroy", "snerf_step_inputs_rays", "snerf_step_inputs_samples", "snerf_step_inputs_table_rows",
+           "snerf_step_inputs_draw", "snerf_step_inputs_get_state", "snerf_step_inputs_set_state", "snerf_step_inputs_words_host"]

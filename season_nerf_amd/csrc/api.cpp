@@ -120,6 +120,16 @@ struct snerf_loader {
     int64_t shadow[4] = {0, 0, 0, 0};        // host copy, advanced per uncaptured launch: sizes a short last batch, nothing else
 };
 
+struct snerf_step_inputs {
+    uint64_t seed = 0;
+    int64_t n_rays = 0, n_samples = 0, table_rows = 0;
+    int rank = 0;
+    double H[12] = {0}, wc[3] = {0}, lon_scale = 0;
+    const float* d_table = nullptr;          // [table_rows, 8], the caller's
+    int64_t* d_state = nullptr;              // {draws, step, reserved, reserved}: what the kernels read; allocated by the first draw
+    int64_t shadow[4] = {0, 0, 0, 0};        // host copy, advanced per uncaptured launch
+};
+
 extern "C" {
 
 const char* snerf_last_error(void) { return g_err.c_str(); }
@@ -1027,6 +1037,109 @@ int snerf_loader_sc_rays_host(uint64_t seed, int64_t draws, int rank, int64_t fi
 int snerf_loader_philox_host(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4) {
     if (!counter4 || !key2 || !out4) return fail(SNERF_E_INVALID, "snerf_loader_philox_host: NULL argument");
     philox4x32_10(counter4, key2, out4);
+    return SNERF_OK;
+}
+
+// ---- per-step training inputs (csrc/loader.hip: step_inputs_draw_kernel; word assignment: csrc/loader_common.h)
+// The device copy of the state is allocated by the first call that needs it (a draw, or get / set once a draw has run): creating a handle and moving its
+// position touch no GPU, so a checkpoint can be prepared - and the argument checks tested - on a host without one.
+static int step_inputs_device(snerf_step_inputs* h) {
+    if (h->d_state) return SNERF_OK;
+    hipError_t e = hipMalloc((void**)&h->d_state, 4 * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMemcpy(h->d_state, h->shadow, 4 * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) return SNERF_OK;
+    if (h->d_state) (void)hipFree(h->d_state);
+    h->d_state = nullptr;
+    return fail_hip(e, "snerf_step_inputs: state allocation");
+}
+
+int snerf_step_inputs_create(uint64_t seed, int64_t n_rays, int64_t n_samples, int rank, const double* W2L_H, const double* world_center,
+                             const float* d_table, int64_t n_table_rows, snerf_step_inputs** out) {
+    if (!out) return fail(SNERF_E_INVALID, "snerf_step_inputs_create: NULL result pointer");
+    *out = nullptr;
+    if (!W2L_H || !world_center || !d_table) return fail(SNERF_E_INVALID, "snerf_step_inputs_create: NULL matrix, centre or table");
+    if (n_rays < 1 || n_rays > 0x7fffffffLL || n_samples < 1 || n_samples > 0x7fffffffLL)
+        return fail(SNERF_E_INVALID, "snerf_step_inputs_create: n_rays and n_samples must be in [1, 2^31)");
+    if (rank < 0 || (uint32_t)rank >= kStepInputsMaxRank) return fail(SNERF_E_INVALID, "snerf_step_inputs_create: rank outside [0, 2^24)");
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(W2L_H[i])) return fail(SNERF_E_INVALID, "snerf_step_inputs_create: non-finite matrix");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(world_center[i])) return fail(SNERF_E_INVALID, "snerf_step_inputs_create: non-finite world centre");
+    if (n_table_rows < 1) return fail(SNERF_E_INVALID, "snerf_step_inputs_create: n_table_rows < 1");
+    snerf_step_inputs* h = new snerf_step_inputs();
+    h->seed = seed; h->n_rays = n_rays; h->n_samples = n_samples; h->rank = rank; h->d_table = d_table; h->table_rows = n_table_rows;
+    for (int i = 0; i < 12; ++i) h->H[i] = W2L_H[i];
+    for (int i = 0; i < 3; ++i) h->wc[i] = world_center[i];
+    h->lon_scale = 1000.0 * 6378.137 * std::cos(world_center[0] * (3.14159265358979323846 / 180.0));      // this file is built with -ffp-contract=off
+    *out = h;
+    return SNERF_OK;
+}
+
+void snerf_step_inputs_destroy(snerf_step_inputs* h) {
+    if (!h) return;
+    if (h->d_state) (void)hipFree(h->d_state);
+    delete h;
+}
+
+int64_t snerf_step_inputs_rays(const snerf_step_inputs* h) { return h ? h->n_rays : fail(SNERF_E_INVALID, "NULL step-inputs handle"); }
+int64_t snerf_step_inputs_samples(const snerf_step_inputs* h) { return h ? h->n_samples : fail(SNERF_E_INVALID, "NULL step-inputs handle"); }
+int64_t snerf_step_inputs_table_rows(const snerf_step_inputs* h) { return h ? h->table_rows : fail(SNERF_E_INVALID, "NULL step-inputs handle"); }
+
+int snerf_step_inputs_draw(snerf_step_inputs* h, const snerf_step_inputs_out* out, void* stream) {
+    if (!h || !out) return fail(SNERF_E_INVALID, "snerf_step_inputs_draw: NULL handle or outputs");
+    if ((out->d_tv_image || out->d_tv_solar) && !out->d_base) return fail(SNERF_E_INVALID, "snerf_step_inputs_draw: the jitter outputs need d_base");
+    const bool capturing = stream_capturing(stream);
+    if (capturing && !h->d_state) return fail(SNERF_E_STATE, "snerf_step_inputs_draw: the first draw of a handle allocates its state - draw once before capturing");
+    if (int rc = step_inputs_device(h)) return rc;
+    StepInputsArgs a{};
+    a.state = h->d_state; a.seed = h->seed; a.rank = (uint32_t)h->rank; a.n_rays = h->n_rays; a.n_samples = h->n_samples;
+    for (int i = 0; i < 12; ++i) a.H[i] = h->H[i];
+    for (int i = 0; i < 3; ++i) a.wc[i] = h->wc[i];
+    a.lon_scale = h->lon_scale;
+    a.inv_s = (float)(1.0 / (double)h->n_samples);
+    a.base = out->d_base; a.table = h->d_table; a.table_rows = h->table_rows;
+    a.starts = out->d_starts; a.ends = out->d_ends; a.vec = out->d_vec; a.times = out->d_times; a.tv_image = out->d_tv_image; a.tv_solar = out->d_tv_solar;
+    a.hyper = out->d_hyper; a.trust = out->d_trust; a.lr2 = out->d_lr2;
+    hipError_t e = launch_step_inputs_draw(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "step inputs draw kernel launch");
+    e = launch_step_inputs_advance(h->d_state, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "step inputs advance kernel launch");
+    if (!capturing) { h->shadow[0] += 1; h->shadow[1] += 1; }      // (a capture executes nothing; its replays advance the device copy only)
+    return SNERF_OK;
+}
+
+int snerf_step_inputs_get_state(snerf_step_inputs* h, int64_t* state4, void* stream) {
+    if (!h || !state4) return fail(SNERF_E_INVALID, "snerf_step_inputs_get_state: NULL argument");
+    if (!h->d_state) {                                             // nothing has run on the device yet: the shadow is the state
+        for (int i = 0; i < 4; ++i) state4[i] = h->shadow[i];
+        return SNERF_OK;
+    }
+    if (stream_capturing(stream)) return fail(SNERF_E_STATE, "snerf_step_inputs_get_state: the stream is capturing");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpy(state4, h->d_state, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "snerf_step_inputs_get_state");
+}
+
+int snerf_step_inputs_set_state(snerf_step_inputs* h, const int64_t* state4, void* stream) {
+    if (!h || !state4) return fail(SNERF_E_INVALID, "snerf_step_inputs_set_state: NULL argument");
+    if (state4[0] < 0 || state4[1] < 0) return fail(SNERF_E_INVALID, "snerf_step_inputs_set_state: draws or step negative");
+    if (h->d_state && stream_capturing(stream)) return fail(SNERF_E_STATE, "snerf_step_inputs_set_state: the stream is capturing");
+    for (int i = 0; i < 4; ++i) h->shadow[i] = state4[i];
+    if (!h->d_state) return SNERF_OK;                              // the device copy starts from the shadow when the first draw creates it
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);      // no draw in flight reads the state while the blocking copy replaces it
+    if (e == hipSuccess) e = hipMemcpy(h->d_state, h->shadow, 4 * sizeof(int64_t), hipMemcpyHostToDevice);
+    return e == hipSuccess ? SNERF_OK : fail_hip(e, "snerf_step_inputs_set_state");
+}
+
+int snerf_step_inputs_words_host(uint64_t seed, int64_t draws, int rank, int64_t n_rays, int64_t n_samples, uint32_t* ray_words, uint32_t* sample_words) {
+    if (draws < 0 || rank < 0 || (uint32_t)rank >= kStepInputsMaxRank || n_rays < 0 || n_rays > 0x7fffffffLL || n_samples < 0 || n_samples > 0x7fffffffLL ||
+        (n_rays > 0 && !ray_words) || (n_samples > 0 && !sample_words))
+        return fail(SNERF_E_INVALID, "snerf_step_inputs_words_host: bad argument");
+    for (int64_t i = 0; i < n_rays; ++i) {
+        step_inputs_words(seed, (uint64_t)draws, (uint32_t)rank, 0, (uint32_t)i, ray_words + i * 8);
+        step_inputs_words(seed, (uint64_t)draws, (uint32_t)rank, 1, (uint32_t)i, ray_words + i * 8 + 4);
+    }
+    for (int64_t s = 0; s < n_samples; ++s) step_inputs_words(seed, (uint64_t)draws, (uint32_t)rank, 2, (uint32_t)s, sample_words + s * 4);
     return SNERF_OK;
 }
 

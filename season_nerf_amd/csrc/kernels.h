@@ -222,6 +222,25 @@ struct LoaderArgs {
 };
 hipError_t launch_loader_draw(const LoaderArgs& a, hipStream_t st);
 hipError_t launch_loader_advance(int64_t* state, int64_t batches_per_epoch, hipStream_t st);
+// loader.hip: what a training step draws per step besides its batch - random sun rays, both jitter vectors, one row of the schedule table
+struct StepInputsArgs {
+    const int64_t* state;      // {draws, step, reserved, reserved}
+    uint64_t seed;
+    uint32_t rank;
+    int64_t n_rays, n_samples;
+    double H[12];              // rows 0..2 of the world -> local matrix
+    double wc[3];              // world centre (lat, lon, height)
+    double lon_scale;          // 1000 * R_km * cos(deg2rad(lat)) of the centre
+    float inv_s;               // fp32(1 / n_samples)
+    const float* base;         // [n_samples]: linspace(0, 1, S + 1)[:-1]; needed with tv_image / tv_solar
+    const float* table;        // [table_rows, 8]
+    int64_t table_rows;
+    float *starts, *ends, *vec, *times;      // each optional: [n_rays, 3] x 3, [n_rays, 4]
+    float *tv_image, *tv_solar;              // each optional: [n_samples]
+    float *hyper, *trust, *lr2;              // each optional: [6], [1], [1]
+};
+hipError_t launch_step_inputs_draw(const StepInputsArgs& a, hipStream_t st);
+hipError_t launch_step_inputs_advance(int64_t* state, hipStream_t st);
 int mlp_lds_bytes(int bias_floats);
 int mlp_tile_points();
 int field_variant_chunks(int W, int C, int variant);

@@ -2,6 +2,7 @@
 // snerf_loader_sc_rays_host): exact, so host and device produce the same indices and the same sun-check rays bit for bit.
 //   loader_perm      keyed bijection of [0, n): balanced Feistel network over 2^bits >= n (bits even), six rounds, murmur3's 32-bit finaliser as the round
 //                    function, round keys from (seed, epoch) through splitmix64, cycle-walking while the value is >= n
+//   step_inputs_words  the words of the per-step training inputs (sun rays, jitter): Philox under a key of its own; the word assignment is stated there
 //   philox4x32_10    Salmon et al., "Parallel random numbers: as easy as 1, 2, 3" (SC 2011); pinned by the known-answer vectors of Random123
 #pragma once
 #include <stdint.h>
@@ -75,5 +76,19 @@ SNERF_HD inline void loader_sc_words(uint64_t seed, uint64_t draws, uint32_t ran
 }
 // u in [0, 1) from the top 24 bits: exact in fp32
 SNERF_HD inline float loader_uniform(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }
+
+// ---- per-step training inputs (step_inputs_draw_kernel of csrc/loader.hip, snerf_step_inputs_words_host of csrc/api.cpp) --------------------------------
+// A stream of its own: the key is the two halves of splitmix64(seed ^ kStepInputsTag) - the sun-check rays above key Philox with the seed itself.
+// Counter (index, draws lo, draws hi, rank + (block << 24)), rank < 2^24; the word assignment:
+//   block 0, index = ray i       w0 azimuth, w1 elevation (all 32 bits: u = w * 2^-32 in float64), w2 start x, w3 start y (top 24 bits: loader_uniform)
+//   block 1, index = ray i       w0 first time angle, w1 second time angle (top 24 bits), w2 / w3 unused
+//   block 2, index = sample s    w0 jitter of the image pass, w1 jitter of the sun-ray pass (top 24 bits), w2 / w3 unused
+constexpr uint64_t kStepInputsTag = 0x73746570696e7031ull;      // "stepinp1"
+constexpr uint32_t kStepInputsMaxRank = 1u << 24;
+SNERF_HD inline void step_inputs_words(uint64_t seed, uint64_t draws, uint32_t rank, uint32_t block, uint32_t index, uint32_t out[4]) {
+    const uint64_t k = splitmix64(seed ^ kStepInputsTag);
+    const uint32_t ctr[4] = {index, (uint32_t)draws, (uint32_t)(draws >> 32), rank + (block << 24)}, key[2] = {(uint32_t)k, (uint32_t)(k >> 32)};
+    philox4x32_10(ctr, key, out);
+}
 
 }  // namespace snerf

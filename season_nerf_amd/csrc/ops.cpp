@@ -41,6 +41,9 @@
 //   season_nerf::loader_next(loader, table[N,22], img_pt!?, top!?, bot!?, view_angle!?, sun_angle!?, time_encoded!?, sample_weight!?, gt_color!?, row_index!?,
 //        sc_top!?, sc_bot!?) -> ()        the next shuffled batch written into the given buffers ([>= batch, w] each, None = skip); the position lives in
 //        device memory behind the handle and advances per call - and per replay of a graph that captured the call            get_data, mg_run_NeRF.py:229-264
+//   season_nerf::step_inputs_draw(handle, table[K,8], starts!?, ends!?, vec!?, times!?, base?, tv_image!?, tv_solar!?, hyper!?, trust!?, lr2!?) -> ()
+//        the step's random sun rays, both jitter vectors and row `step` of the schedule table (`handle` = the snerf_step_inputs of a
+//        season_nerf_amd.step_inputs.DeviceStepInputs); position in device memory as above                          Eval_Tools_2.py:72-108, misc.py:236-241
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm presents HIP devices under the "cuda" device type
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -743,6 +746,28 @@ void loader_next(int64_t loader, const Tensor& table, const c10::optional<Tensor
     TORCH_CHECK(rows > 0, "season_nerf::loader_next failed (code ", rows, "): ", snerf_last_error());
 }
 
+// ---- per-step training inputs: sun rays, jitter and the schedule row drawn on the device (csrc/loader.hip), two kernel launches ------------------------
+void step_inputs_draw(int64_t handle, const Tensor& table, const c10::optional<Tensor>& starts, const c10::optional<Tensor>& ends,
+                      const c10::optional<Tensor>& vec, const c10::optional<Tensor>& times, const c10::optional<Tensor>& base, const c10::optional<Tensor>& tv_image,
+                      const c10::optional<Tensor>& tv_solar, const c10::optional<Tensor>& hyper, const c10::optional<Tensor>& trust, const c10::optional<Tensor>& lr2) {
+    snerf_step_inputs* h = (snerf_step_inputs*)handle;
+    TORCH_CHECK(h, "step_inputs_draw: NULL handle");
+    const int64_t n_rays = snerf_step_inputs_rays(h), n_samples = snerf_step_inputs_samples(h);
+    check_shape(table, "table", snerf_step_inputs_table_rows(h), 8);      // the table the handle was created over (it reads that one)
+    auto out = [&](const c10::optional<Tensor>& t, const char* name, int64_t numel) -> float* {
+        if (!t.has_value()) return nullptr;
+        check_dev_f32(*t, name);
+        TORCH_CHECK(t->device() == table.device() && t->numel() == numel, name, " must hold ", numel, " floats on the table's device, got ", t->sizes());
+        return t->data_ptr<float>();
+    };
+    snerf_step_inputs_out o{};
+    o.d_starts = out(starts, "starts", n_rays * 3); o.d_ends = out(ends, "ends", n_rays * 3); o.d_vec = out(vec, "vec", n_rays * 3);
+    o.d_times = out(times, "times", n_rays * 4); o.d_base = out(base, "base", n_samples); o.d_tv_image = out(tv_image, "tv_image", n_samples);
+    o.d_tv_solar = out(tv_solar, "tv_solar", n_samples); o.d_hyper = out(hyper, "hyper", 6); o.d_trust = out(trust, "trust", 1); o.d_lr2 = out(lr2, "lr2", 1);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(table.device());
+    ck(snerf_step_inputs_draw(h, &o, cur_stream(table)), "step_inputs_draw");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(season_nerf, m) {
@@ -781,6 +806,8 @@ TORCH_LIBRARY(season_nerf, m) {
     m.def("loss_scratch_prepare(Tensor like) -> ()");
     m.def("loader_next(int loader, Tensor table, Tensor(a!)? img_pt, Tensor(b!)? top, Tensor(c!)? bot, Tensor(d!)? view_angle, Tensor(e!)? sun_angle, "
           "Tensor(f!)? time_encoded, Tensor(g!)? sample_weight, Tensor(h!)? gt_color, Tensor(i!)? row_index, Tensor(j!)? sc_top, Tensor(k!)? sc_bot) -> ()");
+    m.def("step_inputs_draw(int handle, Tensor table, Tensor(a!)? starts, Tensor(b!)? ends, Tensor(c!)? vec, Tensor(d!)? times, Tensor? base, Tensor(e!)? tv_image, "
+          "Tensor(f!)? tv_solar, Tensor(g!)? hyper, Tensor(h!)? trust, Tensor(i!)? lr2) -> ()");
     m.def("loss_terms(Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor pe, Tensor? albedo_min_global, int world) "
           "-> (Tensor, Tensor)");
     m.def("loss_terms_bwd(Tensor g_vals, Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor min, int world) "
@@ -819,6 +846,7 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("trainer_zero_grad_", trainer_zero_grad_);
     m.impl("loss_scratch_prepare", loss_scratch_prepare);
     m.impl("loader_next", loader_next);
+    m.impl("step_inputs_draw", step_inputs_draw);
     m.impl("loss_terms", loss_terms);
     m.impl("loss_terms_bwd", loss_terms_bwd);
     m.impl("loss_terms_all", loss_terms_all);

@@ -99,6 +99,10 @@ def _register_fakes():
     def _(loader, table, img_pt, top, bot, view_angle, sun_angle, time_encoded, sample_weight, gt_color, row_index, sc_top, sc_bot):
         return None
 
+    @reg("season_nerf::step_inputs_draw")
+    def _(handle, table, starts, ends, vec, times, base, tv_image, tv_solar, hyper, trust, lr2):
+        return None
+
     @reg("season_nerf::loss_terms")
     def _(rgb, gt, albedo, sky, solar_vis, pv_exact, pe, albedo_min_global, world):
         return rgb.new_empty(5), rgb.new_empty(6)

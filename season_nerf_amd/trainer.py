@@ -78,6 +78,8 @@ class Net_tool:
     def _build_optimisers(self, lr, total_steps, lr_alpha_scale):
         """Net_Tool_2.py:111-130: fresh Adam on the network, fresh Adam on the adaptive-loss parameters, OneCycleLR on both."""
         network, eval_tool = self.network, self.eval_tool
+        self._schedule = (lr, total_steps, lr_alpha_scale)                     # what step_inputs.schedule_table restates as a device table
+        self.device_inputs = None                                              # a step_inputs.DeviceStepInputs once one is attached (opt-in)
         self.optim = FusedAdam(network, lr=lr) if self.fused_adam else torch.optim.Adam(network.parameters(), lr=lr)
         ada = eval_tool.ada_loss
         self.optim2 = None
@@ -97,12 +99,48 @@ class Net_tool:
         for k, v in loss.items():
             self.writer.add_scalar(prefix + k, float(v[0].detach()) if torch.is_tensor(v[0]) else float(v[0]), step)
 
+    def _step_schedulers(self):
+        """Both OneCycle schedules one step on.  With device inputs attached the second optimiser's learning rate is a device tensor that only the draw kernel
+        writes (from the schedule table): its scheduler then steps on host floats - for `get_last_lr` and the logs - and the tensor is put back untouched."""
+        self.sched.step()
+        if self.sched2 is None:
+            return
+        if self.device_inputs is None:
+            self.sched2.step()
+            return
+        groups = self.optim2.param_groups
+        kept = [g["lr"] for g in groups]
+        for g, last in zip(groups, self.sched2.get_last_lr()):
+            g["lr"] = float(last)
+        try:
+            self.sched2.step()
+        finally:
+            for g, t in zip(groups, kept):
+                g["lr"] = t
+
     def train_step(self, data_dict, current_step):
         """mg_run_NeRF.py:288-326.  Returns the loss dict {name: [value, weight]} of this step (tensors, not read back)."""
         self.optim.zero_grad()
         if self.optim2 is not None:
             self.optim2.zero_grad()
-        loss = self.eval_tool.get_loss(data_dict, self.network, current_step, train_mode=True)
+        di, ev = self.device_inputs, self.eval_tool
+        if di is None:
+            loss = ev.get_loss(data_dict, self.network, current_step, train_mode=True)
+        else:
+            # one launch draws the sun rays, both jitter vectors and this step's schedule row (Adam's scalars, trust, the second learning rate) on the device;
+            # the evaluator reads them where a captured step's fixed inputs sit (static_inputs) - the same sequence of draws, captured or not
+            di.check_step(current_step)
+            n = data_dict["Top"].shape[0]
+            if n > di.n_rays:
+                raise ValueError(f"Net_tool.train_step: the device inputs were built for {di.n_rays} rays, the batch has {n}")
+            di.draw_into(di.step_buffers(self))
+            b, gen = di.buffers, ev.solar_creation_tool
+            ev.static_inputs = {"tv_image": b["tv_image"], "tv_solar": b["tv_solar"], "trust": b["trust"] if ev.use_prior else None}
+            ev.solar_creation_tool = lambda m, include_times=True: (b["starts"][:m], b["ends"][:m], b["vec"][:m], b["times"][:m], None)
+            try:
+                loss = ev.get_loss(data_dict, self.network, current_step, train_mode=True)
+            finally:
+                ev.static_inputs, ev.solar_creation_tool = None, gen
         if getattr(loss, "vec", None) is not None:      # the terms are elements of one vector (training.LossDict): one dot product
             total_loss = loss.total()
         else:
@@ -116,9 +154,7 @@ class Net_tool:
             self.optim2.step()                            # must optimise the same objective (Solar_Correction weight = w / scale^2)
         if not self.fused_adam:
             self.network.invalidate_packed()  # parameters changed under a torch optimiser: re-pack before the next inference
-        self.sched.step()
-        if self.sched2 is not None:
-            self.sched2.step()
+        self._step_schedulers()
         self._log("Training/", loss, current_step)
         if self.writer is not None and current_step % self.log_every == 0:
             self.writer.add_scalar("LR/Learning_Rate", self.sched.get_last_lr()[0], current_step)
@@ -169,6 +205,14 @@ class GraphedTrainStep:
         step = GraphedTrainStep(tool, loader=train_loader)
         for k in range(n): loss = step(None, k)
 
+    With `inputs="device"` (opt-in; the default "host" is everything above) a step_inputs.DeviceStepInputs draws the sun rays, both jitter vectors and the
+    step's schedule row - Adam's scalars, the trust factor, the second optimiser's learning rate - inside the graph as well: after the loader's two kernels come
+    the draw's two, `_load` uploads nothing, and a replay takes no host input at all.  Same law as the host draws, a device stream of its own (`seed`), the same
+    sequence captured or eager (the warm-up steps draw from the same object).  `current_step` must be `first_step` + the steps taken: the schedule row is read
+    by the device's own count.
+
+        step = GraphedTrainStep(tool, loader=train_loader, inputs="device", seed=0)
+
     The LossDict a replayed step returns (and `tool.last_loss`) ALIASES the graph's static output: its tensors live in the graph's private
     pool and are overwritten by the next replay.  A caller that keeps losses across steps passes `keep=True` (one 5-float device copy per
     step, stream-ordered, no sync) or reads the value before the next call.
@@ -190,8 +234,13 @@ class GraphedTrainStep:
             return "the loader's last batch of an epoch is short (a replay cannot change its ray count): build it with drop_last=True"
         return None
 
-    def __init__(self, tool, data_dict=None, warmup=3, keep=False, check_every=64, loader=None):
+    def __init__(self, tool, data_dict=None, warmup=3, keep=False, check_every=64, loader=None, inputs="host", seed=0, first_step=0):
         from . import training
+        # inputs: "host" - the reference's host draws, packed and uploaded per replay (`_load`; the default: seeded runs reproduce the eager step's draws) |
+        # "device" - a step_inputs.DeviceStepInputs (the tool's own if one is attached, else a new one on `seed` whose schedule row 0 is the caller's step
+        # `first_step`) draws them inside the graph: with a loader a replay then takes no host input at all
+        if inputs not in ("host", "device"):
+            raise ValueError(f"GraphedTrainStep: inputs must be 'host' or 'device', got {inputs!r}")
         # check_every: every that many replays the parameters, Adam's moments and (adaptive loss) the loss object's parameters and moments are tested for
         # non-finite values ON THE DEVICE (one reduction, its flag copied to pinned memory without a sync and read one period later).  A hit disables the graph:
         # the step falls back to the eager path, with a warning.  0 = no check.  (Rounds 4-6 saw captured steps produce garbage moments; round 6 found the cause -
@@ -222,6 +271,16 @@ class GraphedTrainStep:
             self.data = {k: e(*data_dict[k].shape) for k in ("Top", "Bot", "Sun_Angle", "Time_Encoded", "GT_Color")}
         self.tv = {"tv_image": e(self.S), "tv_solar": e(self.S), "trust": e(1) if ev.use_prior else None}
         self.sol = (e(self.R, 3), e(self.R, 3), e(self.R, 3), e(self.R, 4))
+        self.inputs = tool.device_inputs                 # (a tool that already draws on the device keeps doing so: one stream, captured or not)
+        if inputs == "device" and self.inputs is None:
+            from .step_inputs import DeviceStepInputs
+            self.inputs = DeviceStepInputs(tool, self.R, self.S, seed, first_step=first_step).attach(tool)
+        if self.inputs is not None:
+            if (self.inputs.n_rays, self.inputs.n_samples) != (self.R, self.S):
+                raise ValueError(f"GraphedTrainStep: the device inputs draw {self.inputs.n_rays} rays x {self.inputs.n_samples} samples, the step has {self.R} x {self.S}")
+            b = self.inputs.buffers                      # the captured step reads the draw's own buffers
+            self.tv = {"tv_image": b["tv_image"], "tv_solar": b["tv_solar"], "trust": b["trust"] if ev.use_prior else None}
+            self.sol = (b["starts"], b["ends"], b["vec"], b["times"])
         self._gen = ev.solar_creation_tool
         self.warmup, self.calls, self.graph, self.loss = int(warmup), 0, None, None
 
@@ -234,6 +293,8 @@ class GraphedTrainStep:
         if self.loader is None:                          # (with a loader the graph's first two kernels fill self.data)
             for k, dst in self.data.items():
                 dst.copy_(tr._to_dev(data_dict[k], self.dev))
+        if self.inputs is not None:                      # drawn inside the graph (step_inputs.DeviceStepInputs): nothing to draw, pack or upload here
+            return
         tvi = tr.sample_parameters(self.S, eval_mode=False)
         st, en, vec, stime, _ = self._gen(self.R, include_times=True)
         tvs = tr.sample_parameters(self.S, eval_mode=False, include_end_pt=True)
@@ -257,6 +318,8 @@ class GraphedTrainStep:
         tool, ev = self.tool, self.ev
         if self.loader is not None:
             self.loader.next_into(self.drawn)          # two kernel nodes: the position is read from, and advanced in, device memory
+        if self.inputs is not None:
+            self.inputs.draw_into(self.inputs.step_buffers(tool))      # two more: sun rays, jitter, this step's schedule row
         tool.optim.zero_grad()
         if tool.optim2 is not None:
             # in place: the gradients of the loss object's parameters exist since the eager warm-up steps and keep their addresses - the capture allocates
@@ -289,7 +352,8 @@ class GraphedTrainStep:
 
     def _capture(self):
         tool, ev = self.tool, self.ev
-        tool.optim.make_capturable()
+        if self.inputs is None or tool.optim.hyper is None:      # (with device inputs the eager steps already run on the vector the draw fills: it stays)
+            tool.optim.make_capturable()
         if tool.optim2 is not None:
             self._torch_adam_capturable(tool.optim2, self.dev)
         ev.static_inputs = self.tv
@@ -387,17 +451,21 @@ class GraphedTrainStep:
         if self.loader is None and data_dict["Top"].shape[0] != self.R:
             raise ValueError(f"GraphedTrainStep: captured for {self.R} rays, got {data_dict['Top'].shape[0]}")
         first = self.graph is None
+        if self.inputs is not None:                    # the replay reads its schedule row by the DEVICE's step count: the caller's must be the same
+            self.inputs.check_step(current_step)
         self._load(data_dict, current_step, with_hyper=not first)
         if first:                                      # (the capture creates the device vector of Adam's scalars: filled on its own this once)
             self._capture()
-            tool.optim.set_hyper()
+            if self.inputs is None:
+                tool.optim.set_hyper()
+        if self.inputs is not None:
+            self.inputs.note_replay()
+            self.net._param_store.adam_steps += 1      # (what next_hyper counts on the host path: checkpoints carry it)
         self.graph.replay()
         if self.check_every > 0 and (self.calls - self.warmup) % self.check_every == self.check_every - 1:
             self._finite_check()
         self.net.invalidate_packed()
-        tool.sched.step()
-        if tool.sched2 is not None:
-            tool.sched2.step()                         # fills optim2's device-resident learning rate for the next replay
+        tool._step_schedulers()                        # (host inputs: fills optim2's device-resident learning rate for the next replay)
         loss = self._snapshot() if self.keep else self.loss
         tool._log("Training/", loss, current_step)
         if tool.writer is not None and current_step % tool.log_every == 0:       # as train_step logs it
@@ -433,8 +501,12 @@ class T_NeRF_Net_Tool(Net_tool):
     """
 
     def __init__(self, args, training_DSM, GT_DSM, device, H, WC, *, get_data=None, solar_vecs=None, writer=None, eval_img=None,
-                 fused_adam=True, log_every=1, ada_factory=None, use_graph=False, train_loader=None, val_loader=None, fused_loss="default"):
+                 fused_adam=True, log_every=1, ada_factory=None, use_graph=False, train_loader=None, val_loader=None, fused_loss="default",
+                 device_inputs=False, inputs_seed=None, inputs_rank=0):
         from .network import T_NeRF
+        # device_inputs: every training step - eager or captured - takes its sun rays, jitter and schedule scalars from ONE step_inputs.DeviceStepInputs stream
+        # (seed inputs_seed, default 0) instead of the host's numpy / torch generators; each learning phase gets a new schedule table, the draw counter runs on
+        self._use_device_inputs, self._inputs_seed, self._inputs_rank = bool(device_inputs), int(inputs_seed or 0), int(inputs_rank)
         if fused_loss not in ("default", "all"):
             raise ValueError(f"T_NeRF_Net_Tool: fused_loss must be 'default' or 'all', got {fused_loss!r}")
         self.fused_loss = fused_loss               # carried to every phase's evaluator (All_in_One_Eval.fused_loss)
@@ -469,6 +541,7 @@ class T_NeRF_Net_Tool(Net_tool):
         self.optim = self.optim2 = self.sched = self.sched2 = None
         self._ada_params = []
         self.last_loss = None
+        self.device_inputs, self._inputs_draws = None, 0
         if ada_factory is None:
             from .adaptive_loss import AdaptiveLossFunction
             ada_factory = AdaptiveLossFunction
@@ -505,8 +578,19 @@ class T_NeRF_Net_Tool(Net_tool):
         else:
             raise ValueError(f"T_NeRF_Net_Tool: invalid learning mode {mode}")
         self.eval_tool.fused_loss = self.fused_loss
+        if self.device_inputs is not None:     # the stream runs on through the phase change: the next phase's object starts at this draw count
+            self._inputs_draws = self.device_inputs.get_state()[0]
         self._build_optimisers(args.lr, self.Section_Steps[mode - 1], args.lr_alpha_scale)
         self._graphed = None                   # a new evaluator and new optimisers: a captured step of the previous phase is stale
+
+    def _attach_device_inputs(self, n_rays):
+        """The phase's step_inputs.DeviceStepInputs: a schedule table of this phase's optimisers (row 0 = the phase's first step), the draw counter of the run."""
+        from .step_inputs import DeviceStepInputs
+        if not self.fused_adam:
+            raise ValueError("T_NeRF_Net_Tool: device_inputs needs fused_adam")
+        di = DeviceStepInputs(self, n_rays, self.args.n_samples, self._inputs_seed, rank=self._inputs_rank, first_step=self._step_count)
+        di.set_state(self._inputs_draws, 0)
+        di.attach(self)
 
     def get_data(self, eval_mode=False):
         if self._get_data is not None:
@@ -526,12 +610,16 @@ class T_NeRF_Net_Tool(Net_tool):
         self.network.train()
         loader = self.train_loader if self._get_data is None else None
         graph = self.use_graph and GraphedTrainStep.eligible(self, loader) is None
+        if self._use_device_inputs and self.device_inputs is None and loader is not None:
+            self._attach_device_inputs(loader.batch_size)
         if graph and loader is not None:               # the batch is drawn inside the captured step: nothing to fetch here
             if self._graphed is None:
                 self._graphed = GraphedTrainStep(self, loader=loader, warmup=2)
             self._graphed(None, self._step_count)
         else:
             data = self.get_data(eval_mode=False)
+            if self._use_device_inputs and self.device_inputs is None:
+                self._attach_device_inputs(data["Top"].shape[0])
             if graph:
                 if self._graphed is None or self._graphed.R != data["Top"].shape[0]:
                     self._graphed = GraphedTrainStep(self, data, warmup=2)

@@ -439,19 +439,37 @@ class create_solor_rays_uniform:
         # Host arithmetic in numpy (never threaded); torch only for the RNG draws the reference takes from torch's CPU
         # generator, in the same order - a torch CPU op on these [n,3] arrays can wake the whole intra-op thread pool,
         # whose spinning workers then starve the kernel-launching thread under a container CPU quota.
-        az_el = np.random.random(n * 2).reshape([n, 2]) * np.array([[360, 89]]) + np.array([[-180, 1]])
-        vec = _angles_to_local_vecs(az_el[:, 1], az_el[:, 0], self.WC, self.W2L)   # vectorised, same arithmetic per ray
-        delta = 2 * (vec / vec[:, 2::])
-        starts = np.ones([n, 3], dtype=np.float32)
-        starts[:, 0] = np.float32(2.0) * torch.rand(n).numpy() + np.float32(-1.0)
-        starts[:, 1] = np.float32(2.0) * torch.rand(n).numpy() + np.float32(-1.0)
-        ends = (starts.astype(np.float64) - delta).astype(np.float32)          # fp32 tensor - float64 array, then .float()
-        vec_t = vec.astype(np.float32)
+        u_ang = np.random.random(n * 2).reshape([n, 2])
+        u_x, u_y = torch.rand(n).numpy(), torch.rand(n).numpy()
+        u_t = torch.rand([n, 2]).numpy() if include_times else None
+        starts, ends, vec_t, times, az_el = solar_rays_from_uniforms(u_ang, u_x, u_y, u_t, self.W2L, self.WC)
         if not include_times:
             return torch.from_numpy(starts), torch.from_numpy(ends), torch.from_numpy(vec_t)
-        fr = torch.rand([n, 2]).numpy() * np.float32(2 * np.pi)
-        times = np.stack([np.cos(fr[:, 0]), np.sin(fr[:, 0]), np.cos(fr[:, 1]), np.sin(fr[:, 1])], 1).astype(np.float32)
         return torch.from_numpy(starts), torch.from_numpy(ends), torch.from_numpy(vec_t), torch.from_numpy(times), az_el
+
+
+def solar_rays_from_uniforms(u_ang, u_x, u_y, u_t, W2L_H, WC, times_in_float64=False):
+    """The law of the random sun rays (Eval_Tools_2.py:72-108) on given uniforms: THE host statement of it - `create_solor_rays_uniform` feeds it the
+    reference's host draws, `step_inputs.DeviceStepInputs.host_mirror` the words of the device stream.
+    u_ang [n, 2] float64 (azimuth, elevation), u_x / u_y [n] fp32, u_t [n, 2] fp32 or None -> starts, ends, vec [n, 3] fp32, times [n, 4] fp32 (None
+    without u_t), az_el [n, 2] float64.  times_in_float64: cos / sin of the fp32 angle in float64, then rounded (what the device kernel computes);
+    default: numpy's fp32 cos / sin, as the host path always has."""
+    n = u_ang.shape[0]
+    az_el = u_ang * np.array([[360, 89]]) + np.array([[-180, 1]])
+    vec = _angles_to_local_vecs(az_el[:, 1], az_el[:, 0], WC, W2L_H)   # vectorised, same arithmetic per ray
+    delta = 2 * (vec / vec[:, 2::])
+    starts = np.ones([n, 3], dtype=np.float32)
+    starts[:, 0] = np.float32(2.0) * u_x + np.float32(-1.0)
+    starts[:, 1] = np.float32(2.0) * u_y + np.float32(-1.0)
+    ends = (starts.astype(np.float64) - delta).astype(np.float32)          # fp32 tensor - float64 array, then .float()
+    vec_t = vec.astype(np.float32)
+    if u_t is None:
+        return starts, ends, vec_t, None, az_el
+    fr = u_t * np.float32(2 * np.pi)
+    if times_in_float64:
+        fr = fr.astype(np.float64)
+    times = np.stack([np.cos(fr[:, 0]), np.sin(fr[:, 0]), np.cos(fr[:, 1]), np.sin(fr[:, 1])], 1).astype(np.float32)
+    return starts, ends, vec_t, times, az_el
 
 
 def _after_train_forward(net):
@@ -782,6 +800,7 @@ class FusedAdam(torch.optim.Optimizer):
             store.adam_v.zero_()
             store.adam_steps = 0
         self.hyper = None              # device vector [lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t] of the capturable form
+        self.hyper_from_device = False # True: a kernel fills `hyper` before every step (step_inputs.DeviceStepInputs), the host uploads nothing
 
     def make_capturable(self):
         """Switch to the form a hipGraph can hold: `step()` launches the Adam kernel that reads its scalars from `self.hyper`; the host
@@ -858,7 +877,10 @@ class FusedAdam(torch.optim.Optimizer):
                                                                         # first run with two real ranks, tests/test_gpu_two_ranks.py)
         if self.hyper is not None:     # capturable form: the step's scalars come from device memory (a replayed graph: set_hyper before every replay)
             if not torch.cuda.is_current_stream_capturing():
-                self.set_hyper()       # an eager step after make_capturable(): refresh them here
+                if self.hyper_from_device:      # step_inputs.DeviceStepInputs has written this step's row of its schedule table into self.hyper
+                    self.net._param_store.adam_steps += 1
+                else:
+                    self.set_hyper()   # an eager step after make_capturable(): refresh them here
             eng.adam_step_dev(self.hyper)
         else:
             eng.adam_step(g["lr"], g["betas"], g["eps"])
