@@ -359,6 +359,11 @@ int snerf_trainer_bind(snerf_trainer* t, float* d_params, float* d_grads, float*
 /* the sizes the trainer is bound to (any pointer may be NULL); SNERF_E_STATE before snerf_trainer_bind */
 int snerf_trainer_bound_sizes(const snerf_trainer* t, int64_t* n_rays, int64_t* n_solar_rays, int* n_samples);
 /* image-ray pass: T_NeRF.forward + compositing.  train_bn: 1 = batch statistics + EMA update, 0 = running statistics.
+ * The pass remembers which it was, and its backward (snerf_trainer_backward_image / _dt / _points) differentiates the function that ran:
+ * after train_bn = 1 the BatchNorm layers give dz = gamma istd (dy - mean(dy) - xhat mean(dy xhat)), after train_bn = 0 (frozen BatchNorm:
+ * mean and istd are constants) dz = gamma istd dy, and the biases in front of BatchNorm get a gradient.  d gamma = sum dy xhat and
+ * d beta = sum dy in both, xhat from the statistics of the forward.  A train_bn = 0 pass and its backward leave the running statistics alone
+ * and need no collective (snerf_trainer_set_allreduce: none is issued).
  * flags: bit0 = classic solar as in snerf_composite_rays.  bit1 (zero segment length outside the cube) is refused with SNERF_E_INVALID:
  * the compositing backward differentiates the plain segment length, so a forward with bit1 would get the gradients of another function. */
 int snerf_trainer_forward_image(snerf_trainer* t, int64_t n_rays, int n_samples, const float* d_top, const float* d_bot,

@@ -29,6 +29,9 @@
 // parameter / gradient / workspace tensors).  The forward ops are functional in their tensor arguments (torch.library.register_autograd
 // attaches the backward ops to them, season_nerf_amd/training.py); the engine keeps the activations of its last forward and the BatchNorm
 // running statistics behind the handle.  `params` only ties the ops into the autograd graph of the parameters.
+// train_bn = false (a module in .eval(): frozen BatchNorm, running statistics) is differentiable too: the engine remembers the mode of each pass's
+// forward and train_bwd_image / train_bwd_points return the gradient of THAT function (dz = gamma istd dy through a frozen layer; the biases in front
+// of BatchNorm get a gradient); nothing of the running statistics changes.
 //   season_nerf::train_fwd_image(trainer, top, bot, tvals, sun, time, train_bn, classic, n_classes, height_map?, trust, trust_dev?, params[])       get_loss, image rays
 //        -> [rgb, albedo, sky, pe, rgb_merged, albedo_merged | pv, ps, delta, classes, rho, solar_vis, col, pts, adjust_col | prior terms]  Eval_Tools_2.py:165-252
 //   season_nerf::train_bwd_image(trainer, grads!, g_rgb?, g_albedo?, g_sky?, g_pe?, rho_prior?, trust, g_rgb_merged?, g_albedo_merged?) -> ()

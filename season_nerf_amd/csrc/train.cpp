@@ -92,6 +92,7 @@ struct snerf_trainer {
         Act Hc[9], Hac[3], Hsc[3], In5c, In_s1c, Zc3, Zc8;
         float* tabs = nullptr;      // [15 layers][2][W] activation-on-load tables of this pass
         bool aol = false;
+        bool batch_bn = true;       // the last forward of this pass normalised with batch statistics (train_bn != 0); false: with the running estimates
         float* tab(int slot, int W) const { return aol ? tabs + (int64_t)slot * 2 * W : nullptr; }      // slots: 0-8 trunk, 9-11 adjust, 12-14 solar
     } img, sol;
     Act dA, dB, dX1;
@@ -326,9 +327,11 @@ static int sine_fwd(snerf_trainer* t, const LayerP& L, Act In, int64_t M, Act Z,
 // Accumulates weight/bias (and BN affine) gradients; if dIn.p != null writes dL/dIn[:, :n_in_cols].
 static int sine_bwd(snerf_trainer* t, const LayerP& L, Act D, Act Z, Act In, int64_t M, float* bnslot,
                     Act dIn, int n_in_cols, bool accumulate_in, hipStream_t st, bool pre_activated = false,
-                    const ActBelow* below = nullptr, bool* fused_below = nullptr) {
+                    const ActBelow* below = nullptr, bool* fused_below = nullptr, bool batch_bn = true) {
     // pre_activated: the dgrad that produced D already applied this layer's activation backward (D = dL/dH * cos) and left the
     // column sums in t->bn_stats.  below / fused_below: the same offer for the layer that will consume dIn.
+    // batch_bn: the forward normalised with batch statistics.  false (train_bn = 0, running estimates): mean and istd do not depend on
+    // the batch, so dZ = gamma istd dY; d beta and d gamma keep their form, with xhat taken from the running estimates.
     const int C = L.n_out;
     if (fused_below) *fused_below = false;
     // EXPERIMENT (never on by default): the inter-layer gradient as bf16.  Rounds dL/dY (as the dgrad above would have stored it) and, behind the
@@ -354,7 +357,10 @@ static int sine_bwd(snerf_trainer* t, const LayerP& L, Act D, Act Z, Act In, int
             HIPCK(launch_copy_cols(sdy, C, t->grads + L.beta, C, 1, C, true, st));       // parameter gradients stay per-rank sums
             HIPCK(launch_copy_cols(sdyx, C, t->grads + L.g, C, 1, C, true, st));
         }
-        RC(all_reduce(t, t->bn_bwd, 2 * t->W, false, st));                               // the BatchNorm backward means are global
+        if (batch_bn) RC(all_reduce(t, t->bn_bwd, 2 * t->W, false, st));                 // the BatchNorm backward means are global
+        // frozen statistics: the sums have gone into d beta / d gamma above.  With both at zero every dZ form below (bn_bwd2, its column-pass
+        // twins, the ride in the weight-gradient kernel) computes gamma istd (dY - 0 - xhat 0) = gamma istd dY exactly; d bias = 30 sum dZ follows
+        else HIPCK(snerf_zero_async(t->bn_bwd, 0, 2 * t->W * sizeof(float), st));
         const int64_t Mg = M * (t->ar_fn ? t->world : 1);
         // D holds dL/dY: the dZ sweep rides in the weight-gradient kernel (dY -> dZ in registers, written back in place) or is a pass of its own
         bn = WgradBN{Z.p, Z.ld, t->params + L.g, mean, istd, sdy, sdyx, 1.f / (float)Mg, 30.f, t->grads + L.b};
@@ -415,6 +421,7 @@ static int forward_pass(snerf_trainer* t, snerf_trainer::Pass& P, bool solar, in
     // Needs the bf16x3 kernels for every consumer (K <= 512, widths multiples of 16) and enough points for them to be used.
     const bool aol = t->aol_mode == 1 && W % 16 == 0 && rows_ok(engine_policy(t), N, W + 64, 1);
     P.aol = aol;
+    P.batch_bn = train_bn;
     auto view = [&](Act Z, Act H, int slot, int n) { return aol ? Act{Z.p, Z.ld, P.tab(slot, W), n} : H; };
     // fc4's output lives inside fc5's concat input [ . | PE]: its H without, its Z with activation on load
     // likewise fc9's inside fc_solar_1's concat input [ . | PE(sun)]
@@ -738,12 +745,12 @@ static int network_backward_image(snerf_trainer* t, bool classic, const float* d
     };
     {
         const ActBelow b = below_of(7);
-        RC(sine_bwd(t, Ls[L_FC9], Act{t->dX1.p, W2}, P.Zc8, P.Hc[7], N, P.bn + 7 * 4 * W, Act{cur, W}, W, false, st, pre9, &b, &pre));
+        RC(sine_bwd(t, Ls[L_FC9], Act{t->dX1.p, W2}, P.Zc8, P.Hc[7], N, P.bn + 7 * 4 * W, Act{cur, W}, W, false, st, pre9, &b, &pre, P.batch_bn));
     }
     for (int l = 7; l >= 1; --l) {
         const Act In = l == 4 ? P.In5c : P.Hc[l - 1];
         const ActBelow b = below_of(l - 1);
-        RC(sine_bwd(t, Ls[L_FC1 + l], Act{cur, W}, l == 3 ? P.Zc3 : P.Z[l], In, N, P.bn + (l - 1) * 4 * W, Act{nxt, W}, W, false, st, pre, &b, &pre));
+        RC(sine_bwd(t, Ls[L_FC1 + l], Act{cur, W}, l == 3 ? P.Zc3 : P.Z[l], In, N, P.bn + (l - 1) * 4 * W, Act{nxt, W}, W, false, st, pre, &b, &pre, P.batch_bn));
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
     RC(sine_bwd(t, Ls[L_FC1], Act{cur, W}, P.Z[0], Act{P.E.p, 64}, N, nullptr, Act{nullptr, 0}, 0, false, st, pre));
