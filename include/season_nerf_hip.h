@@ -517,42 +517,33 @@ int snerf_trainer_adam_step(snerf_trainer* t, float lr, float beta1, float beta2
  * step captured in a hipGraph (kernel arguments are frozen at capture): the host rewrites the six floats before every replay (OneCycleLR,
  * Net_Tool_2.py:123-130; Adam's bias corrections). */
 int snerf_trainer_adam_step_dev(snerf_trainer* t, const float* d_hyper6, void* stream);
-/* ---- the scalar loss terms of a training step: All_in_One_Eval.get_loss, Eval_Tools_2.py:340-420, in the default training configuration (MSE colour
- * loss :413, solar rays on :350-372, default solar model, no DSM prior).  forward: d_vals5 = [Solar_Correction (:361), Solar_Correction_2 (:366,
- * a value only: detached in this configuration), Sky_Color_Var (:381-388), Albedo_Color (:374-379), Color (:413)], d_min3 (SIX floats) = the per-channel
- * albedo minimum the Albedo_Color term used, then - as int32 bits - the ONE row that owns each minimum on this rank (the lowest tied row, as
- * torch.min; -1 where the global minimum lives on another rank): the backward hands the minimum's gradient to that row only.  d_sky is the per-ray sky colour [R,3] (the reference's [R,S,3] tensor holds S copies of it).
- * d_albedo_min_global (optional, [3]) + world: data-parallel training - the minimum over the global batch (one MIN all-reduce by the caller), the
- * value divided by n_rays * world.  backward: from dL/d(vals5) to dL/dRendered_Col, dL/dAlbedo_Color, dL/dSky_Col [R,3] and dL/dSolar_Vis [Rs,S]
- * (what snerf_trainer_backward_image / _solar take).  d_scratch: snerf_loss_scratch_bytes() bytes, initialised ONCE by snerf_loss_scratch_init (the
- * forward leaves it initialised). */
-size_t snerf_loss_scratch_bytes(void);
-int snerf_loss_scratch_init(void* d_scratch, void* stream);
-int snerf_loss_terms_forward(int64_t n_rays, int64_t n_solar_rays, int n_samples, const float* d_rgb, const float* d_gt, const float* d_albedo,
-                             const float* d_sky, const float* d_solar_vis, const float* d_pv_exact, const float* d_pe, const float* d_albedo_min_global,
-                             int world, void* d_scratch, float* d_vals5, float* d_min3, void* stream);
-int snerf_loss_terms_backward(int64_t n_rays, int64_t n_solar_rays, int n_samples, const float* d_rgb, const float* d_gt, const float* d_albedo,
-                              const float* d_sky, const float* d_solar_vis, const float* d_pv_exact, const float* d_min3, int world, const float* d_g_vals5,
-                              float* d_g_rgb, float* d_g_albedo, float* d_g_sky, float* d_g_solar_vis, void* stream);
-/* ---- the loss terms of the configurations snerf_loss_terms_* does not serve: Barron's adaptive colour loss (Eval_Tools_2.py:421-450) and / or the
- * DSM-prior phase (:243, :391-412), default solar model.  flags selects the configuration; the value vector follows get_loss's key order:
+/* ---- the scalar loss terms of a training step: All_in_One_Eval.get_loss, Eval_Tools_2.py:340-450, solar rays on (:350-372), default solar model: the MSE
+ * colour loss (:413) or Barron's adaptive colour loss (:421-450), without or with the DSM-prior phase (:243, :391-412).  flags selects the configuration;
+ * the value vector follows get_loss's key order:
+ *   0                                      (5):  Solar_Correction (:361), Solar_Correction_2 (:366, a value only: detached), Sky_Color_Var (:381-388),
+ *                                                Albedo_Color (:374-379), Color (:413)
  *   SNERF_LOSS_ADAPTIVE                    (8):  Solar_Correction, Solar_Correction_2, Sky_Color_Var, Albedo_Color, Color_ada, Color_alpha, Color_width, Color
  *   SNERF_LOSS_ADAPTIVE | SNERF_LOSS_PRIOR (12): Solar_Correction, Solar_Correction_2, Sky_Color_Var, Albedo_Color, Alpha_Adjust_ada, Color_ada, Color_alpha,
  *                                                Color_width, Alpha_Adjust, Alpha_alpha, Alpha_width, Color
  *   SNERF_LOSS_PRIOR                       (6):  Solar_Correction, Solar_Correction_2, Sky_Color_Var, Albedo_Color, Color, Alpha_Adjust
- * SNERF_LOSS_SKY_DETACHED: Sky_Color_Var is a value only (the reference detaches it in the prior phase).  Color_ada = mean over [R,3] of
+ * SNERF_LOSS_SKY_DETACHED: Sky_Color_Var is a value only (the reference detaches it in the prior phase).  d_sky is the per-ray sky colour [R,3] (the
+ * reference's [R,S,3] tensor holds S copies of it).  Color_ada = mean over [R,3] of
  * nll(Rendered_Col - GT) with nll(x) = rho(x, alpha, c) + log c + log Z(alpha) (Barron 2019, as season_nerf_amd/adaptive_loss.py states it; parity with
  * robust_loss_pytorch is NOT pinned); Alpha_Adjust_ada = mean over [R,S] of nll(PE - PE_Supervised) under the second, one-dimensional loss object;
  * Alpha_Adjust = MSE(PE, PE_Supervised); Color = MSE(d_rgb_merged if given, else d_rgb, GT) - a value only beside the adaptive loss.  alpha / scale are
  * the float32 vectors the caller formed ([3] for colour, [1] for alpha); log Z is the cubic Hermite spline on d_logz_value / d_logz_slope: 513 float64 numbers
  * each on the grid alpha_i = 4 i / 512 (float64: rounding the table to float32 alone moves d log Z / d alpha by 1.5e-5).  Pointers a configuration does not use may be NULL.
+ * d_albedo_min_global (optional, [3]) + world: data-parallel training - the minimum over the global batch (one MIN all-reduce by the caller), the
+ * Albedo_Color value divided by n_rays * world.
  * forward: d_vals and d_weights hold snerf_loss_all_term_count(flags) floats - the weights of sum(value * weight): w_solar / mean(scale colour)^2 for the
  * two Solar_Correction terms beside the adaptive loss (w_solar otherwise), w_solar for Sky_Color_Var and Albedo_Color, w_color for Color_ada / Color,
- * w_alpha for Alpha_Adjust(_ada), 1 for the logged means; d_aux14: 14 floats for the backward (albedo minima and their rows as d_min3 above, then
- * d term / d alpha and d term / d scale per channel of both loss objects).  Values are reduced without floating-point atomics, block sums in a fixed
+ * w_alpha for Alpha_Adjust(_ada), 1 for the logged means; d_aux14: 14 floats for the backward - the per-channel albedo minimum the Albedo_Color term
+ * used (3), then - as int32 bits - the ONE row that owns each minimum on this rank (3; the lowest tied row, as torch.min; -1 where the global minimum
+ * lives on another rank): the backward hands the minimum's gradient to that row only; then d term / d alpha and d term / d scale per channel of both
+ * loss objects (8; zeros without the adaptive loss).  Values are reduced without floating-point atomics, block sums in a fixed
  * order: two calls on the same inputs give the same bits.  d_scratch: snerf_loss_all_scratch_bytes() bytes, no initial state needed, one per stream.
- * backward: from d_g_vals (dL / d vals) to the gradients of snerf_loss_grads; terms that are values only contribute nothing, the gradient of a detached
- * input is written as zeros; outputs of inputs the configuration lacks may be NULL. */
+ * backward: from d_g_vals (dL / d vals) to the gradients of snerf_loss_grads (what snerf_trainer_backward_image / _solar take); terms that are values
+ * only contribute nothing, the gradient of a detached input is written as zeros; outputs of inputs the configuration lacks may be NULL. */
 #define SNERF_LOSS_ADAPTIVE 1
 #define SNERF_LOSS_PRIOR 2
 #define SNERF_LOSS_SKY_DETACHED 4
@@ -565,7 +556,7 @@ typedef struct snerf_loss_in {
     const float *d_alpha_color, *d_scale_color;                            /* adaptive: [3] */
     const float *d_alpha_alpha, *d_scale_alpha;                            /* adaptive + prior: [1] */
     const double *d_logz_value, *d_logz_slope;                             /* adaptive: [513], float64 */
-    const float* d_albedo_min_global;                                      /* optional [3] + world, as snerf_loss_terms_forward */
+    const float* d_albedo_min_global;                                      /* optional [3] + world: data parallel */
     int world;
     float w_solar, w_color, w_alpha;
 } snerf_loss_in;

@@ -214,7 +214,6 @@ EXPORTS = ["snerf_last_error", "snerf_abi_version", "snerf_model_create", "snerf
            "snerf_trainer_forward_image", "snerf_trainer_backward_image", "snerf_trainer_backward_image_dt", "snerf_trainer_backward_points", "snerf_trainer_forward_solar",
            "snerf_trainer_backward_solar", "snerf_trainer_zero_grad", "snerf_trainer_set_allreduce", "snerf_trainer_adam_step", "snerf_trainer_adam_step_dev", "snerf_adam_step", "snerf_trainer_debug_read", "snerf_train_kernel_debug",
            "snerf_rows_debug_set", "snerf_rows_record_reset", "snerf_rows_record_read",
-           "snerf_loss_scratch_bytes", "snerf_loss_scratch_init", "snerf_loss_terms_forward", "snerf_loss_terms_backward",
            "snerf_loss_all_scratch_bytes", "snerf_loss_all_term_count", "snerf_loss_all_forward", "snerf_loss_all_backward",
            "snerf_loader_create", "snerf_loader_destroy", "snerf_loader_batches_per_epoch", "snerf_loader_batch", "snerf_loader_next", "snerf_loader_get_state", "snerf_loader_set_state",
            "snerf_loader_indices_host", "snerf_loader_sc_rays_host", "snerf_loader_philox_host",

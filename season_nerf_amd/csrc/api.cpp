@@ -133,7 +133,7 @@ struct snerf_step_inputs {
 extern "C" {
 
 const char* snerf_last_error(void) { return g_err.c_str(); }
-int snerf_abi_version(void) { return 9; }
+int snerf_abi_version(void) { return 10; }
 
 snerf_model* snerf_model_create(int layer_width, int n_classes) {
     if (layer_width != 64 && layer_width != 256 && layer_width != 512) {

@@ -582,25 +582,9 @@ void trainer_zero_grad_(int64_t trainer, Tensor grads) {
     ck(snerf_trainer_zero_grad(t, cur_stream(grads)), "trainer_zero_grad_");
 }
 
-// the self-cleaning reduction scratch of loss_terms: one per (device, stream), created (and initialised, in stream order) at first use; launches of one
-// stream are serialised, and the forward leaves the scratch in its initial state.  (one scratch per DEVICE let two streams of a device - a
-// captured step on its side stream next to an eager validation step, two networks trained side by side - mix their sums.)
-static Tensor loss_scratch(const Tensor& like) {
-    static std::mutex mu;
-    static auto* per_stream = new std::map<std::pair<int, void*>, Tensor>();      // leaked on purpose: no tensor destructor after the HIP runtime has shut down
-    std::lock_guard<std::mutex> lock(mu);
-    static const bool per_dev = getenv("SNERF_LOSS_SCRATCH_PER_DEVICE") != nullptr;      // A/B switch (debug)
-    Tensor& s = (*per_stream)[{like.get_device(), per_dev ? nullptr : cur_stream(like)}];
-    if (!s.defined()) {
-        s = at::empty({(int64_t)snerf_loss_scratch_bytes()}, like.options().dtype(at::kByte));
-        ck(snerf_loss_scratch_init(s.data_ptr(), cur_stream(like)), "loss_scratch");
-    }
-    return s;
-}
-
-// Create (and initialise) the reduction scratch of the CURRENT stream now: a captured step calls this on its capture stream BEFORE the capture begins, so that
-// the capture neither allocates it from the graph's private pool nor records its initialisation as a node that re-runs on every replay.
-// the block-sum scratch of loss_terms_all: one per (device, stream) as above; it needs no initial state (snerf_loss_all_forward)
+// the block-sum scratch of loss_terms_all: one per (device, stream), created at first use; launches of one stream are serialised, and the scratch needs no
+// initial state (snerf_loss_all_forward).  (One scratch per DEVICE would let two streams of a device - a captured step on its side stream next to an eager
+// validation step, two networks trained side by side - mix their sums.)
 static Tensor loss_all_scratch(const Tensor& like) {
     static std::mutex mu;
     static auto* per_stream = new std::map<std::pair<int, void*>, Tensor>();
@@ -609,47 +593,15 @@ static Tensor loss_all_scratch(const Tensor& like) {
     if (!s.defined()) s = at::empty({(int64_t)snerf_loss_all_scratch_bytes()}, like.options().dtype(at::kByte));
     return s;
 }
+// Create the scratch of the CURRENT stream now: a captured step calls this on its capture stream BEFORE the capture begins, so that the capture does not
+// allocate it from the graph's private pool.
 void loss_scratch_prepare(const Tensor& like) {
     check_dev_f32(like, "like");
     c10::hip::HIPGuardMasqueradingAsCUDA g(like.device());
-    (void)loss_scratch(like);
     (void)loss_all_scratch(like);
 }
 
-// ---- scalar loss terms of a training step (get_loss, Eval_Tools_2.py:340-420, default configuration) ---------------------------------
-// loss_terms(rgb, gt, albedo, sky, solar_vis, pv_exact, pe, albedo_min_global?, world) -> (vals[5], min[6]: the minima + the rows that own them);  loss_terms_bwd: the gradients
-std::tuple<Tensor, Tensor> loss_terms(const Tensor& rgb, const Tensor& gt, const Tensor& albedo, const Tensor& sky, const Tensor& sv, const Tensor& pv,
-                                      const Tensor& pe, const c10::optional<Tensor>& alb_min_global, int64_t world) {
-    check_shape(rgb, "rgb", -1, 3);
-    const int64_t R = rgb.size(0);
-    check_shape(gt, "gt", R, 3); check_shape(albedo, "albedo", R, 3); check_shape(sky, "sky", R, 3);
-    check_dev_f32(sv, "solar_vis"); check_dev_f32(pv, "pv_exact"); check_dev_f32(pe, "pe");
-    TORCH_CHECK(sv.dim() >= 2 && pv.numel() == sv.numel() && pe.numel() == sv.numel(), "solar_vis, pv_exact and pe must be [Rs, S(, 1)] tensors of one size");
-    const int64_t Rs = sv.size(0), S = sv.numel() / Rs;
-    TORCH_CHECK(world >= 1, "world must be >= 1");
-    c10::hip::HIPGuardMasqueradingAsCUDA g(rgb.device());
-    Tensor scratch = loss_scratch(rgb);
-    Tensor vals = at::empty({5}, rgb.options()), minv = at::empty({6}, rgb.options());
-    ck(snerf_loss_terms_forward(R, Rs, (int)S, fptr(rgb), fptr(gt), fptr(albedo), fptr(sky), fptr(sv), fptr(pv), fptr(pe), optptr(alb_min_global, "albedo_min_global", 3),
-                                (int)world, scratch.data_ptr(), mptr(vals), mptr(minv), cur_stream(rgb)), "loss_terms");
-    return {vals, minv};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor> loss_terms_bwd(const Tensor& g_vals, const Tensor& rgb, const Tensor& gt, const Tensor& albedo, const Tensor& sky,
-                                                          const Tensor& sv, const Tensor& pv, const Tensor& minv, int64_t world) {
-    check_shape(rgb, "rgb", -1, 3);
-    const int64_t R = rgb.size(0);
-    check_shape(gt, "gt", R, 3); check_shape(albedo, "albedo", R, 3); check_shape(sky, "sky", R, 3);
-    check_dev_f32(sv, "solar_vis"); check_dev_f32(pv, "pv_exact"); check_dev_f32(g_vals, "g_vals"); check_dev_f32(minv, "min");
-    TORCH_CHECK(g_vals.numel() == 5 && minv.numel() == 6 && pv.numel() == sv.numel() && sv.dim() >= 2, "g_vals [5], min [6], pv_exact like solar_vis");
-    const int64_t Rs = sv.size(0), S = sv.numel() / Rs;
-    c10::hip::HIPGuardMasqueradingAsCUDA g(rgb.device());
-    Tensor d_rgb = at::empty_like(rgb), d_alb = at::empty_like(albedo), d_sky = at::empty_like(sky), d_sv = at::empty_like(sv);
-    ck(snerf_loss_terms_backward(R, Rs, (int)S, fptr(rgb), fptr(gt), fptr(albedo), fptr(sky), fptr(sv), fptr(pv), fptr(minv), (int)world, fptr(g_vals),
-                                 mptr(d_rgb), mptr(d_alb), mptr(d_sky), mptr(d_sv), cur_stream(rgb)), "loss_terms_bwd");
-    return {d_rgb, d_alb, d_sky, d_sv};
-}
-
-// ---- the loss terms of the adaptive colour loss and / or the DSM-prior phase (snerf_loss_all_*): values, their weight vector, what the backward needs ----
+// ---- scalar loss terms of a training step (get_loss, Eval_Tools_2.py:340-450; snerf_loss_all_*): values, their weight vector, what the backward needs ----
 struct LossAllIn {
     const Tensor &rgb, &gt, &albedo, &sky, &sv, &pv, &pe_sun;
     const c10::optional<Tensor> &rgb_merged, &pe, &pe_sup, &alpha_c, &scale_c, &alpha_a, &scale_a, &logz_v, &logz_s, &alb_min_global;
@@ -662,7 +614,7 @@ static snerf_loss_in loss_all_in(const LossAllIn& t, int64_t world, int64_t flag
     TORCH_CHECK(t.sv.dim() >= 2 && t.pv.numel() == t.sv.numel() && t.pe_sun.numel() == t.sv.numel(), "solar_vis, pv_exact and pe_solar must be [Rs, S(, 1)] tensors of one size");
     const int64_t Rs = t.sv.size(0), S = t.sv.numel() / Rs;
     TORCH_CHECK(world >= 1, "world must be >= 1");
-    TORCH_CHECK(flags >= 1 && flags <= 7 && (flags & 3), "flags must select the adaptive colour loss (1) and / or the prior phase (2)");
+    TORCH_CHECK(flags >= 0 && flags <= 7, "flags must combine the adaptive colour loss (1), the prior phase (2) and a detached sky term (4)");
     const bool ada = flags & SNERF_LOSS_ADAPTIVE, prior = flags & SNERF_LOSS_PRIOR;
     TORCH_CHECK(!ada || (t.alpha_c.has_value() && t.scale_c.has_value() && (!with_table || (t.logz_v.has_value() && t.logz_s.has_value()))), "the adaptive colour loss needs alpha_color, scale_color, logz_value, logz_slope");
     TORCH_CHECK(!prior || (t.pe.has_value() && t.pe_sup.has_value()), "the prior phase needs pe and pe_supervised");
@@ -811,10 +763,6 @@ TORCH_LIBRARY(season_nerf, m) {
           "Tensor(f!)? time_encoded, Tensor(g!)? sample_weight, Tensor(h!)? gt_color, Tensor(i!)? row_index, Tensor(j!)? sc_top, Tensor(k!)? sc_bot) -> ()");
     m.def("step_inputs_draw(int handle, Tensor table, Tensor(a!)? starts, Tensor(b!)? ends, Tensor(c!)? vec, Tensor(d!)? times, Tensor? base, Tensor(e!)? tv_image, "
           "Tensor(f!)? tv_solar, Tensor(g!)? hyper, Tensor(h!)? trust, Tensor(i!)? lr2) -> ()");
-    m.def("loss_terms(Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor pe, Tensor? albedo_min_global, int world) "
-          "-> (Tensor, Tensor)");
-    m.def("loss_terms_bwd(Tensor g_vals, Tensor rgb, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor min, int world) "
-          "-> (Tensor, Tensor, Tensor, Tensor)");
     m.def("loss_terms_all(Tensor rgb, Tensor? rgb_merged, Tensor gt, Tensor albedo, Tensor sky, Tensor solar_vis, Tensor pv_exact, Tensor pe_solar, Tensor? pe, "
           "Tensor? pe_supervised, Tensor? alpha_color, Tensor? scale_color, Tensor? alpha_alpha, Tensor? scale_alpha, Tensor? logz_value, Tensor? logz_slope, "
           "Tensor? albedo_min_global, int world, int flags, float w_solar, float w_color, float w_alpha) -> (Tensor, Tensor, Tensor)");
@@ -850,8 +798,6 @@ TORCH_LIBRARY_IMPL(season_nerf, CUDA, m) {      // "CUDA" is the dispatch key of
     m.impl("loss_scratch_prepare", loss_scratch_prepare);
     m.impl("loader_next", loader_next);
     m.impl("step_inputs_draw", step_inputs_draw);
-    m.impl("loss_terms", loss_terms);
-    m.impl("loss_terms_bwd", loss_terms_bwd);
     m.impl("loss_terms_all", loss_terms_all);
     m.impl("loss_terms_all_bwd", loss_terms_all_bwd);
     m.impl("fused_adam_", fused_adam_);

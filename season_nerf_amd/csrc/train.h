@@ -247,31 +247,19 @@ hipError_t launch_round_bf16(float* p, int64_t ld, int64_t M, int C, hipStream_t
 // broadcast per-group rows [G,C] to per-point rows [G*S, C] and the transposed reduction
 hipError_t launch_bcast_rows(const float* src, int C, float* dst, int64_t ld_dst, int col0, int64_t n, int n_samples, hipStream_t st);
 hipError_t launch_reduce_rows(const float* src, int64_t ld_src, int col0, int C, float* dst, int64_t n_groups, int n_samples, hipStream_t st);
-// the scalar loss terms of get_loss (MSE colour loss, solar rays, default solar model, no prior) and their gradients (train_kernels.hip)
-struct LossArgs {
-    int64_t R, Rs;                             // image rays, sun rays
-    int S;
-    const float *rgb, *gt, *albedo, *sky;      // [R,3] each (sky: per ray, after the sigmoid)
-    const float *sv, *pv, *pe;                 // sun-ray pass [Rs,S]: Solar_Vis, PV_Exact, PE
-    const float* alb_min_in;                   // optional [3]: the albedo minimum over the GLOBAL batch (data parallel); NULL: the local one
-    int world;                                 // ranks the global batch spans (1 without alb_min_in)
-};
-hipError_t launch_loss_scratch_init(void* scratch, hipStream_t st);
-hipError_t launch_loss_terms(const LossArgs& a, void* scratch, float* vals5, float* minv3, hipStream_t st);
-hipError_t launch_loss_terms_bwd(const LossArgs& a, const float* g5, const float* minv3, float* d_rgb, float* d_albedo, float* d_sky, float* d_sv, hipStream_t st);
-// the same terms for Barron's adaptive colour loss and / or the DSM-prior phase (default solar model), with the weight vector and the gradients of the loss
-// objects' alpha and scale (train_kernels.hip, snerf_loss_all_* of include/season_nerf_hip.h)
+// the scalar loss terms of get_loss (solar rays, default solar model) and their gradients: MSE or Barron's adaptive colour loss, without or with the
+// DSM-prior phase, with the weight vector and the gradients of the loss objects' alpha and scale (train_kernels.hip, snerf_loss_all_* of include/season_nerf_hip.h)
 constexpr int kLossAdaptive = 1, kLossPrior = 2, kLossSkyDetached = 4;
 struct LossAllArgs {
-    int64_t R, Rs;
+    int64_t R, Rs;                                          // image rays, sun rays
     int S, flags;
-    const float *rgb, *rgb_merged, *gt, *albedo, *sky;      // [R,3]; rgb_merged optional: what `Color` is formed on
+    const float *rgb, *rgb_merged, *gt, *albedo, *sky;      // [R,3] (sky: per ray, after the sigmoid); rgb_merged optional: what `Color` is formed on
     const float *sv, *pv, *pe_sun;                          // sun-ray pass [Rs,S]
     const float *pe, *pe_sup;                               // prior: PE, PE_Supervised of the image rays [R,S]
     const float *alpha_c, *scale_c, *alpha_a, *scale_a;     // adaptive: the colour loss object's alpha / scale [3]; adaptive + prior: the alpha loss object's [1]
     const double *logz_v, *logz_s;                          // adaptive: log Z table, values and slopes [513], float64 (see ada_logz)
-    const float* alb_min_in;
-    int world;
+    const float* alb_min_in;                                // optional [3]: the albedo minimum over the GLOBAL batch (data parallel); NULL: the local one
+    int world;                                              // ranks the global batch spans (1 without alb_min_in)
     float w_sc, w_color, w_alpha;                           // weights of the Solar_Correction family, Color / Color_ada, Alpha_Adjust / Alpha_Adjust_ada
 };
 struct LossAllIdx { int sc, sc2, sky, alb, aa_ada, c_ada, c_alpha, c_width, aa, a_alpha, a_width, color, n; };      // position of each term in the value vector (-1: absent)

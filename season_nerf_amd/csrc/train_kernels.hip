@@ -1241,148 +1241,18 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, 
     return hipGetLastError();
 }
 
-// ---- the scalar loss terms of a training step in three launches (get_loss, Eval_Tools_2.py:340-420: MSE colour loss, solar rays on, default solar
-// model, no DSM prior).  The reference forms them with ~45 small tensor ops (and as many again in autograd's backward): ~110 launches of 3-5 us
-// each per step here, a tenth of a step in launch gaps alone.  scratch: 4 doubles (sums) + 3 64-bit keys per block of the partial kernel (albedo minima: float bits << 32 | row; at most 1024 blocks);
-// self-cleaning - the finalize kernel leaves it in its initial state (sums 0, minima +inf), loss_scratch_init sets that state once.
-// mins: 64-bit keys (albedo as float bits << 32 | row): the minimum AND the lowest row that attains it in one comparison - torch.min(albedo, 0)
-// hands its gradient to ONE row (ADVICE r4: with ties - a saturated albedo - every tied row used to receive it)
-constexpr unsigned long long kMinInit = 0x7f800000ffffffffull;
-__global__ void loss_scratch_init_kernel(double* sums, unsigned long long* mins) {
-    if (threadIdx.x < 4) sums[threadIdx.x] = 0.0;
-    (void)mins;
-}
-__global__ __launch_bounds__(256) void loss_partial_kernel(const LossArgs A, double* sums, unsigned long long* mins) {
-    float color = 0.f, sk = 0.f, sc = 0.f, ab = 0.f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    // rows, not elements: a thread sees all three channels of its rays, so the channel minima reduce in registers and the wave (one atomic per
-    // wave and channel: thousands of atomics on three addresses cost 85 us when every element issued its own)
-    unsigned long long mn[3] = {kMinInit, kMinInit, kMinInit};
-    for (int64_t rr = t0; rr < A.R; rr += stride) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int64_t i = rr * 3 + c;
-            const float d = A.rgb[i] - A.gt[i];
-            color += d * d;
-            const float x = (A.sky[i] - .5f) / .5f;
-            if (x > 0.f) sk += x * x;
-            // non-negative floats order as their bits; the row in the low half breaks ties towards the lowest row
-            const unsigned long long key = ((unsigned long long)__float_as_uint(fmaxf(A.albedo[i], 0.f)) << 32) | (unsigned long long)(unsigned)rr;
-            mn[c] = key < mn[c] ? key : mn[c];
-        }
-    }
-    // per-block minima, no atomics (a 64-bit atomicMin under contention - 12 288 of them on three addresses - cost the step 6 ms: measured 20.2 against
-    // 13.8 ms): wave reduction, the four waves through LDS, one plain store per block and channel; loss_finalize_kernel reduces the blocks
-    __shared__ unsigned long long bmin[3][4];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        unsigned long long v = mn[c];
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long w = __shfl_xor(v, o);
-            v = w < v ? w : v;
-        }
-        if ((threadIdx.x & 63) == 0) bmin[c][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long v = bmin[threadIdx.x][0];
-        for (int k = 1; k < 4; ++k) v = bmin[threadIdx.x][k] < v ? bmin[threadIdx.x][k] : v;
-        mins[(size_t)blockIdx.x * 3 + threadIdx.x] = v;
-    }
-    for (int64_t j = t0; j < A.Rs * A.S; j += stride) {
-        const float v = A.sv[j], p = A.pv[j], d = v - p;
-        sc += d * d;
-        ab += A.pe[j] * p * v;
-    }
-    __shared__ float red[4][4];
-    float vals[4] = {sc, ab, sk, color};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float v = vals[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) atomicAdd(sums + threadIdx.x, (double)red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
-}
-// minv [6]: the three minima the Albedo_Color term used, then (as int bits) the row that owns each one on THIS rank (-1: the global minimum lives elsewhere)
-__global__ void loss_finalize_kernel(const LossArgs A, double* sums, unsigned long long* mins, int nblocks, float* vals, float* minv) {
-    // one wave: the per-block minima of the partial kernel (3 keys per block) reduced by 64 lanes, then lane 0 writes the terms
-    unsigned long long key[3] = {kMinInit, kMinInit, kMinInit};
-    for (int b = threadIdx.x; b < nblocks; b += 64)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) key[c] = mins[(size_t)b * 3 + c] < key[c] ? mins[(size_t)b * 3 + c] : key[c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long w = __shfl_xor(key[c], o);
-            key[c] = w < key[c] ? w : key[c];
-        }
-    if (threadIdx.x != 0) return;
-    const double Rs = (double)A.Rs, R = (double)A.R;
-    vals[0] = (float)(sums[0] / Rs);                          // Solar_Correction   = mean_r sum_s (Solar_Vis - PV_Exact)^2      (:361)
-    vals[1] = (float)(1.0 - sums[1] / Rs);                    // Solar_Correction_2 = mean_r (1 - sum_s PE PV_Exact Solar_Vis)  (:366, detached)
-    vals[2] = (float)(sums[2] / (3.0 * R));                   // Sky_Color_Var      = sum_{x > 0} x^2 / numel over [R, S, 3]: S copies of each ray's sky (:381-388)
-    float h = 0.f;
-    for (int c = 0; c < 3; ++c) {
-        const float local = __uint_as_float((unsigned)(key[c] >> 32));
-        const float a = A.alb_min_in ? A.alb_min_in[c] : local;
-        minv[c] = a;
-        minv[3 + c] = __int_as_float(local == a ? (int)(unsigned)(key[c] & 0xffffffffull) : -1);
-        if (a < .2f) { const float u = 1.f - a / .2f; h += u * u; }
-    }
-    vals[3] = h / (float)(R * A.world);                       // Albedo_Color       = sum_c [a_c < .2] (1 - a_c / .2)^2 / R, a = min over the batch (:374-379)
-    vals[4] = (float)(sums[3] / (3.0 * R));                   // Color              = MSE(Rendered_Col, GT_Color)                (:413)
-    for (int k = 0; k < 4; ++k) sums[k] = 0.0;      // (the per-block minima are rewritten by every launch)
-}
-__global__ __launch_bounds__(256) void loss_bwd_kernel(const LossArgs A, const float* g, const float* minv, float* d_rgb, float* d_albedo, float* d_sky,
-                                                       float* d_sv) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    const float g_sc = g[0], g_sk = g[2], g_al = g[3], g_col = g[4];
-    const float inv3r = 1.f / (3.f * (float)A.R), invr = 1.f / (float)A.R, invrs = 1.f / (float)A.Rs;
-    for (int64_t i = t0; i < A.R * 3; i += stride) {
-        d_rgb[i] = g_col * 2.f * (A.rgb[i] - A.gt[i]) * inv3r;
-        const float x = (A.sky[i] - .5f) / .5f;
-        d_sky[i] = x > 0.f ? g_sk * 4.f * x * inv3r : 0.f;                              // d x^2 / d sky = 2 x / .5
-        const float a = minv[i % 3];
-        const int own = __float_as_int(minv[3 + i % 3]);
-        // the minimum's gradient goes to the ONE row that attains it - the lowest such row, as torch.min(albedo, 0) (on the rank that owns the global
-        // minimum, divided by the LOCAL ray count: the rank average of the gradients is then the global-batch gradient, training.albedo_min_loss)
-        d_albedo[i] = ((int)(i / 3) == own && a < .2f) ? g_al * 2.f * (1.f - a / .2f) * (-1.f / .2f) * invr : 0.f;
-    }
-    for (int64_t j = t0; j < A.Rs * A.S; j += stride) d_sv[j] = g_sc * 2.f * (A.sv[j] - A.pv[j]) * invrs;
-}
-hipError_t launch_loss_scratch_init(void* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(loss_scratch_init_kernel, dim3(1), dim3(64), 0, st, (double*)scratch, (unsigned long long*)((double*)scratch + 4));
-    return hipGetLastError();
-}
-hipError_t launch_loss_terms(const LossArgs& a, void* scratch, float* vals, float* minv, hipStream_t st) {
-    double* sums = (double*)scratch;
-    unsigned long long* mins = (unsigned long long*)(sums + 4);
-    int64_t n = a.Rs * a.S > a.R * 3 ? a.Rs * a.S : a.R * 3;
-    int64_t b = (n + 255) / 256;
-    if (b > 1024) b = 1024;
-    if (b < 1) b = 1;
-    hipLaunchKernelGGL(loss_partial_kernel, dim3((unsigned)b), dim3(256), 0, st, a, sums, mins);
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, a, sums, mins, (int)b, vals, minv);
-    return hipGetLastError();
-}
-hipError_t launch_loss_terms_bwd(const LossArgs& a, const float* g, const float* minv, float* d_rgb, float* d_albedo, float* d_sky, float* d_sv, hipStream_t st) {
-    int64_t n = a.Rs * a.S > a.R * 3 ? a.Rs * a.S : a.R * 3;
-    int64_t b = (n + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)b), dim3(256), 0, st, a, g, minv, d_rgb, d_albedo, d_sky, d_sv);
-    return hipGetLastError();
-}
-
-// ---- the loss terms of the configurations the three kernels above do not serve: Barron's adaptive colour loss (Eval_Tools_2.py:421-450) and the DSM-prior
-// phase (:243, :391-412), default solar model.  Same three launches - partial sums per block, one finalize wave, one elementwise backward - with two changes:
+// ---- the scalar loss terms of a training step in three launches (get_loss, Eval_Tools_2.py:340-450, solar rays on, default solar model): the MSE colour
+// loss (:413) or Barron's adaptive colour loss (:421-450), without or with the DSM-prior phase (:243, :391-412) - flags selects.  The reference forms them
+// with ~45 small tensor ops (and as many again in autograd's backward): ~110 launches of 3-5 us each per step here, a tenth of a step in launch gaps
+// alone.  Partial sums per block, one finalize wave, one elementwise backward:
 //   * no floating-point atomics: every block STORES its sums (kLossAllSums doubles) and its three albedo keys, the finalize wave adds the blocks in a fixed
 //     order (lane l takes blocks l, l + 64, ...; then the shuffle tree) - the values are the same bits from launch to launch, and the scratch needs no
 //     initial state (every slot the finalize reads was written by the partial pass of the same call);
 //   * besides the sums of the terms, per channel of a loss object the sums of rho, d rho / d alpha and d rho / d scale: the gradients with respect to the
 //     loss object's alpha and scale are then saved sums times the upstream gradient (aux, written by the finalize), O(1) in the backward.
+// mins: 64-bit keys (albedo as float bits << 32 | row): the minimum AND the lowest row that attains it in one comparison - torch.min(albedo, 0)
+// hands its gradient to ONE row (with ties - a saturated albedo - every tied row used to receive it)
+constexpr unsigned long long kMinInit = 0x7f800000ffffffffull;
 // nll(x) = rho(x, alpha, c) + log c + log Z(alpha) as adaptive_loss.py states it: z = (x / c)^2, b = |alpha - 2| + eps, d = alpha +- eps,
 // rho = (b / d) ((z / b + 1)^(d / 2) - 1).  b, d and sign(alpha - 2) are formed in float32 from the float32 alpha the caller's torch ops formed, with the very
 // operations torch applies (the loss is logarithmically singular in alpha at 2: one ulp of b there moves d rho / d alpha by 10 %); everything per element
@@ -1432,6 +1302,9 @@ __device__ inline void ada_logz(float alpha_f, const double* v, const double* s,
 // sums per block: 0 Solar_Correction, 1 absorbed, 2 sky, 3 colour squared difference, 4-6 / 7-9 / 10-12 colour rho / d alpha / d c per channel,
 // 13 alpha squared difference, 14 / 15 / 16 alpha rho / d alpha / d c
 constexpr int kLossAllSums = 17, kLossAllMaxBlocks = 1024;
+// the sums a configuration reduces, stores and re-reads: the first four in the MSE free phase (the others stay zero there and nothing reads them) - a bound
+// that is uniform over the launch, tested inside the unrolled loops so that they keep their static register indices (profiles/r23: what it buys the forward pair)
+__device__ inline int loss_all_sums(int flags) { return (flags & (kLossAdaptive | kLossPrior)) ? kLossAllSums : 4; }
 size_t loss_all_scratch_bytes() { return (size_t)kLossAllMaxBlocks * (kLossAllSums * sizeof(double) + 3 * sizeof(unsigned long long)); }
 __global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs A, double* sums, unsigned long long* mins) {
     const bool ada = A.flags & kLossAdaptive, prior = A.flags & kLossPrior;
@@ -1444,6 +1317,7 @@ __global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs
     for (int k = 0; k < kLossAllSums; ++k) acc[k] = 0.0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const float* col = A.rgb_merged ? A.rgb_merged : A.rgb;       // `Color`: the merged colour in the prior phase in train mode (:413, :450)
+    // rows, not elements: a thread sees all three channels of its rays, so the channel minima reduce in registers and the wave
     unsigned long long mn[3] = {kMinInit, kMinInit, kMinInit};
     for (int64_t rr = t0; rr < A.R; rr += stride) {
 #pragma unroll
@@ -1453,6 +1327,7 @@ __global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs
             acc[3] += (double)(d * d);
             const float x = (A.sky[i] - .5f) / .5f;
             if (x > 0.f) acc[2] += (double)(x * x);
+            // non-negative floats order as their bits; the row in the low half breaks ties towards the lowest row
             const unsigned long long key = ((unsigned long long)__float_as_uint(fmaxf(A.albedo[i], 0.f)) << 32) | (unsigned long long)(unsigned)rr;
             mn[c] = key < mn[c] ? key : mn[c];
             if (ada) {                                             // the adaptive loss sees the un-merged colour (:422)
@@ -1462,6 +1337,8 @@ __global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs
             }
         }
     }
+    // per-block minima, no atomics (a 64-bit atomicMin under contention - 12 288 of them on three addresses - cost the step 6 ms: measured 20.2 against
+    // 13.8 ms): wave reduction, the four waves through LDS, one plain store per block and channel; loss_all_finalize_kernel reduces the blocks
     __shared__ unsigned long long bmin[3][4];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -1487,12 +1364,15 @@ __global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs
                 acc[14] += rho; acc[15] += da; acc[16] += dc;
             }
         }
+    const int nsum = loss_all_sums(A.flags);
     __shared__ double red[kLossAllSums][4];
 #pragma unroll
     for (int k = 0; k < kLossAllSums; ++k) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
+        if (k < nsum) {
+            double v = acc[k];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+            if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
+        }
     }
     __syncthreads();
     if (threadIdx.x < 3) {
@@ -1500,21 +1380,25 @@ __global__ __launch_bounds__(256) void loss_all_partial_kernel(const LossAllArgs
         for (int k = 1; k < 4; ++k) v = bmin[threadIdx.x][k] < v ? bmin[threadIdx.x][k] : v;
         mins[(size_t)blockIdx.x * 3 + threadIdx.x] = v;
     }
-    if (threadIdx.x < kLossAllSums)
+    if (threadIdx.x < nsum)
         sums[(size_t)blockIdx.x * kLossAllSums + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
 }
-// aux [14]: the three albedo minima, the rows that own them (int bits; as loss_finalize_kernel), then d term / d alpha and d term / d scale of the colour
-// loss object per channel (6) and of the alpha loss object (2): what loss_all_bwd_kernel multiplies with the upstream gradients
+// aux [14]: the three minima the Albedo_Color term used, then (as int bits) the row that owns each one on THIS rank (-1: the global minimum lives
+// elsewhere), then d term / d alpha and d term / d scale of the colour loss object per channel (6) and of the alpha loss object (2): what
+// loss_all_bwd_kernel multiplies with the upstream gradients (zeros without the adaptive loss)
+// one wave: the per-block sums and minima of the partial kernel reduced by 64 lanes, then lane 0 writes the terms
 __global__ void loss_all_finalize_kernel(const LossAllArgs A, const double* sums, const unsigned long long* mins, int nblocks, float* vals, float* wts, float* aux) {
     unsigned long long key[3] = {kMinInit, kMinInit, kMinInit};
     double s[kLossAllSums];
 #pragma unroll
     for (int k = 0; k < kLossAllSums; ++k) s[k] = 0.0;
+    const int nsum = loss_all_sums(A.flags);
     for (int b = threadIdx.x; b < nblocks; b += 64) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) key[c] = mins[(size_t)b * 3 + c] < key[c] ? mins[(size_t)b * 3 + c] : key[c];
 #pragma unroll
-        for (int k = 0; k < kLossAllSums; ++k) s[k] += sums[(size_t)b * kLossAllSums + k];
+        for (int k = 0; k < kLossAllSums; ++k)
+            if (k < nsum) s[k] += sums[(size_t)b * kLossAllSums + k];
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -1524,15 +1408,16 @@ __global__ void loss_all_finalize_kernel(const LossAllArgs A, const double* sums
         }
 #pragma unroll
     for (int k = 0; k < kLossAllSums; ++k)
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);
+        if (k < nsum)
+            for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);
     if (threadIdx.x != 0) return;
     const bool ada = A.flags & kLossAdaptive, prior = A.flags & kLossPrior;
     const LossAllIdx I = loss_all_idx(A.flags);
     const double Rs = (double)A.Rs, R = (double)A.R, RS = R * (double)A.S;
     for (int k = 0; k < 14; ++k) aux[k] = 0.f;
-    vals[I.sc] = (float)(s[0] / Rs);
-    vals[I.sc2] = (float)(1.0 - s[1] / Rs);
-    vals[I.sky] = (float)(s[2] / (3.0 * R));
+    vals[I.sc] = (float)(s[0] / Rs);                          // Solar_Correction   = mean_r sum_s (Solar_Vis - PV_Exact)^2      (:361)
+    vals[I.sc2] = (float)(1.0 - s[1] / Rs);                   // Solar_Correction_2 = mean_r (1 - sum_s PE PV_Exact Solar_Vis)  (:366, detached)
+    vals[I.sky] = (float)(s[2] / (3.0 * R));                  // Sky_Color_Var      = sum_{x > 0} x^2 / numel over [R, S, 3]: S copies of each ray's sky (:381-388)
     float hsum = 0.f;
     for (int c = 0; c < 3; ++c) {
         const float local = __uint_as_float((unsigned)(key[c] >> 32));
@@ -1541,8 +1426,8 @@ __global__ void loss_all_finalize_kernel(const LossAllArgs A, const double* sums
         aux[3 + c] = __int_as_float(local == a ? (int)(unsigned)(key[c] & 0xffffffffull) : -1);
         if (a < .2f) { const float u = 1.f - a / .2f; hsum += u * u; }
     }
-    vals[I.alb] = hsum / (float)(R * A.world);
-    vals[I.color] = (float)(s[3] / (3.0 * R));
+    vals[I.alb] = hsum / (float)(R * A.world);                // Albedo_Color       = sum_c [a_c < .2] (1 - a_c / .2)^2 / R, a = min over the batch (:374-379)
+    vals[I.color] = (float)(s[3] / (3.0 * R));                // Color              = MSE(Rendered_Col, GT_Color)                (:413)
     float w_sc = A.w_sc;
     for (int k = 0; k < I.n; ++k) wts[k] = 1.f;                  // the mean alpha / scale entries: logged values, weight 1 (:431-447)
     if (ada) {
@@ -1614,9 +1499,11 @@ __global__ __launch_bounds__(256) void loss_all_bwd_kernel(const LossAllArgs A, 
         if (ada) d_rgb += (float)(g_cada * ada_dx(P[c], (double)A.rgb[i] - (double)gt) * inv3r_d);
         G.d_rgb[i] = d_rgb;
         const float x = (A.sky[i] - .5f) / .5f;
-        G.d_sky[i] = x > 0.f ? g_sk * 4.f * x * inv3r : 0.f;
+        G.d_sky[i] = x > 0.f ? g_sk * 4.f * x * inv3r : 0.f;                              // d x^2 / d sky = 2 x / .5
         const float a = aux[c];
         const int own = __float_as_int(aux[3 + c]);
+        // the minimum's gradient goes to the ONE row that attains it - the lowest such row, as torch.min(albedo, 0) (on the rank that owns the global
+        // minimum, divided by the LOCAL ray count: the rank average of the gradients is then the global-batch gradient, training.albedo_min_loss)
         G.d_albedo[i] = ((int)(i / 3) == own && a < .2f) ? g_al * 2.f * (1.f - a / .2f) * (-1.f / .2f) * invr : 0.f;
     }
     for (int64_t j = t0; j < A.Rs * A.S; j += stride) G.d_sv[j] = g_sc * 2.f * (A.sv[j] - A.pv[j]) * invrs;

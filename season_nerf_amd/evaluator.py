@@ -58,8 +58,8 @@ def sample_parameters_on(dev, n_samples, eval_mode, include_end_pt=False):
 
 
 class All_in_One_Eval:
-    # which configurations form their loss terms in fused kernels: "default" - the MSE colour loss without the DSM prior (season_nerf::loss_terms); "all" -
-    # also Barron's adaptive colour loss and the DSM-prior phase (season_nerf::loss_terms_all).  SNERF_FUSED_LOSS=0 turns every fused path off.
+    # which configurations form their loss terms in the fused kernels (season_nerf::loss_terms_all): "default" - the MSE colour loss without the DSM prior;
+    # "all" - also Barron's adaptive colour loss and the DSM-prior phase.  SNERF_FUSED_LOSS=0 turns every fused path off.
     fused_loss = "default"
 
     def __init__(self, args, device, n_steps, use_prior, ada_loss, H, WC, base_solar_vecs=None):

@@ -103,18 +103,10 @@ def _register_fakes():
     def _(handle, table, starts, ends, vec, times, base, tv_image, tv_solar, hyper, trust, lr2):
         return None
 
-    @reg("season_nerf::loss_terms")
-    def _(rgb, gt, albedo, sky, solar_vis, pv_exact, pe, albedo_min_global, world):
-        return rgb.new_empty(5), rgb.new_empty(6)
-
-    @reg("season_nerf::loss_terms_bwd")
-    def _(g_vals, rgb, gt, albedo, sky, solar_vis, pv_exact, min, world):
-        return torch.empty_like(rgb), torch.empty_like(albedo), torch.empty_like(sky), torch.empty_like(solar_vis)
-
     @reg("season_nerf::loss_terms_all")
     def _(rgb, rgb_merged, gt, albedo, sky, solar_vis, pv_exact, pe_solar, pe, pe_supervised, alpha_color, scale_color, alpha_alpha, scale_alpha, logz_value,
           logz_slope, albedo_min_global, world, flags, w_solar, w_color, w_alpha):
-        n = {1: 8, 3: 12, 2: 6}[flags & 3]
+        n = {0: 5, 1: 8, 3: 12, 2: 6}[flags & 3]
         return rgb.new_empty(n), rgb.new_empty(n), rgb.new_empty(14)
 
     @reg("season_nerf::loss_terms_all_bwd")

@@ -370,7 +370,7 @@ class GraphedTrainStep:
             self.graph = torch.cuda.CUDAGraph()
             import os
             ctx = torch.cuda.graph(self.graph)           # torch's own capture stream
-            # The loss kernels' reduction scratch is keyed by stream (csrc/ops.cpp): create the capture stream's one NOW, on that stream, so that the capture
+            # The loss kernels' block-sum scratch is keyed by stream (csrc/ops.cpp; no initial state to set): create the capture stream's one NOW, so that the capture
             # allocates nothing and the scratch does not pin a block of this graph's private pool after the graph is gone.  Round 6 first tried this
             # while the engine still issued hipMemcpyAsync / hipMemsetAsync inside the step and found that ANY event wait between the current stream and another in
             # front of a process's second capture made the new graph's replays drift (tools/graph_wait_probe.py: 3-4 runs of 6 for the variants below) - one more face

@@ -330,16 +330,6 @@ def _register_autograd():
             ops.train_bwd_solar(ctx.trainer, eng.grads, g[0])
         return ctx.no_grads
 
-    def setup_loss(ctx, inputs, output):
-        rgb, gt, albedo, sky, sv, pv, pe, alb_min_global, world = inputs
-        ctx.save_for_backward(rgb, gt, albedo, sky, sv, pv, output[1])
-        ctx.world = int(world)
-
-    def bwd_loss(ctx, g_vals, g_min):
-        rgb, gt, albedo, sky, sv, pv, minv = ctx.saved_tensors
-        d_rgb, d_alb, d_sky, d_sv = ops.loss_terms_bwd(g_vals.contiguous(), rgb, gt, albedo, sky, sv, pv, minv, ctx.world)
-        return d_rgb, None, d_alb, d_sky, d_sv, None, None, None, None
-
     def setup_loss_all(ctx, inputs, output):
         rgb, rgb_m, gt, albedo, sky, sv, pv, pe_sun, pe, pe_sup, a_c, s_c, a_a, s_a = inputs[:14]
         ctx.save_for_backward(rgb, rgb_m, gt, albedo, sky, sv, pv, pe, pe_sup, a_c, s_c, a_a, s_a, output[2])
@@ -354,7 +344,6 @@ def _register_autograd():
         return (d[0], on(d[1], t[1] is not None and not ada), None, d[2], on(d[3], not sky_detached), d[4], None, None, on(d[5], prior), None,
                 on(d[6], ada), on(d[7], ada), on(d[8], ada and prior), on(d[9], ada and prior), None, None, None, None, None, None, None, None)
 
-    torch.library.register_autograd("season_nerf::loss_terms", bwd_loss, setup_context=setup_loss)
     torch.library.register_autograd("season_nerf::loss_terms_all", bwd_loss_all, setup_context=setup_loss_all)
     torch.library.register_autograd("season_nerf::train_fwd_image", bwd_image, setup_context=setup_image)
     torch.library.register_autograd("season_nerf::train_fwd_points", bwd_points, setup_context=setup_points)
@@ -515,7 +504,7 @@ class LossDict(dict):
     instead of one multiply and one add per term (trainer.Net_tool.train_step)."""
     vec = None
     names = ()
-    wvec = None            # the weights as a device vector next to `vec` (season_nerf::loss_terms_all: two of them depend on the loss object's scale)
+    wvec = None            # the weights as a device vector next to `vec` (two of them depend on the adaptive loss object's scale); None in the MSE free phase
 
     def total(self):
         if self.wvec is not None:
@@ -540,33 +529,8 @@ def _fused_loss_ok(ev, args, out, so):
             and isinstance(out, _TrainOut) and out.sky_ray is not None and out["Rendered_Col"].is_cuda and so["Solar_Vis"].is_cuda)
 
 
-def _fused_loss(ev, net, out, so, gt, weight):
-    """The five terms of the default training configuration from ONE forward op (two launches) and one backward launch
-    (csrc/train_kernels.hip loss_*_kernel) instead of ~45 tensor ops and their autograd graph."""
-    from . import parallel
-    from .network import _ops
-    _register_autograd()
-    ops = _ops()
-    rgb = out["Rendered_Col"]
-    store = getattr(net, "_param_store", None)
-    group = store.bn_sync[0] if (store is not None and store.bn_sync is not None) else None
-    g_min, world = None, 1
-    if parallel.data_parallel(group):          # the reference's minimum runs over the WHOLE batch (:374): one MIN all-reduce of 3 floats
-        g_min, world = parallel.global_min(out["Albedo_Color"].detach().min(0).values, group)
-    vals, _ = ops.loss_terms(rgb, gt.contiguous(), out["Albedo_Color"], out.sky_ray, so["Solar_Vis"], so["PV_Exact"].detach(), so["PE"].detach(), g_min, world)
-    v = vals.unbind(0)
-    w_sc = weight["Solar_Correction"]
-    L = LossDict()
-    L["Solar_Correction"] = [v[0], w_sc]
-    L["Solar_Correction_2"] = [v[1].detach(), w_sc]
-    L["Sky_Color_Var"] = [v[2], w_sc]
-    L["Albedo_Color"] = [v[3], w_sc]
-    L["Color"] = [v[4], weight["Color"]]
-    L.vec, L.names = vals, ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color")
-    return L
-
-
 _ALL_NAMES = {
+    0: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color"),
     1: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color_ada", "Color_alpha", "Color_width", "Color"),
     3: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Alpha_Adjust_ada", "Color_ada", "Color_alpha", "Color_width", "Alpha_Adjust",
         "Alpha_alpha", "Alpha_width", "Color"),
@@ -575,7 +539,7 @@ _ALL_LOGGED = ("Solar_Correction_2", "Color_alpha", "Color_width", "Alpha_alpha"
 
 
 def _fused_loss_all_ok(ev, args, out, so):
-    """The opt-in op (`All_in_One_Eval.fused_loss == "all"`) serves what `_fused_loss_ok` refuses except the classic solar model: Barron's adaptive colour
+    """Opt-in (`All_in_One_Eval.fused_loss == "all"`): the op also serves what `_fused_loss_ok` refuses except the classic solar model: Barron's adaptive colour
     loss and / or the DSM-prior phase.  Everything it cannot take - a loss object with a fixed alpha or scale or of another class, CPU tensors, a missing
     PE_Supervised - stays on the tensor ops."""
     import os
@@ -596,10 +560,11 @@ def _fused_loss_all_ok(ev, args, out, so):
     return True
 
 
-def _fused_loss_all(ev, net, out, so, gt, weight, train_mode):
-    """The terms of the adaptive colour loss and / or the DSM-prior phase from ONE forward op (two launches) and one backward launch (csrc/train_kernels.hip
-    loss_all_*_kernel).  alpha and scale enter as the tensors the loss object's own alpha() / scale() form - the kernel sees the very float32 alpha - and
-    autograd chains their gradients to the latents.  -> LossDict with `vec`, `wvec` and `names`; each entry [value, weight] as the tensor-op path gives it."""
+def _fused_loss(ev, net, out, so, gt, weight, train_mode):
+    """The terms of every fused configuration - MSE or adaptive colour loss, free or DSM-prior phase - from ONE forward op (two launches) and one backward
+    launch (csrc/train_kernels.hip loss_all_*_kernel) instead of ~45 tensor ops and their autograd graph.  alpha and scale enter as the tensors the loss
+    object's own alpha() / scale() form - the kernel sees the very float32 alpha - and autograd chains their gradients to the latents.  -> LossDict with
+    `vec`, `names` and (except in the MSE free phase, whose weights are host numbers) `wvec`; each entry [value, weight] as the tensor-op path gives it."""
     from . import parallel
     from .adaptive_loss import table_on
     from .network import _ops
@@ -610,7 +575,7 @@ def _fused_loss_all(ev, net, out, so, gt, weight, train_mode):
     store = getattr(net, "_param_store", None)
     group = store.bn_sync[0] if (store is not None and store.bn_sync is not None) else None
     g_min, world = None, 1
-    if parallel.data_parallel(group):
+    if parallel.data_parallel(group):          # the reference's minimum runs over the WHOLE batch (:374): one MIN all-reduce of 3 floats
         g_min, world = parallel.global_min(out["Albedo_Color"].detach().min(0).values, group)
     a_c = s_c = a_a = s_a = lz_v = lz_s = None
     if ada:
@@ -624,9 +589,9 @@ def _fused_loss_all(ev, net, out, so, gt, weight, train_mode):
                                       out.sky_ray, so["Solar_Vis"], so["PV_Exact"].detach(), so["PE"].detach(), pe,
                                       out["PE_Supervised"].detach().contiguous() if prior else None, a_c, s_c, a_a, s_a, lz_v, lz_s, g_min, world, flags,
                                       float(weight["Solar_Correction"]), float(weight["Color"]), float(weight["Alpha_Adjust"]))
-    wts = wts.detach()
+    wts = wts.detach() if flags & 3 else None        # the MSE free phase keeps host weights: total() multiplies with its cached vector of them
     names = _ALL_NAMES[flags & 3]
-    v, w = vals.unbind(0), wts.unbind(0)
+    v, w = vals.unbind(0), (wts.unbind(0) if ada else None)
     host_w = {"Sky_Color_Var": weight["Solar_Correction"], "Albedo_Color": weight["Solar_Correction"], "Color": weight["Color"], "Color_ada": weight["Color"],
               "Alpha_Adjust": weight["Alpha_Adjust"], "Alpha_Adjust_ada": weight["Alpha_Adjust"]}
     L = LossDict()
@@ -739,10 +704,8 @@ def get_loss(ev, data_dict, net, current_step, train_mode):
     if args.Use_Solar:
         starts, ends, vec, stime, _ = ev.solar_creation_tool(n_rays, include_times=True)
         so = ev.eval_Rho_Only({"Top": starts, "Bot": ends, "Sun_Angle": vec, "Time_Encoded": stime}, net, train_mode, current_step)
-        if _fused_loss_ok(ev, args, out, so):
-            return _fused_loss(ev, net, out, so, data_dict["GT_Color"].to(dev), weight)
-        if _fused_loss_all_ok(ev, args, out, so):
-            return _fused_loss_all(ev, net, out, so, data_dict["GT_Color"].to(dev), weight, train_mode)
+        if _fused_loss_ok(ev, args, out, so) or _fused_loss_all_ok(ev, args, out, so):
+            return _fused_loss(ev, net, out, so, data_dict["GT_Color"].to(dev), weight, train_mode)
         Loss["Solar_Correction"] = [torch.mean(torch.sum(_sq(so["Solar_Vis"] - so["PV_Exact"].detach()), 1)), weight["Solar_Correction"]]
         absorb = torch.mean(1 - torch.sum(so["PE"].detach() * so["PV_Exact"].detach() * so["Solar_Vis"], 1))
         Loss["Solar_Correction_2"] = [absorb.detach() if not args.Solar_Type_2 else absorb, weight["Solar_Correction"]]

@@ -1,5 +1,5 @@
 """Float64 statements of the loss terms behind snerf_loss_all_forward / _backward (csrc/train_kernels.hip loss_all_*_kernel; season_nerf::loss_terms_all):
-Barron's adaptive colour loss and / or the DSM-prior phase (Eval_Tools_2.py:361-450).  Shared by tests/test_loss_all_refs.py (CPU: the closed forms
+the MSE or Barron's adaptive colour loss, without or with the DSM-prior phase (Eval_Tools_2.py:361-450).  Shared by tests/test_loss_all_refs.py (CPU: the closed forms
 against torch.autograd on season_nerf_amd/adaptive_loss.py, the conditions on the cases) and tests/test_gpu_loss_all.py (the kernels against float64).
 
 Two statements:
@@ -21,8 +21,9 @@ from season_nerf_amd import adaptive_loss as al
 
 EPS = al._EPS
 ADAPTIVE, PRIOR, SKY_DETACHED = 1, 2, 4
-CONFIGS = {"adaptive-free": ADAPTIVE, "adaptive-prior": ADAPTIVE | PRIOR | SKY_DETACHED, "mse-prior": PRIOR | SKY_DETACHED}
-NAMES = {1: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color_ada", "Color_alpha", "Color_width", "Color"),
+CONFIGS = {"mse-free": 0, "adaptive-free": ADAPTIVE, "adaptive-prior": ADAPTIVE | PRIOR | SKY_DETACHED, "mse-prior": PRIOR | SKY_DETACHED}
+NAMES = {0: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color"),
+         1: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color_ada", "Color_alpha", "Color_width", "Color"),
          3: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Alpha_Adjust_ada", "Color_ada", "Color_alpha", "Color_width",
              "Alpha_Adjust", "Alpha_alpha", "Alpha_width", "Color"),
          2: ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color", "Alpha_Adjust")}

@@ -1,7 +1,8 @@
-"""season_nerf::loss_terms_all - the fused loss terms of Barron's adaptive colour loss and / or the DSM-prior phase (csrc/train_kernels.hip
-loss_all_partial_kernel / loss_all_finalize_kernel / loss_all_bwd_kernel) - on the GPU:
+"""season_nerf::loss_terms_all - the fused loss terms of every configuration: MSE or Barron's adaptive colour loss, free or DSM-prior phase
+(csrc/train_kernels.hip loss_all_partial_kernel / loss_all_finalize_kernel / loss_all_bwd_kernel) - on the GPU:
   * the kernels through the C ABI against float64 (tests/loss_all_cases.reference: adaptive_loss.py's own functions and torch.autograd in float64 on the
-    CPU, alpha and scale as leaves), over the alpha set, NaN sentinels around every output, two launches on the same inputs bit for bit;
+    CPU, alpha and scale as leaves), over the alpha set, NaN sentinels around every output, two launches on the same inputs bit for bit, the albedo
+    minima and the rows that own them exactly;
     tolerance train_kernel_cases.tolerance(E_ref, scale) = 4 (E_ref + 2^-24 scale), E_ref = the float32 evaluation of the same reference on these inputs;
   * the op and its registered backward inside a training step against the tensor-op path of get_loss;
   * the captured step under fused_loss="all" against the eager one, its graph's nodes;
@@ -24,7 +25,9 @@ import train_kernel_cases as tk
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WC, H4 = np.array([41.29, -95.9, 300.0]), np.array([[310.0, 12.0, 0.0, -11650.0], [-9.0, 240.0, 0.0, 23390.0], [0.0, 0.0, 0.01, -3.0], [0, 0, 0, 1.0]])
-SIZES = [(1, 1, 1), (257, 131, 7), (5547, 300, 40), (3000, 1000, 96)]      # one ray | odd sizes | > 64 blocks for the finalize wave | R S past the 1024-block cap
+# one ray | odd sizes | > 64 blocks for the finalize wave | R S past the 1024-block cap | the image rays past it (262200 elements) | the sun rays past it
+SIZES = [(1, 1, 1), (257, 131, 7), (5547, 300, 40), (3000, 1000, 96), (87400, 1000, 13), (1000, 10925, 30)]
+SIZE_IDS = ["one-ray", "R257", "blocks-over-64", "RS-over-1024-blocks", "R87400-over-1024-blocks", "sun-rays-over-1024-blocks"]
 PAD = 16
 
 
@@ -50,7 +53,7 @@ def _ratio(err, tol):
 
 
 @pytest.mark.parametrize("config", list(lc.CONFIGS))
-@pytest.mark.parametrize("R,Rs,S", SIZES, ids=["one-ray", "R257", "blocks-over-64", "RS-over-1024-blocks"])
+@pytest.mark.parametrize("R,Rs,S", SIZES, ids=SIZE_IDS)
 def test_loss_all_kernels_against_float64(L, R, Rs, S, config):
     from season_nerf_amd._lib import LossIn, LossGrads
     from season_nerf_amd.adaptive_loss import table_on
@@ -65,7 +68,7 @@ def test_loss_all_kernels_against_float64(L, R, Rs, S, config):
     lz_v, lz_s = table_on("cuda:0", torch.float64)
     g = np.linspace(0.5, 1.5, n).astype(np.float32)
     worst = {}
-    for alpha in (lc.ALPHAS if ada else lc.ALPHAS[:1]):                  # (the MSE prior configuration reads no alpha)
+    for alpha in (lc.ALPHAS if ada else lc.ALPHAS[:1]):                  # (the MSE configurations read no alpha)
         h = lc.make_inputs(f"loss-all-{R}-{Rs}-{S}", R, Rs, S, alpha)
         v64, w64, scale, g64 = lc.reference(h, flags, torch.float64, g)
         v32, w32, _, g32 = lc.reference(h, flags, torch.float32, g)
@@ -103,6 +106,10 @@ def test_loss_all_kernels_against_float64(L, R, Rs, S, config):
                 for a_, b_ in zip(first, bits):
                     assert torch.equal(a_.view(torch.int32), b_.view(torch.int32))
         vals, wts = fb[0][1].cpu().numpy().astype(np.float64), fb[1][1].cpu().numpy().astype(np.float64)
+        aux = fb[2][1].cpu().numpy()
+        np.testing.assert_array_equal(aux[:3], h["albedo"].min(0))                       # the float32 column minima, exactly
+        np.testing.assert_array_equal(aux[3:6].view(np.int32), h["albedo"].argmin(0))    # the lowest row that attains each
+        assert ada or not aux[6:].any()
         for what, got, want, e_ref, sc in (("vals", vals, v64, np.abs(v32 - v64), scale), ("weights", wts, w64, np.abs(w32 - w64), np.abs(w64))):
             tol = tk.tolerance(e_ref, sc)
             err = np.abs(got - want)
@@ -374,8 +381,8 @@ def test_captured_step_under_all_holds_kernel_nodes_only_and_fewer_of_them(tmp_p
 # ------------------------------------------------------------------------------------------------------------------ default behaviour
 def test_default_and_switch_reach_the_code_they_reached(monkeypatch):
     """fused_loss="default" (and the keyword's default) keeps every configuration where it was: the generic dict for the adaptive loss and the prior phase, the
-    five-term op for the MSE free phase - whose loss vector is, bit for bit, what season_nerf::loss_terms gives on the step's tensors, under "all" too; and
-    SNERF_FUSED_LOSS=0 turns every fused path off, "all" included."""
+    fused op for the MSE free phase - whose loss vector is, bit for bit, what season_nerf::loss_terms_all at flags 0 gives on the step's tensors (the sums
+    are reproducible), under "all" too; and SNERF_FUSED_LOSS=0 turns every fused path off, "all" included."""
     import season_nerf_amd as sn
     from season_nerf_amd import training
     from season_nerf_amd.training import LossDict
@@ -395,9 +402,9 @@ def test_default_and_switch_reach_the_code_they_reached(monkeypatch):
     seen = {}
     orig = training._fused_loss
 
-    def spy(ev_, net_, out, so, gt, weight):
-        seen["args"] = (out["Rendered_Col"], gt.contiguous(), out["Albedo_Color"], out.sky_ray, so["Solar_Vis"], so["PV_Exact"].detach(), so["PE"].detach())
-        return orig(ev_, net_, out, so, gt, weight)
+    def spy(ev_, net_, out, so, gt, weight, train_mode):
+        seen["args"] = (out["Rendered_Col"], None, gt.contiguous(), out["Albedo_Color"], out.sky_ray, so["Solar_Vis"], so["PV_Exact"].detach(), so["PE"].detach())
+        return orig(ev_, net_, out, so, gt, weight, train_mode)
 
     monkeypatch.setattr(training, "_fused_loss", spy)
     for mode in ("default", "all"):
@@ -405,7 +412,7 @@ def test_default_and_switch_reach_the_code_they_reached(monkeypatch):
         with torch.no_grad():
             loss = ev.get_loss(data, net, 3, True)
             assert isinstance(loss, LossDict) and loss.wvec is None and loss.names == ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color")
-            want, _ = torch.ops.season_nerf.loss_terms(*seen.pop("args"), None, 1)
+            want = torch.ops.season_nerf.loss_terms_all(*seen.pop("args"), *[None] * 9, 1, 0, 0.03, 1.0, 1.0)[0]
         assert torch.equal(loss.vec.view(torch.int32), want.view(torch.int32))
         monkeypatch.setenv("SNERF_FUSED_LOSS", "0")
         with torch.no_grad():

@@ -257,11 +257,16 @@ def _loss_terms_torch(rgb, gt, albedo, sky, sv, pv, pe, S):
 
 @pytest.mark.parametrize("dark", [True, False])
 def test_fused_loss_terms_vs_tensor_ops(dark):
-    """season_nerf::loss_terms (+ its registered backward) against the same five terms formed with tensor ops and differentiated by
+    """season_nerf::loss_terms_all at flags 0 (+ its registered backward) against the same five terms formed with tensor ops and differentiated by
     autograd: values to fp32 rounding, gradients of a weighted total element by element."""
     ops()
     from season_nerf_amd import training
     training._register_autograd()
+
+    def loss_terms(rgb, gt, albedo, sky, sv, pv, pe, g_min, world):      # the MSE free phase -> (vals [5], aux[:6]: the minima + the rows that own them)
+        vals, _, aux = torch.ops.season_nerf.loss_terms_all(rgb, None, gt, albedo, sky, sv, pv, pe, *[None] * 8, g_min, world, 0, 0.03, 1.0, 1.0)
+        return vals, aux[:6]
+
     S = 40
     ins = _loss_inputs(S=S, dark=dark)
     w = torch.tensor([0.03, 0.03, 0.03, 0.03, 1.0], device="cuda")
@@ -270,8 +275,8 @@ def test_fused_loss_terms_vs_tensor_ops(dark):
     (ref * w).sum().backward()
     leaves_b = [t.clone().requires_grad_(True) for t in ins]
     rgb, gt, albedo, sky, sv, pv, pe = leaves_b
-    for rep in range(2):                                                  # twice: the op's reduction scratch must come back clean
-        vals, minv = torch.ops.season_nerf.loss_terms(rgb, gt, albedo, sky, sv, pv.detach(), pe.detach(), None, 1)
+    for rep in range(2):                                                  # twice: the op's reduction scratch carries nothing from call to call
+        vals, minv = loss_terms(rgb, gt, albedo, sky, sv, pv.detach(), pe.detach(), None, 1)
         np.testing.assert_allclose(vals.detach().cpu().numpy(), ref.detach().cpu().numpy(), rtol=2e-6, atol=1e-7)
         np.testing.assert_array_equal(minv[:3].detach().cpu().numpy(), albedo.detach().min(0).values.cpu().numpy())
         np.testing.assert_array_equal(minv[3:].detach().view(torch.int32).cpu().numpy(), albedo.detach().min(0).indices.cpu().numpy())      # the row that owns each minimum
@@ -285,7 +290,7 @@ def test_fused_loss_terms_vs_tensor_ops(dark):
     assert bool((leaves_b[2].grad != 0).any()) == dark
     # data parallel: the global minimum and world size come in from outside (one MIN all-reduce by the caller)
     g_min = albedo.detach().min(0).values * torch.tensor([1.0, 0.5, 1.0], device="cuda")        # another rank owns channel 1's minimum
-    vals2, minv2 = torch.ops.season_nerf.loss_terms(rgb, gt, albedo, sky, sv, pv.detach(), pe.detach(), g_min, 2)
+    vals2, minv2 = loss_terms(rgb, gt, albedo, sky, sv, pv.detach(), pe.detach(), g_min, 2)
     h = torch.sum(torch.where(g_min < .2, (1 - g_min / .2) ** 2, torch.zeros_like(g_min))) / (2 * rgb.shape[0])
     np.testing.assert_allclose(float(vals2[3]), float(h), rtol=2e-6)
     albedo.grad = None
@@ -294,8 +299,8 @@ def test_fused_loss_terms_vs_tensor_ops(dark):
     assert not bool(own[:, 1].any()) and bool((albedo.grad[:, 1] == 0).all())                 # no gradient for a minimum this rank does not own
     if dark:
         assert bool((albedo.grad[:, 0] != 0).sum() == 1)
-    torch.library.opcheck(torch.ops.season_nerf.loss_terms.default, (rgb.detach(), gt.detach(), albedo.detach(), sky.detach(), sv.detach(), pv.detach(), pe.detach(),
-                                                                     None, 1), test_utils=("test_schema", "test_faketensor"))
+    torch.library.opcheck(torch.ops.season_nerf.loss_terms_all.default, (rgb.detach(), None, gt.detach(), albedo.detach(), sky.detach(), sv.detach(), pv.detach(), pe.detach(),
+                                                                         *[None] * 8, None, 1, 0, 0.03, 1.0, 1.0), test_utils=("test_schema", "test_faketensor"))
     # ties: a saturated albedo shared by several rows - torch.min hands the gradient to ONE row (the first), and so must the fused backward
     tied = albedo.detach().clone()
     tied[[5, 17, 40], 0] = 0.01
@@ -303,7 +308,7 @@ def test_fused_loss_terms_vs_tensor_ops(dark):
     ta = tied.clone().requires_grad_(True)
     tb = tied.clone().requires_grad_(True)
     _loss_terms_torch(rgb.detach(), gt, ta, sky.detach(), sv.detach(), pv, pe, S)[3].backward()
-    v3, m3 = torch.ops.season_nerf.loss_terms(rgb.detach(), gt, tb, sky.detach(), sv.detach(), pv.detach(), pe.detach(), None, 1)
+    v3, m3 = loss_terms(rgb.detach(), gt, tb, sky.detach(), sv.detach(), pv.detach(), pe.detach(), None, 1)
     v3[3].backward()
     assert m3[3:].view(torch.int32).tolist()[0] == 5 and m3[3:].view(torch.int32).tolist()[2] == 8
     np.testing.assert_allclose(tb.grad.cpu().numpy(), ta.grad.cpu().numpy(), rtol=1e-5, atol=1e-9)
@@ -319,7 +324,7 @@ def test_optimiser_step_runs_on_the_ops():
     with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU]) as prof:
         tool.train_step(data, 1)
     names = {e.key for e in prof.key_averages()}
-    for op in ["trainer_zero_grad_", "trainer_adam_step_", "loss_terms", "train_fwd_image", "train_bwd_image"]:
+    for op in ["trainer_zero_grad_", "trainer_adam_step_", "loss_terms_all", "train_fwd_image", "train_bwd_image"]:
         assert "season_nerf::" + op in names, (op, sorted(n for n in names if "season" in n))
     eng = net._train_engine
     with pytest.raises(RuntimeError, match="flat arenas"):

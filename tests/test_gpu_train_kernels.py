@@ -1,7 +1,6 @@
 """The element kernels of the training engine (csrc/train_kernels.hip), one launcher at a time through snerf_train_kernel_debug, against the
 float64 references of tests/train_kernel_cases.py: the encodings, the column passes of the SineLayer backward, sin(BN(z)), the BatchNorm
-finalisers, the thin input gradient, the point outputs, softmax / sigmoid, the small copies and reductions - and the fused loss terms at the sizes
-tests/test_gpu_ops.py does not reach, through their public calls.
+finalisers, the thin input gradient, the point outputs, softmax / sigmoid, the small copies and reductions.  (The fused loss terms: tests/test_gpu_loss_all.py.)
 
 Per case: inputs are the case's seeded fp32 arrays in buffers with padding columns (ld > C, ldd != ld) and two extra rows behind them; the padding
 of the inputs holds NaN, that of the outputs (and, before the call, every pure output) a sentinel that must come back untouched, bit for bit;
@@ -15,7 +14,7 @@ column passes, 16 instead of 4 for every case alike (train_kernel_cases.CHAIN_FA
 FACTOR = 4 colpass_vec_kernel<1> measured 1.07 x the tolerance at C = 4, M = 256, the CPU emulation of that chain from float64 quantities 0.93).
 No case is skipped or masked, NaN passes nowhere (the comparison is `err <= tol`).
 
-Measured on an MI355X (696 cases + 5 loss sizes, every call twice; no kernel failed, none was changed) - per kernel the largest E_ref over its cases
+Measured on an MI355X (696 cases, every call twice; no kernel failed, none was changed) - per kernel the largest E_ref over its cases
 and the worst deviation as a fraction of the tolerance:
     kernel                        E_ref     worst        kernel                        E_ref     worst
     pe_points_kernel              6.1e-08   0.161        point_out_fwd_kernel          2.4e-07   0.183
@@ -30,8 +29,8 @@ and the worst deviation as a fraction of the tolerance:
     bn_finalize_shifted_kernel    3.3e-03   0.326        reduce_rows_kernel            1.8e-07   0.150
     act_sums_finalize_kernel      1.7e-04   0.170        fill_zero_kernel, copy_f32_kernel, fill_zero_bytes_kernel,
     act_table_kernel              3.2e-08   0.101          copy_bytes_kernel           0         0 (exact)
-    sin_fwd_kernel                8.6e-07   0.234        loss terms (forward)          1.5e-07   0.164
-    sin_fwd_vec_kernel            1.0e-06   0.237        loss terms (backward)         1.1e-08   0.185
+    sin_fwd_kernel                8.6e-07   0.234
+    sin_fwd_vec_kernel            1.0e-06   0.237
     thin_dgrad_kernel<false>      2.5e-07   0.186
     thin_dgrad_kernel<true>       3.4e-02   0.246
 (the column sums at FACTOR = 4: colpass_vec_kernel<1> 1.073, <2> 0.857, <3> 0.836, <4> 0.653, colreduce_kernel 0.935, bn_bwd2_kernel 0.772 - all at C = 4;
@@ -138,74 +137,3 @@ def test_every_kernel_variant_is_reached(L):
     assert set(RETURNED.values()) == set(tk.KERNELS.values()), sorted(set(tk.KERNELS.values()) - set(RETURNED.values()))
     for k, (e, w) in sorted(FIGURES.items()):
         print(f"SUMMARY {k}: largest E_ref {e:.3e}, worst deviation / tolerance {w:.3f}")
-
-
-# ------------------------------------------------------------------------------------------------------------------ the fused loss terms
-def _loss_reference(a, S, dt):
-    rgb, gt, albedo, sky, sv, pv, pe = [x.astype(dt) for x in a]
-    R, Rs = rgb.shape[0], sv.shape[0]
-    d = sv - pv
-    x = (sky - dt(.5)) / dt(.5)
-    amin = albedo.min(0)
-    terms = {"sc": d * d, "sc2": pe * pv * sv, "sk": np.where(x > 0, x * x, 0), "col": (rgb - gt) ** 2}
-    sums = {k: np.sum(t, dtype=dt) for k, t in terms.items()}
-    h = np.sum(np.where(amin < dt(.2), (1 - amin / dt(.2)) ** 2, 0), dtype=dt)
-    vals = np.array([sums["sc"] / Rs, 1 - sums["sc2"] / Rs, sums["sk"] / (3 * R), h / R, sums["col"] / (3 * R)], dtype=dt)
-    scale = np.array([np.abs(terms["sc"]).sum() / Rs, 1 + np.abs(terms["sc2"]).sum() / Rs, terms["sk"].sum() / (3 * R), float(h) / R,
-                      terms["col"].sum() / (3 * R)], dtype=np.float64)
-    return vals, scale, amin, albedo.argmin(0)
-
-
-def _loss_grads(a, amin, arow, g5, dt):
-    rgb, gt, albedo, sky, sv, pv = [x.astype(dt) for x in a[:6]]
-    R, Rs = rgb.shape[0], sv.shape[0]
-    g = g5.astype(dt)
-    x = (sky - dt(.5)) / dt(.5)
-    inv3r, invr, invrs = dt(1) / dt(3 * R), dt(1) / dt(R), dt(1) / dt(Rs)
-    d_alb = np.zeros((R, 3), dtype=dt)
-    for c in range(3):
-        if amin[c] < .2:
-            d_alb[arow[c], c] = g[3] * dt(2) * (dt(1) - dt(amin[c]) / dt(.2)) * (dt(-1) / dt(.2)) * invr
-    return [g[4] * dt(2) * (rgb - gt) * inv3r, d_alb, np.where(x > 0, g[2] * dt(4) * x * inv3r, dt(0)), g[0] * dt(2) * (sv - pv) * invrs]
-
-
-@pytest.mark.parametrize("R,Rs,S", [(1, 1, 1), (257, 131, 7), (5547, 300, 40), (87400, 1000, 13), (1000, 87400 // 8, 30)],
-                         ids=["one-ray", "R257", "blocks-over-64", "R87400-over-1024-blocks", "sun-rays-over-1024-blocks"])
-def test_loss_terms_sizes_against_float64(L, R, Rs, S):
-    """snerf_loss_terms_forward / _backward at ray counts that are no multiple of 256, with more than 64 blocks for loss_finalize_kernel's one wave to
-    reduce and past the 1024-block cap of loss_partial_kernel (R = 87400: 262200 elements; and the same through the sun rays), against float64."""
-    r = tk.rng_for(f"loss-{R}-{Rs}-{S}")
-    u = lambda *s: r.uniform(0, 1, s).astype(np.float32)
-    host = [u(R, 3), u(R, 3), u(R, 3) * .8 + .05, u(R, 3), u(Rs, S), u(Rs, S), u(Rs, S) * .1]
-    v64, scale, amin, arow = _loss_reference(host, S, np.float64)
-    v32 = _loss_reference(host, S, np.float32)[0]
-    tol = tk.tolerance(np.abs(v32.astype(np.float64) - v64), scale)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.snerf_loss_scratch_bytes.restype = C.c_size_t
-    scratch = torch.zeros(L.snerf_loss_scratch_bytes(), dtype=torch.uint8, device="cuda")
-    assert L.snerf_loss_scratch_init(p(scratch), st) == 0
-    g5 = np.float32([.7, 0, .3, .9, 1.1])
-    for rep in range(2):
-        dev = [torch.from_numpy(x).cuda() for x in host]
-        vals, minv = torch.full((5,), float("nan"), device="cuda"), torch.full((6,), float("nan"), device="cuda")
-        rc = L.snerf_loss_terms_forward(C.c_int64(R), C.c_int64(Rs), C.c_int(S), *[p(t) for t in dev], None, C.c_int(1), p(scratch), p(vals), p(minv), st)
-        assert rc == 0, L.snerf_last_error().decode()
-        got = vals.cpu().numpy().astype(np.float64)
-        err = np.abs(got - v64)
-        print(f"FIG loss_terms R={R} Rs={Rs} S={S} E_ref={np.abs(v32 - v64).max():.3e} worst={np.max(np.where(err == 0, 0, err / np.maximum(tol, 1e-300))):.3f}")
-        assert (err <= tol).all(), (got, v64, tol)
-        m = minv.cpu().numpy()
-        np.testing.assert_array_equal(m[:3], amin)
-        np.testing.assert_array_equal(m[3:].view(np.int32), arow)
-        g = torch.from_numpy(g5).cuda()
-        outs = [torch.full((R, 3), float("nan"), device="cuda") for _ in range(3)] + [torch.full((Rs, S), float("nan"), device="cuda")]
-        rc = L.snerf_loss_terms_backward(C.c_int64(R), C.c_int64(Rs), C.c_int(S), *[p(t) for t in dev[:6]], p(minv), C.c_int(1), p(g), *[p(t) for t in outs], st)
-        assert rc == 0, L.snerf_last_error().decode()
-        want, want32 = _loss_grads(host, amin, arow, g5, np.float64), _loss_grads(host, amin, arow, g5, np.float32)
-        for name, o, w, w32 in zip(["d_rgb", "d_albedo", "d_sky", "d_sv"], outs, want, want32):
-            e = np.abs(o.cpu().numpy().astype(np.float64) - w)
-            e_ref = float(np.abs(w32.astype(np.float64) - w).max())
-            t = tk.tolerance(e_ref, np.abs(w))
-            print(f"FIG loss_bwd {name} R={R} E_ref={e_ref:.3e} worst={np.max(np.where(e == 0, 0, e / np.maximum(t, 1e-300))):.3f}")
-            assert (e <= t).all(), name

@@ -72,8 +72,10 @@ def test_reference_matches_the_closed_forms_and_the_key_order():
             assert wts[0] == pytest.approx(0.03 / width ** 2, rel=1e-12) and wts[1] == wts[0] and wts[2] == 0.03
             assert grads["rgb_merged"] is None or not grads["rgb_merged"].any()           # `Color` is a value only beside the adaptive loss
         else:
-            assert names == ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color", "Alpha_Adjust")
-            assert grads["rgb_merged"].any() and (grads["rgb"] is None or not grads["rgb"].any())
+            assert names == ("Solar_Correction", "Solar_Correction_2", "Sky_Color_Var", "Albedo_Color", "Color") + (("Alpha_Adjust",) if flags & lc.PRIOR else ())
+            on, off = ("rgb_merged", "rgb") if flags & lc.PRIOR else ("rgb", "rgb_merged")          # `Color` is formed on the merged colour in the prior phase
+            assert grads[on].any() and (grads[off] is None or not grads[off].any())
+            assert list(wts[:4]) == [0.03] * 4 and wts[4] == 1.0
         assert (grads["sky"] is None or not grads["sky"].any()) == bool(flags & lc.SKY_DETACHED)
         if flags & lc.PRIOR:
             assert grads["pe"].any()
@@ -100,7 +102,8 @@ def test_loss_all_entry_points_refuse_before_any_launch(lib):
     a = buf.ctypes.data
     assert lib.snerf_loss_all_scratch_bytes() >= 1024 * (17 * 8 + 3 * 8)
     assert [lib.snerf_loss_all_term_count(f) for f in (1, 3, 2, 5, 7, 6)] == [8, 12, 6, 8, 12, 6]
-    for f in (0, 4, 8, -1):
+    assert [lib.snerf_loss_all_term_count(f) for f in (0, 4)] == [5, 5]
+    for f in (8, -1):
         assert lib.snerf_loss_all_term_count(f) == -1 and b"flags" in lib.snerf_last_error()
 
     def full(flags=3, **kw):
@@ -127,9 +130,10 @@ def test_loss_all_entry_points_refuse_before_any_launch(lib):
         refused.append(word)
 
     check(fwd(None), "NULL input")
-    check(fwd(full(flags=0)), "flags")
-    check(fwd(full(flags=4)), "flags")
     check(fwd(full(flags=8)), "flags")
+    for f in (0, 4):      # the MSE free phase is a served configuration: the call gets as far as its outputs, with no pointer of the other configurations
+        none = {k: None for k in ("d_rgb_merged", "d_pe", "d_pe_supervised", "d_alpha_color", "d_scale_color", "d_alpha_alpha", "d_scale_alpha", "d_logz_value", "d_logz_slope")}
+        assert fwd(full(flags=f, **none), scratch=None) == -1 and b"NULL scratch" in lib.snerf_last_error()
     for k in ("n_rays", "n_solar_rays", "n_samples", "world"):
         check(fwd(full(**{k: 0})), "counts")
     check(fwd(full(n_rays=1 << 31)), "counts")
@@ -151,4 +155,4 @@ def test_loss_all_entry_points_refuse_before_any_launch(lib):
     check(bwd(full(), grads(), g=None), "NULL aux")
     for k in ("d_g_rgb", "d_g_albedo", "d_g_sky", "d_g_solar_vis", "d_g_rgb_merged", "d_g_pe", "d_g_alpha_color", "d_g_scale_color", "d_g_alpha_alpha", "d_g_scale_alpha"):
         check(bwd(full(), grads(**{k: None})), "NULL gradient output")
-    assert len(refused) == 43
+    assert len(refused) == 41

@@ -2,7 +2,8 @@
 """Do two csrc trees give the same device code?   python tools/kernel_identity.py OLD_CSRC NEW_CSRC kernels.hip kernels_ks.hip ...
 
 Each source is compiled in both trees with build.py's FLAGS + EXTRA and `-S --cuda-device-only`; the listing is cut per function symbol (kernels and
-the device functions they call), and comments, labels and assembler directives are dropped.  Prints IDENTICAL or DIFF per symbol with the instruction
+the device functions they call), comments, labels and assembler directives are dropped, and the function number inside branch targets (.LBB<fn>_<n>) is
+taken out: it is the function's position in the module, so that adding or removing one function would report every later one.  Prints IDENTICAL or DIFF per symbol with the instruction
 counts of both sides, and every difference in the kernels' metadata (registers, spills, scratch, LDS).  Exit status 1 on any DIFF.  Whole instruction
 streams are compared, whatever they contain.  --asm-dir DIR keeps the listings (DIR/old, DIR/new); a listing newer than every file of its tree is
 reused, so the unchanged side of a comparison is compiled once.  --flags "-DSNERF_ABLATE -DABL=2" appends flags to both sides (a diagnostic
@@ -40,6 +41,7 @@ def functions(asm):
         elif re.match(r"\s*\.size\s", line):
             cur = None
         text = re.sub(r"\s+", " ", re.split(r";|//", line)[0]).strip()
+        text = re.sub(r"\.LBB\d+_", ".LBB_", text)      # a branch label carries its function's position in the module: not code, and it moves when a function above goes
         if cur is not None and text and not text.endswith(":") and not text.startswith("."):
             cur.append(text)
     return out
